@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark: device-resident RS encode + decode of 1 MiB chunks on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--cpu-seconds S] [--workload c2c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--workload c2c3|c4|c5]
+    python bench.py --full [--cpu-seconds S] [--no-cpu] [--no-e2e] [--no-c4] [--no-c5] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -33,6 +34,14 @@ pinned host memory (the kernels read and write the host buffers over PCIe: the p
 zero-copy path); value = job bytes encoded + decoded per step / max-over-ranks time.  The
 device-resident kernel rates and the staged (pageable -> pinned slabs -> hipMemcpyAsync) rate
 are reported beside it.
+
+A plain run sets up, warms up, times --steps steps (`ms_per_step` = the timed region / steps),
+writes the last step's outputs when --dump-outputs DIR is given (dump_outputs(); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output) and prints
+the line.  `roofline` and `encode_kernel` below come from the timed steps themselves.  Everything
+that takes work of its own (cpu_baseline, decode_recover_only_kernel, e2e, the nested c4 / c5
+objects and in_process lines, and under --workload c4 / c5 the CPU baseline and the staged rates)
+is measured only with --full.
 
 Also reported on the headline line:
   roofline      the decode kernel, the dominant one by time: algorithmic bytes per launch
@@ -135,7 +144,22 @@ def parse(argv=None):
     ap.add_argument("--no-in-process", action="store_true",
                     help="c2c3 under N > 1 ranks: skip the nested in-process measurement rank 0 takes after the "
                          "rank-per-GPU lines (the other ranks wait on a CPU barrier meanwhile)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the line's own figure: CPU baselines, the recover-only "
+                         "decode, the host-buffer (e2e / staged) rates, the nested c4 / c5 objects and the nested "
+                         "in-process lines; the --no-* options then drop single parts.  Without it a run sets up, "
+                         "warms up, times its steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2c3: after the timed steps write what the last step computed (parity blocks and "
+                         "reassembled chunks) to DIR/<name>.npy, see dump_outputs()")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and (args.workload != "c2c3" or args.in_process):
+        ap.error("--dump-outputs belongs to the headline workload (c2c3) in its rank form")
+    if not args.full:
+        args.no_cpu = args.no_e2e = args.no_recover = args.no_c4 = args.no_c5 = args.no_in_process = True
+    return args
 
 
 # ---------------------------------------------------------------- ranks
@@ -505,6 +529,31 @@ def recover_only_rate(eng, torch, src, par, nchunks, n, k, m, B, reps=10) -> dic
             "avg_launch_ms": round(t * 1e3, 4), "launches": nl}
 
 
+DUMP_SAMPLE = 1 << 22  # sampled bytes per dumped array: 16 MiB as float32
+
+
+def dump_outputs(dirname, rank, world, nchunks, arrays) -> None:
+    """--dump-outputs: `arrays` maps a name to a uint8 tensor of `nchunks` equal rows (what the
+    caller of the timed path receives).  Each gives two files, so that two builds can be compared
+    output for output: <name>.npy, the bytes at DUMP_SAMPLE positions drawn once with seed 0
+    (sorted; the whole array when it is no longer than that) as float32, and <name>_chunk_sums.npy,
+    every chunk's byte sum over the WHOLE array as float64 (exact).  With more than one rank the
+    names carry `_rank<r>`."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE, dtype=np.int64))
+            t_s = t[torch.from_numpy(idx).to(t.device)]
+        else:
+            t_s = t
+        np.save(os.path.join(dirname, f"{name}{tag}.npy"), t_s.cpu().numpy().astype(np.float32))
+        sums = t.view(nchunks, -1).sum(dim=1, dtype=torch.int64)
+        np.save(os.path.join(dirname, f"{name}_chunk_sums{tag}.npy"), sums.cpu().numpy().astype(np.float64))
+
+
 # ---------------------------------------------------------------- BASELINE configs[1]+[2] (headline)
 def c2c3_run(ctx, steps, warmup, nchunks=N_CHUNKS, events=True):
     """This rank's 1024 x 1 MiB RS(4,2) encode + {1,3}-erased decode; returns the rank's numbers
@@ -540,7 +589,8 @@ def c2c3_run(ctx, steps, warmup, nchunks=N_CHUNKS, events=True):
 
     counts = D.gather_counts(ctx.dmod, nchunks, ctx.rank, ctx.world, ctx.local)
     return {"el_max": el_max, "B": B, "chunks": nchunks, "per_rank_chunks": counts, "enc_avg_s": enc_avg_s,
-            "enc_launches": enc_n, "dec_avg_s": dec_avg_s, "dec_launches": dec_n, "src": src, "par": par}
+            "enc_launches": enc_n, "dec_avg_s": dec_avg_s, "dec_launches": dec_n, "src": src, "par": par,
+            "out": out}
 
 
 def main_c2c3(args, ctx):
@@ -548,6 +598,8 @@ def main_c2c3(args, ctx):
 
     r = c2c3_run(ctx, args.steps, args.warmup, args.chunks, events=not args.no_events)
     nchunks, n, k, m, B = args.chunks, CHUNK, K, M, r["B"]
+    if args.dump_outputs:  # the last timed step's parity and reassembled chunks, before anything else runs
+        dump_outputs(args.dump_outputs, ctx.rank, ctx.world, nchunks, {"parity": r["par"], "decoded": r["out"]})
     bytes_per_step = 2 * nchunks * n  # encoded + decoded chunk bytes
     total_chunks = sum(r["per_rank_chunks"])
     value = args.steps * 2 * total_chunks * n / r["el_max"] / GIB
@@ -598,7 +650,7 @@ def main_c2c3(args, ctx):
 
     # BASELINE configs[3] and [4] on the same run, after the headline's timed region (VERDICT r03
     # item 1): each its own line's fields, nested; every rank takes part (its share of the job)
-    r.pop("src"), r.pop("par")
+    r.pop("src"), r.pop("par"), r.pop("out")
     sub_cpu = 0 if args.no_cpu else args.sub_cpu_seconds
     if not args.no_c4:
         c4 = c4_result(args, ctx, sub_cpu, args.steps, args.warmup)

@@ -28,8 +28,8 @@ def _run(args, extra_env=None, timeout=240):
 
 @pytest.mark.timeout(300)
 def test_bench_gpus2_c2c3_spawns_two_ranks():
-    p, lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--chunks", "3", "--no-cpu", "--no-e2e",
-                     "--c4-chunks", "12", "--c5-bytes", str(6 << 20), "--c5-steps", "1"],
+    p, lines = _run(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--chunks", "3", "--no-cpu",
+                     "--no-e2e", "--c4-chunks", "12", "--c5-bytes", str(6 << 20), "--c5-steps", "1"],
                     {"STORB_STUB_SLOW_RANK": "1"})
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout  # rank 0 only
@@ -85,7 +85,7 @@ def test_bench_world_size_mismatch_exits_nonzero():
 @pytest.mark.timeout(300)
 def test_bench_gpus1_c4_cpu_baseline_line():
     # N = 1: no children; the c4 line carries its CPU baseline (the oracle's RS(10,4) encode)
-    p, lines = _run(["--workload", "c4", "--steps", "1", "--warmup", "1", "--c4-chunks", "8",
+    p, lines = _run(["--full", "--workload", "c4", "--steps", "1", "--warmup", "1", "--c4-chunks", "8",
                      "--cpu-seconds", "0.3"])
     assert p.returncode == 0, p.stderr[-3000:]
     j = json.loads(lines[0])
@@ -100,8 +100,9 @@ def test_bench_gpus1_c4_cpu_baseline_line():
 def test_bench_gpus1_c2c3_nests_c4_c5_with_cpu_baselines():
     """N = 1 headline line: configs[3] and [4] measured in the same run, each with its roofline and
     its own CPU baseline."""
-    p, lines = _run(["--steps", "1", "--warmup", "1", "--chunks", "2", "--no-e2e", "--cpu-seconds", "0.2",
-                     "--sub-cpu-seconds", "0.2", "--c4-chunks", "8", "--c5-bytes", str(4 << 20), "--c5-steps", "1"])
+    p, lines = _run(["--full", "--steps", "1", "--warmup", "1", "--chunks", "2", "--no-e2e", "--cpu-seconds",
+                     "0.2", "--sub-cpu-seconds", "0.2", "--c4-chunks", "8", "--c5-bytes", str(4 << 20),
+                     "--c5-steps", "1"])
     assert p.returncode == 0, p.stderr[-3000:]
     j = json.loads(lines[0])
     assert j["cpu_baseline"]["kind"] == "port"
@@ -134,8 +135,9 @@ def test_bench_gpus_n_headline_line_with_in_process(n):
     """`bench.py --gpus N`: the headline line with c4 / c5 nested and, after them, the in-process
     form (EngineGroup over N stub engines) nested as `in_process`."""
     c5_bytes = 8 << 20
-    p, lines = _run(["--gpus", str(n), "--steps", "1", "--warmup", "1", "--chunks", "2", "--no-cpu", "--no-e2e",
-                     "--c4-chunks", str(2 * n), "--c5-bytes", str(c5_bytes), "--c5-steps", "1"], timeout=540)
+    p, lines = _run(["--full", "--gpus", str(n), "--steps", "1", "--warmup", "1", "--chunks", "2", "--no-cpu",
+                     "--no-e2e", "--c4-chunks", str(2 * n), "--c5-bytes", str(c5_bytes), "--c5-steps", "1"],
+                    timeout=540)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout
     j = json.loads(lines[0])
@@ -193,10 +195,87 @@ def test_c4_default_job_splits_8_x_8192():
 def test_bench_in_process_mode_stub():
     """`bench.py --gpus 4 --in-process`: one process, the line's value is the in-process headline."""
     c5_bytes = 8 << 20
-    p, lines = _run(["--gpus", "4", "--in-process", "--steps", "1", "--warmup", "1", "--chunks", "2",
+    p, lines = _run(["--full", "--gpus", "4", "--in-process", "--steps", "1", "--warmup", "1", "--chunks", "2",
                      "--c5-bytes", str(c5_bytes), "--c5-steps", "1"])
     assert p.returncode == 0, p.stderr[-3000:]
     j = json.loads(lines[0])
     assert j["n_gpus"] == 4 and j["config"]["world_size"] == 1 and "in-process x4" in j["config"]["parallelism"]
     assert j["value"] == j["in_process"]["c2c3"]["value"]
     _check_in_process(j["in_process"], 4, c5_bytes)
+
+
+# ---- the plain run and --dump-outputs ----
+FULL_ONLY = ("c4", "c5", "e2e", "decode_recover_only_kernel", "in_process")
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W`: nothing but the headline's own figures on the line;
+    --dump-outputs writes the last step's parity and reassembled chunks, the same from run to run,
+    and they are the oracle's bytes for the seeded input."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import cfec
+
+    nch, n, k, m = 3, bench.CHUNK, bench.K, bench.M
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        p, lines = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--chunks", str(nch),
+                         "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert len(lines) == 1, p.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["dtype"] == "u8" and j["higher_is_better"] is True
+        assert j["value"] == pytest.approx(2 * 2 * nch * n / (j["ms_per_step"] * 2 / 1e3) / (1 << 30), rel=0.02)
+        assert j["roofline"]["launches"] == 2 and j["encode_kernel"]["launches"] == 2  # --steps timed steps
+        assert j["cpu_baseline"] is None and not [f for f in FULL_ONLY if f in j]
+        assert sorted(os.listdir(d)) == ["decoded.npy", "decoded_chunk_sums.npy", "parity.npy",
+                                         "parity_chunk_sums.npy"]
+        dumps.append({f: np.load(d / f) for f in os.listdir(d)})
+        assert sum(a.nbytes for a in dumps[-1].values()) <= 64 << 20
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, dumps[1][f]), f
+
+    g = torch.Generator(device="cpu")
+    g.manual_seed(1000)  # rank 0's input, as c2c3_run draws it
+    src = torch.randint(0, 256, (nch * n,), dtype=torch.uint8, generator=g).numpy()
+    par = np.frombuffer(b"".join(b"".join(cfec.easy_encode(src[c * n:(c + 1) * n].tobytes(), k, m)[k:])
+                                 for c in range(nch)), np.uint8)
+    for name, want in (("decoded", src), ("parity", par)):
+        assert want.size <= bench.DUMP_SAMPLE  # small enough to be dumped whole
+        assert np.array_equal(dumps[0][name + ".npy"], want.astype(np.float32)), name
+        assert np.array_equal(dumps[0][name + "_chunk_sums.npy"], want.reshape(nch, -1).sum(axis=1, dtype=np.float64))
+
+
+def test_dump_outputs_samples_a_large_array(tmp_path):
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    t = (torch.arange(bench.DUMP_SAMPLE * 2 + 64, dtype=torch.int64) * 7 % 251).to(torch.uint8)
+    bench.dump_outputs(str(tmp_path), 1, 2, 2, {"x": t})
+    s, sums = np.load(tmp_path / "x_rank1.npy"), np.load(tmp_path / "x_chunk_sums_rank1.npy")
+    idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), bench.DUMP_SAMPLE, dtype=np.int64))
+    assert s.dtype == np.float32 and np.array_equal(s, t.numpy()[idx].astype(np.float32))
+    assert sums.dtype == np.float64 and np.array_equal(sums, t.numpy().reshape(2, -1).sum(axis=1, dtype=np.float64))
+
+
+def test_bench_rejects_zero_steps_and_dump_of_other_workloads():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    for argv in (["--steps", "0"], ["--workload", "c4", "--dump-outputs", "x"],
+                 ["--in-process", "--dump-outputs", "x"]):
+        with pytest.raises(SystemExit) as e:
+            bench.parse(argv)
+        assert e.value.code == 2
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.no_cpu and a.no_e2e and a.no_recover and a.no_c4 and a.no_c5 and a.no_in_process
+    a = bench.parse(["--full", "--no-c5"])
+    assert a.full and a.no_c5 and not (a.no_cpu or a.no_e2e or a.no_recover or a.no_c4 or a.no_in_process)

@@ -9,7 +9,7 @@ V=$R/build/variants/libstorbec_${VAR:-p12}.so
 for i in 1 2; do
   for L in base var; do
     if [ $L = var ]; then export STORB_EC_LIB=$V; else unset STORB_EC_LIB; fi
-    echo "== $L $i c5" && timeout -k 10 300 python3 -u bench.py --workload c5 --steps 20 --warmup 3 --no-cpu > $O/pt_${L}_${i}_c5.log 2>&1 || { tail -20 $O/pt_${L}_${i}_c5.log; exit 1; }
+    echo "== $L $i c5" && timeout -k 10 300 python3 -u bench.py --full --workload c5 --steps 20 --warmup 3 --no-cpu > $O/pt_${L}_${i}_c5.log 2>&1 || { tail -20 $O/pt_${L}_${i}_c5.log; exit 1; }
     echo "== $L $i stream" && timeout -k 10 400 python3 -u tools/stream_rate.py --mib 1024 --reps 2 > $O/pt_${L}_${i}_stream.json 2> $O/pt_${L}_${i}_stream.err || { tail -20 $O/pt_${L}_${i}_stream.err; exit 1; }
     echo "== $L $i small" && timeout -k 10 300 python3 -u tools/small_call_profile.py --reps 100 > $O/pt_${L}_${i}_small.json 2> $O/pt_${L}_${i}_small.err || { tail -20 $O/pt_${L}_${i}_small.err; exit 1; }
   done

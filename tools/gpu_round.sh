@@ -15,12 +15,12 @@ if [ -z "$SKIP_PMC" ]; then  # first, so the bench lines below carry this build'
   for W in c2 c4 c5; do echo "== pmc $W" && bash tools/gpu_pmc.sh $W > $O/pmc_$W.log 2>&1 || { tail -30 $O/pmc_$W.log; exit 1; }
     cp $O/pmc_$W.json $R/profiles/pmc_$W.json; done
 fi
-echo "== bench" && timeout -k 10 300 python3 -u bench.py > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
+echo "== bench" && timeout -k 10 300 python3 -u bench.py --full > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
 tail -1 $O/bench.log
 echo "== rocprofv3 stats" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu --no-e2e --no-recover --no-c4 --no-c5 > $O/prof.log 2>&1 || { tail -30 $O/prof.log; exit 1; }
-echo "== bench c4" && timeout -k 10 300 python3 -u bench.py --workload c4 > $O/bench_c4.log 2>&1 || { tail -30 $O/bench_c4.log; exit 1; }
+echo "== bench c4" && timeout -k 10 300 python3 -u bench.py --full --workload c4 > $O/bench_c4.log 2>&1 || { tail -30 $O/bench_c4.log; exit 1; }
 tail -1 $O/bench_c4.log
-echo "== bench c5" && timeout -k 10 300 python3 -u bench.py --workload c5 > $O/bench_c5.log 2>&1 || { tail -30 $O/bench_c5.log; exit 1; }
+echo "== bench c5" && timeout -k 10 300 python3 -u bench.py --full --workload c5 > $O/bench_c5.log 2>&1 || { tail -30 $O/bench_c5.log; exit 1; }
 tail -1 $O/bench_c5.log
 echo "== rehearse --gpus 2 (two ranks on one GPU, gloo)" && bash tools/gpu_rehearse_n2.sh > $O/rehearse.log 2>&1 || { tail -30 $O/rehearse.log; exit 1; }
 cat $O/rehearse.log
