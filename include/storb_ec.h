@@ -134,7 +134,8 @@ int sec_sync(sec_ctx *ctx);
  * event pair around its encode / decode kernels on the launch stream. */
 int sec_ctx_set_timing(sec_ctx *ctx, int enable);
 /* Waits for recorded pairs, returns the summed milliseconds and launch count of
- * kind 0 = encode, 1 = decode, 2 = SHA-1, 3 = bignum (APDP), and clears them. */
+ * kind 0 = encode, 1 = decode, 2 = SHA-1, 3 = bignum (APDP), 4 = repair (its kernels and,
+ * with digests, their SHA-1), and clears them. */
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches);
 
 /* ---- context options --------------------------------------------------------
@@ -205,6 +206,64 @@ int sec_decode_batch_ex(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchun
                         const int32_t *sharenums, const uint64_t *block_offs,
                         const uint64_t *block_avail, const uint8_t *blocks, uint8_t *out,
                         unsigned flags);
+
+/* ---- repair: lost pieces regenerated from any k survivors ---------------------------------
+ * A miner is gone; the validator still reaches k other pieces of the chunk and needs the lost
+ * pieces back AS PIECES, data or parity, to seed them elsewhere, and their piece ids to check
+ * against what it recorded at upload.  Block t of the code word is a fixed GF(2^8) combination of
+ * any k blocks: row t of zfec's encode matrix times the inverse sec_decode_matrix returns.  No
+ * zfec counterpart: the reference would decode the chunk and encode it again.
+ *
+ * sec_repair_matrix (host arithmetic, no device needed): the ntargets x k matrix, row-major, row r
+ * for block targets[r], columns in the caller's sharenum order, so that
+ *     block targets[r] = XOR_j out[r*k + j] * (block sharenums[j]).
+ * Errors, checked in this order and shared with sec_repair_batch (there before any device work):
+ * SEC_EINVAL ntargets < 0 or a NULL array; SEC_EKM; SEC_ESHARENUM a source or target outside
+ * [0, m); SEC_EDUPSHARE a repeated source, a repeated target, or a target that is also a source
+ * (repair never copies a block the caller already holds).  ntargets == 0 is valid and writes
+ * nothing. */
+int sec_repair_matrix(int k, int m, const int32_t *sharenums, const int32_t *targets, int ntargets,
+                      uint8_t *out);
+
+/* One chunk to repair.  Its k source blocks are entries slot0 .. slot0+k-1 of sharenums[] /
+ * block_offs[] / block_avail[] (as sec_dec_chunk's), its lost blocks entries tgt0 ..
+ * tgt0+ntargets-1 of target_nums[] / target_offs[]. */
+typedef struct sec_rep_chunk {
+    uint64_t B;      /* block bytes                                                     */
+    uint64_t slot0;  /* first of the chunk's k entries in sharenums[] / block_offs[] /
+                        block_avail[]                                                   */
+    uint64_t tgt0;   /* first of its ntargets entries in target_nums[] / target_offs[]  */
+    int32_t ntargets;
+    int32_t k;
+    int32_t m;
+    int32_t pad;
+} sec_rep_chunk; /* 40 bytes */
+
+/* For every chunk, block target_nums[tgt0 + j] is written at out + target_offs[tgt0 + j], all B
+ * bytes of it (for data block k-1 too: zfec's zero padding is part of the piece), in the caller's
+ * target order, from the k blocks at blocks + block_offs[slot0 + i] numbered sharenums[slot0 + i].
+ * Every target is its own buffer at any byte alignment.  `blocks` or `out` may be NULL: the
+ * offsets are then absolute addresses.  block_avail (nullable) as in sec_decode_batch_ex: that
+ * many bytes of a source exist, the rest read as zero, and nothing past them is read.
+ * digests (nullable): 20 bytes per target at digests + 20 (tgt0 + j), the SHA-1 of the repaired
+ * piece (storb's piece id), computed by the SHA-1 kernel while the targets are device-resident;
+ * digests live where the targets do (device memory, or host memory with SEC_F_HOST).
+ * More than 8 targets of a chunk take ceil(ntargets / 8) passes over its sources.
+ * Aliasing: no target range may overlap a source block or another target of any chunk in the
+ * call: workgroups read sources while others write targets, so an overlap gives unspecified
+ * bytes.  The library does not check this (sec_decode_batch's rule).
+ * Flags: none (device pointers; SEC_F_ASYNC allowed) or SEC_F_HOST (host pointers; SEC_F_ASYNC
+ * is then SEC_EINVAL); any other flag is SEC_EINVAL.  SEC_F_HOST is ALWAYS staged: the sources
+ * are gathered into pinned slabs and the targets and digests scattered back from them.  Unlike
+ * the encode / decode host paths it never page-locks a caller's buffer for the call and never
+ * runs the kernels on caller memory in place, pinned or not; sec_ctx_host_paths counts every
+ * such call as staged.
+ * Errors: sec_repair_matrix's per chunk, SEC_ESIZE for B >= 2^31. */
+int sec_repair_batch(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks,
+                     const int32_t *sharenums, const uint64_t *block_offs,
+                     const uint64_t *block_avail, const uint8_t *blocks,
+                     const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out,
+                     uint8_t *digests, unsigned flags);
 
 /* ---- piece ids: SHA-1 (piece_hash, /root/reference/storb/util/piece.py:54-68) ----
  * A message is `len` bytes at `addr`, of which the first `avail` exist in

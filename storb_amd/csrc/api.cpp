@@ -19,6 +19,7 @@
 #include <sys/mman.h>
 
 #include <algorithm>
+#include <array>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -290,6 +291,9 @@ struct SubPlan {
     uint32_t nsegs = 0, max_seg = 0;       // segment count; most segments of one message
     uint64_t dig_first = 0;                // first digest slot of this unit
     uint64_t dig_off = 0;                  // host mode: digests' offset in the slab output
+    size_t off_toff = 0;                   // repair: the targets' addresses (RepSlots::tgt_off)
+    // repair digests: runs of consecutive digest slots, (first message, count, first slot)
+    std::vector<std::array<uint64_t, 3>> sha_runs;
     // syndrome decodes (decode): phase 1 launches (bit-sliced syndromes) and phase 2 launches
     // (the Cauchy solve), one each per shape
     // (shape, (first, count)) in tiles; synf: the fused kernel (both phases in one wave)
@@ -641,13 +645,13 @@ struct sec_ctx {
     hipStream_t own = nullptr;
     hipStream_t ext = nullptr;
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[4];
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[5];
     std::vector<hipEvent_t> ev_pool;
     hipEvent_t stop_ev = nullptr;  // between timing_begin and timing_end of an attached launch
     PinBuf pin{nullptr, 0, false};  // metadata image staging (its own, not pooled: small, every call)
     hipEvent_t pin_ev = nullptr, meta_ev = nullptr;
-    TableCache enc_tabs, dec_tabs;
-    Plan enc_plan, dec_plan, sha_plan, bn_plan;
+    TableCache enc_tabs, dec_tabs, rep_tabs;
+    Plan enc_plan, dec_plan, sha_plan, bn_plan, rep_plan;
     DevBuf bn_scratch;  // host-mode staging of sec_bn_modexp / mulmod operands
     DevBuf bn_part;     // partial residues of segmented reductions (one region per slot)
     DevBuf syn;         // syndrome rows of device-mode syndrome decodes
@@ -889,6 +893,29 @@ int check_sharenums(int k, int m, const int32_t *s)
         if (seen[s[i]])
             return SEC_EDUPSHARE;
         seen[s[i]] = true;
+    }
+    return SEC_OK;
+}
+
+// Preconditions of a repair (sec_repair_matrix, sec_repair_batch): k distinct sources and nt
+// distinct targets in [0, m), no target among the sources (repair never copies a block the
+// caller already holds).
+int check_repair(int k, int m, const int32_t *sources, const int32_t *targets, int nt)
+{
+    if (nt < 0 || !sources || (nt > 0 && !targets))
+        return SEC_EINVAL;
+    if (k < 1 || m < k || m > 256)
+        return SEC_EKM;
+    RC(check_sharenums(k, m, sources));
+    bool seen[256] = {false};
+    for (int i = 0; i < k; ++i)
+        seen[sources[i]] = true;
+    for (int i = 0; i < nt; ++i) {
+        if (targets[i] < 0 || targets[i] >= m)
+            return SEC_ESHARENUM;
+        if (seen[targets[i]])
+            return SEC_EDUPSHARE;
+        seen[targets[i]] = true;
     }
     return SEC_OK;
 }
@@ -1462,6 +1489,200 @@ int launch_decode_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
     return SEC_OK;
 }
 
+// ---- repair plan --------------------------------------------------------------
+// A sibling of the decode plan's direct branch: no syndrome choice and no copies.  Per chunk the
+// repair matrix's tables (layout [slot][target][5], cached by sources and targets), the k slots
+// in normalised order, one address per target, tiles as a copy-free decode's (add_work), and one
+// SHA-1 message per target when digests are asked for.
+struct RepLayout {
+    std::vector<int> perm, idx;
+    std::vector<uint64_t> first;  // per chunk: start in perm / idx
+};
+
+RepLayout rep_layout(const sec_rep_chunk *chunks, int64_t nchunks, const int32_t *sharenums)
+{
+    RepLayout L;
+    L.first.resize((size_t)nchunks);
+    std::vector<int> idx, perm;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const sec_rep_chunk &c = chunks[i];
+        idx.assign(sharenums + c.slot0, sharenums + c.slot0 + c.k);
+        sec::normalise_slots(c.k, idx, perm);
+        L.first[i] = L.perm.size();
+        L.perm.insert(L.perm.end(), perm.begin(), perm.end());
+        L.idx.insert(L.idx.end(), idx.begin(), idx.end());
+    }
+    return L;
+}
+
+uint64_t rep_avail(const sec_rep_chunk &c, const uint64_t *block_avail, int j)
+{
+    return block_avail ? std::min<uint64_t>(block_avail[c.slot0 + j], c.B) : c.B;
+}
+
+int build_repair_plan(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks, const uint64_t *block_offs,
+                      const uint64_t *block_avail, const int32_t *target_nums, const uint64_t *target_offs,
+                      const RepLayout &L, bool host, bool digest)
+{
+    Plan &plan = ctx->rep_plan;
+    TableCache &tc = ctx->rep_tabs;
+    std::vector<PendingExpand> pending;
+    std::vector<uint32_t> tab_of((size_t)nchunks, 0);
+    for (int attempt = 0;; ++attempt) {
+        pending.clear();
+        size_t need = 0;
+        bool overflow = false;
+        for (int64_t i = 0; i < nchunks && !overflow; ++i) {
+            const sec_rep_chunk &c = chunks[i];
+            const int k = c.k, nt = c.ntargets;
+            if (nt == 0)
+                continue;
+            const int *idx = &L.idx[L.first[i]];
+            std::string key = std::to_string(k) + "/" + std::to_string(c.m) + ":";
+            for (int s = 0; s < k; ++s)
+                key += std::to_string(idx[s]) + ",";
+            key += "|";
+            for (int r = 0; r < nt; ++r)
+                key += std::to_string(target_nums[c.tgt0 + r]) + ",";
+            auto it = tc.index.find(key);
+            if (it != tc.index.end()) {
+                tab_of[i] = it->second;
+                continue;
+            }
+            std::vector<uint8_t> rm, coef((size_t)k * nt);
+            if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k),
+                                    std::vector<int>(target_nums + c.tgt0, target_nums + c.tgt0 + nt), rm))
+                return SEC_ESINGULAR;
+            for (int s = 0; s < k; ++s)
+                for (int r = 0; r < nt; ++r)
+                    coef[(size_t)s * nt + r] = rm[(size_t)r * k + s];
+            need += coef.size() * sec::kTabDwords;
+            uint32_t off = 0;
+            if (table_ensure(tc, key, std::move(coef), pending, &off)) {
+                overflow = true;
+                break;
+            }
+            tab_of[i] = off;
+        }
+        if (!overflow)
+            break;
+        if (attempt == 1)
+            return SEC_ENOMEM;
+        RC(table_reset(ctx, tc, need * 2 + ((size_t)1 << 18)));
+    }
+
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    if (host) {
+        std::vector<uint64_t> ib((size_t)nchunks);
+        for (int64_t i = 0; i < nchunks; ++i)
+            ib[i] = (uint64_t)chunks[i].k * chunks[i].B;
+        // with digests few large slabs, as the encode's digest mode (one SHA-1 chain per piece)
+        ranges = slabs_of(ib, (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
+    } else {
+        ranges.emplace_back(0, nchunks);
+    }
+    Image img;
+    plan.subs.clear();
+    for (auto [c0, c1] : ranges) {
+        SubPlan sp;
+        sp.c0 = c0;
+        sp.c1 = c1;
+        std::vector<sec::RepDesc> descs((size_t)(c1 - c0));
+        std::vector<uint64_t> soff, toff;
+        std::vector<uint32_t> savail;
+        std::vector<sec::MsgDesc> msgs;
+        Bins bins;
+        std::vector<sec::TailItem> tail;
+        for (int64_t i = c0; i < c1; ++i) {
+            const sec_rep_chunk &c = chunks[i];
+            const uint64_t base = L.first[i];
+            sec::RepDesc &d = descs[i - c0];
+            d.B = (uint32_t)c.B;
+            d.k = (uint32_t)c.k;
+            d.nt = (uint32_t)c.ntargets;
+            d.tab = tab_of[i];
+            d.slot0 = (uint32_t)soff.size();
+            d.tgt0 = (uint32_t)toff.size();
+            d.pad = 0;
+            uint64_t min_avail = c.B;
+            for (int s = 0; s < c.k; ++s) {
+                const int from = L.perm[base + s];
+                soff.push_back(host ? sp.in_bytes + (uint64_t)s * c.B : block_offs[c.slot0 + from]);
+                const uint64_t av = host ? c.B : rep_avail(c, block_avail, from);  // staged slots are zero-filled
+                savail.push_back((uint32_t)av);
+                min_avail = std::min(min_avail, av);
+            }
+            d.valid = (uint32_t)min_avail;
+            for (int r = 0; r < c.ntargets; ++r) {
+                const uint64_t to = host ? sp.out_bytes + (uint64_t)r * c.B : target_offs[c.tgt0 + r];
+                if (digest) {
+                    // device mode: the caller's digest slot tgt0 + r; consecutive slots share a launch
+                    const uint64_t slot = host ? msgs.size() : c.tgt0 + (uint64_t)r;
+                    if (sp.sha_runs.empty() || sp.sha_runs.back()[2] + sp.sha_runs.back()[1] != slot)
+                        sp.sha_runs.push_back({(uint64_t)msgs.size(), 0, slot});
+                    ++sp.sha_runs.back()[1];
+                    msgs.push_back(sec::MsgDesc{to, c.B, c.B, 0, 0});
+                }
+                toff.push_back(to);
+            }
+            sp.in_bytes += (uint64_t)c.k * c.B;
+            sp.out_bytes += (uint64_t)c.ntargets * c.B;
+            if (c.ntargets > 0)
+                add_work(bins, tail, (uint32_t)(i - c0), c.B, (int64_t)min_avail, c.ntargets, c.k, true, false,
+                         dec_small_kb(c.k));
+        }
+        std::vector<sec::Tile> tiles;
+        flatten(bins, sp.groups, tiles, true);
+        sp.ntail = (uint32_t)tail.size();
+        sp.nmsgs = (uint32_t)msgs.size();
+        sp.sha_split = sha1_split(ctx->opt, msgs);
+        sp.dig_off = align_up(sp.out_bytes, 4);  // host mode: digests follow the slab's targets (dword stores)
+        if (host)
+            sp.out_bytes = sp.dig_off + (uint64_t)msgs.size() * 20;
+        sp.off_desc = img.put(descs.data(), descs.size() * sizeof(sec::RepDesc));
+        sp.off_tiles = img.put(tiles.data(), tiles.size() * sizeof(sec::Tile));
+        sp.off_tail = img.put(tail.data(), tail.size() * sizeof(sec::TailItem));
+        soff.resize(soff.size() + sec::kBatchVecs, 0);  // the kernel loads a batch's offsets unconditionally
+        sp.off_soff = img.put(soff.data(), soff.size() * 8);
+        sp.off_savail = img.put(savail.data(), savail.size() * 4);
+        sp.off_toff = img.put(toff.data(), toff.size() * 8);
+        sp.off_msgs = img.put(msgs.data(), msgs.size() * sizeof(sec::MsgDesc));
+        plan.subs.push_back(std::move(sp));
+    }
+    RC(upload_plan(ctx, plan, img, tc, pending));
+    plan.gen = tc.gen;
+    return SEC_OK;
+}
+
+int launch_repair_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const uint8_t *blocks, uint8_t *out,
+                      uint8_t *digests, hipStream_t s)
+{
+    const sec::RepDesc *dd = plan.meta.as<sec::RepDesc>(sp.off_desc);
+    const sec::Tile *dt = plan.meta.as<sec::Tile>(sp.off_tiles);
+    const uint32_t *tabs = ctx->rep_tabs.buf.as<uint32_t>();
+    const sec::RepSlots sl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
+                           plan.meta.as<uint64_t>(sp.off_toff)};
+    for (const Group &g : sp.groups) {
+        int e = sec_launch_repair(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
+                                  g.mfma);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_repair_kernel");
+    }
+    if (sp.ntail) {
+        int e = sec_launch_repair_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_repair_tail");
+    }
+    // the repaired pieces' SHA-1 (storb's piece ids) while they are device-resident
+    for (const auto &run : sp.sha_runs) {
+        int e = sec_launch_sha1(out, out, plan.meta.as<sec::MsgDesc>(sp.off_msgs) + run[0], (uint32_t)run[1],
+                                digests + 20 * run[2], s, sp.sha_split);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_sha1_kernel");
+    }
+    return SEC_OK;
+}
+
 // ---- pinned caller memory: the zero-copy host path ----------------------------
 // A SEC_F_HOST encode / decode whose caller buffers all lie in page-locked host memory the
 // HIP runtime maps at the same address on the device (hipHostMalloc / sec_host_alloc,
@@ -1839,10 +2060,12 @@ void sec_ctx_destroy(sec_ctx *ctx)
     ctx->pin.release();
     ctx->enc_tabs.buf.release();
     ctx->dec_tabs.buf.release();
+    ctx->rep_tabs.buf.release();
     ctx->enc_plan.meta.release();
     ctx->dec_plan.meta.release();
     ctx->sha_plan.meta.release();
     ctx->bn_plan.meta.release();
+    ctx->rep_plan.meta.release();
     ctx->bn_scratch.release();
     ctx->bn_part.release();
     ctx->syn.release();
@@ -1892,7 +2115,7 @@ int sec_ctx_set_option(sec_ctx *ctx, const char *name, int64_t value)
     RC(set_dev(ctx));
     RC(drain_all(ctx));  // nothing in flight may still use a plan or pool built the old way
     ctx->opt.v[i] = value;
-    for (Plan *p : {&ctx->enc_plan, &ctx->dec_plan, &ctx->sha_plan, &ctx->bn_plan})
+    for (Plan *p : {&ctx->enc_plan, &ctx->dec_plan, &ctx->sha_plan, &ctx->bn_plan, &ctx->rep_plan})
         p->valid = false;
     if (i == O_COPY_THREADS) {
         ctx->tasks.reset();
@@ -1917,7 +2140,7 @@ const char *sec_option_name(int index)
 
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches)
 {
-    if (!ctx || kind < 0 || kind > 3 || !total_ms || !launches)
+    if (!ctx || kind < 0 || kind > 4 || !total_ms || !launches)
         return SEC_EINVAL;
     RC(set_dev(ctx));
     double tot = 0;
@@ -2035,6 +2258,24 @@ int sec_decode_matrix(int k, int m, const int32_t *sharenums, uint8_t *out, int3
     if (out_index)
         for (int i = 0; i < k; ++i)
             out_index[i] = idx[i];
+    return SEC_OK;
+}
+
+int sec_repair_matrix(int k, int m, const int32_t *sharenums, const int32_t *targets, int ntargets, uint8_t *out)
+{
+    RC(check_repair(k, m, sharenums, targets, ntargets));
+    if (ntargets == 0)
+        return SEC_OK;
+    if (!out)
+        return SEC_EINVAL;
+    std::vector<int> idx(sharenums, sharenums + k), perm, tg(targets, targets + ntargets);
+    sec::normalise_slots(k, idx, perm);
+    std::vector<uint8_t> rm;
+    if (!sec::repair_matrix(k, m, idx, tg, rm))
+        return SEC_ESINGULAR;
+    for (int r = 0; r < ntargets; ++r)  // normalised slot c holds the caller's block perm[c]
+        for (int c = 0; c < k; ++c)
+            out[(size_t)r * k + perm[c]] = rm[(size_t)r * k + c];
     return SEC_OK;
 }
 
@@ -3141,6 +3382,134 @@ int decode_core(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks, cons
     return SEC_OK;
 }
 }  // namespace
+
+// ---- repair: lost pieces from any k survivors -------------------------------------------
+int sec_repair_batch(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                     const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
+                     const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out, uint8_t *digests,
+                     unsigned flags)
+{
+    if (!ctx || nchunks < 0 || (nchunks > 0 && (!chunks || !sharenums || !block_offs)) ||
+        (flags & ~(SEC_F_HOST | SEC_F_ASYNC)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
+        return SEC_EINVAL;
+    if (nchunks == 0)
+        return SEC_OK;
+    if (nchunks >= (int64_t)UINT32_MAX)
+        return SEC_EINVAL;
+    const bool host = flags & SEC_F_HOST;
+    const bool digest = digests != nullptr;
+    RC(set_dev(ctx));
+
+    // preconditions of every chunk before any device work (sec_repair_matrix's)
+    uint64_t total_slots = 0, total_tgts = 0, total_out = 0;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const sec_rep_chunk &c = chunks[i];
+        if (c.ntargets < 0 || (c.ntargets > 0 && (!target_nums || !target_offs)))
+            return SEC_EINVAL;
+        if (c.k < 1 || c.m < c.k || c.m > 256)
+            return SEC_EKM;
+        RC(check_repair(c.k, c.m, sharenums + c.slot0, c.ntargets ? target_nums + c.tgt0 : nullptr, c.ntargets));
+        if (c.B >= (1ull << 31))
+            return SEC_ESIZE;
+        total_slots = std::max<uint64_t>(total_slots, c.slot0 + (uint64_t)c.k);
+        if (c.ntargets)
+            total_tgts = std::max<uint64_t>(total_tgts, c.tgt0 + (uint64_t)c.ntargets);
+        total_out += (uint64_t)c.ntargets * c.B;
+    }
+    if (total_tgts == 0 || (total_out == 0 && !digest))
+        return SEC_OK;
+    if (total_slots >= UINT32_MAX || total_tgts >= UINT32_MAX)
+        return SEC_EINVAL;
+    // (blocks and out may be NULL: block_offs / target_offs are then absolute addresses)
+
+    // Plan key: host mode keys on shapes, sharenums and targets only (its slots are staged densely,
+    // zero-filled past their avail, its targets dense in the slab); device mode on every descriptor,
+    // sharenum, target, address and avail.
+    Plan &plan = ctx->rep_plan;
+    std::vector<uint8_t> key;
+    auto put = [&](const void *p, size_t n) {
+        const uint8_t *b = (const uint8_t *)p;
+        key.insert(key.end(), b, b + n);
+    };
+    if (host) {
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const sec_rep_chunk &c = chunks[i];
+            put(&c.B, 8);
+            put(&c.ntargets, 4);
+            put(&c.k, 4);
+            put(&c.m, 4);
+            put(sharenums + c.slot0, (size_t)c.k * 4);
+            if (c.ntargets)
+                put(target_nums + c.tgt0, (size_t)c.ntargets * 4);
+        }
+    } else {
+        put(chunks, sizeof(sec_rep_chunk) * (size_t)nchunks);
+        put(sharenums, total_slots * 4);
+        put(block_offs, total_slots * 8);
+        if (block_avail)
+            put(block_avail, total_slots * 8);
+        put(target_nums, total_tgts * 4);
+        put(target_offs, total_tgts * 8);
+    }
+    const unsigned kflags = (host ? SEC_F_HOST : 0u) | (!host && block_avail ? 0x10000u : 0u) | (digest ? 0x20000u : 0u);
+    put(&kflags, sizeof(kflags));
+    const bool reuse = plan.valid && plan.gen == ctx->rep_tabs.gen && plan.key == key;
+    RepLayout L;
+    if (!reuse || host)
+        L = rep_layout(chunks, nchunks, sharenums);
+    if (!reuse) {
+        plan.valid = false;
+        RC(build_repair_plan(ctx, chunks, nchunks, block_offs, block_avail, target_nums, target_offs, L, host, digest));
+        plan.key.swap(key);
+        plan.valid = true;
+    }
+
+    if (!host) {
+        hipEvent_t t0 = nullptr;
+        RC(timing_begin(ctx, &t0, ctx->stream()));
+        RC(launch_repair_sub(ctx, plan, plan.subs[0], blocks, out, digests, ctx->stream()));
+        RC(timing_end(ctx, t0, 4, ctx->stream()));
+        if (!(flags & SEC_F_ASYNC))
+            CK(hipStreamSynchronize(ctx->stream()));
+        return SEC_OK;
+    }
+    // Host mode is always staged: the sources are gathered into pinned slabs, the targets (and
+    // digests) scattered back; a caller's buffer is never page-locked (no HostLock) nor used in
+    // place.
+    ++ctx->staged_calls;
+    auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        uint64_t o = 0;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const sec_rep_chunk &c = chunks[i];
+            for (int s = 0; s < c.k; ++s) {
+                const int from = L.perm[L.first[i] + s];
+                const uint64_t av = rep_avail(c, block_avail, from);
+                jobs.push_back(sec::CopyJob{stage + o, (const void *)((uintptr_t)blocks + block_offs[c.slot0 + from]), av});
+                if (av < c.B)  // the slot's bytes past its avail are zero
+                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
+                o += c.B;
+            }
+        }
+    };
+    auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        uint64_t o = 0, g = sp.dig_off;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const sec_rep_chunk &c = chunks[i];
+            for (int r = 0; r < c.ntargets; ++r) {
+                jobs.push_back(sec::CopyJob{(void *)((uintptr_t)out + target_offs[c.tgt0 + r]), stage + o, c.B});
+                o += c.B;
+                if (digest) {
+                    jobs.push_back(sec::CopyJob{digests + 20 * (c.tgt0 + (uint64_t)r), stage + g, 20});
+                    g += 20;
+                }
+            }
+        }
+    };
+    auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
+        return launch_repair_sub(ctx, plan, sp, din, dout, dout + sp.dig_off, s);
+    };
+    return run_pipeline(ctx, plan, gather, scatter, launch);
+}
 
 // ---------------------------------------------------------------------------
 int sec_malloc(sec_ctx *ctx, size_t bytes, void **dptr)

@@ -194,4 +194,34 @@ inline bool decode_matrix(int k, int m, const std::vector<int> &idx, std::vector
     return gf_invert(minv, k);
 }
 
+// Repair matrix: block `targets[r]` of the code word as a combination of the k source blocks in
+// normalised slot order (idx after normalise_slots).  Row r = E[t] * Minv with E[t] the unit row t
+// for a data block (so the row is Minv's own row t) and zfec's parity row for t >= k.
+// out: targets.size() x k, row-major; false if the sources' decode matrix is singular.
+inline bool repair_matrix(int k, int m, const std::vector<int> &idx, const std::vector<int> &targets,
+                          std::vector<uint8_t> &out)
+{
+    const Gf &g = gf();
+    std::vector<uint8_t> minv;
+    if (!decode_matrix(k, m, idx, minv))
+        return false;
+    const std::vector<uint8_t> enc = encode_matrix(k, m);
+    out.assign(targets.size() * (size_t)k, 0);
+    for (size_t r = 0; r < targets.size(); ++r) {
+        const int t = targets[r];
+        uint8_t *row = &out[r * (size_t)k];
+        if (t < k) {
+            memcpy(row, &minv[(size_t)t * k], k);
+            continue;
+        }
+        for (int j = 0; j < k; ++j) {
+            const uint8_t e = enc[(size_t)t * k + j];
+            if (e)
+                for (int c = 0; c < k; ++c)
+                    row[c] ^= g.mul(e, minv[(size_t)j * k + c]);
+        }
+    }
+    return true;
+}
+
 }  // namespace sec

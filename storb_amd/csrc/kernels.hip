@@ -740,6 +740,164 @@ __global__ __launch_bounds__(256) void sec_decode_tail(const u8 *__restrict__ bl
     }
 }
 
+// ---- repair: lost pieces from any k survivors ---------------------------------
+// Target row r of a chunk is XOR_c Rm[r][c] * slot_c, Rm = E[targets] * Minv (gf_host.hpp
+// repair_matrix): a lost data block or a lost parity block alike.  The decomposition is the
+// direct decode's (tile = chunk, t0, r0; up to 8 target rows per group, every group re-reading
+// the k slots), with three differences: nothing is copied (R >= 1), every row is a whole B-byte
+// piece (block k-1's zero padding included, as computed bytes), and every row is stored at an
+// address of its own, out + tgt_off[tgt0 + r0 + r], at any byte alignment (a piece is its own
+// buffer: a Python bytes payload starts at a header offset), hence the unaligned 16 B stores.
+// Positions < valid = min(B, every slot's avail) are the tiles'; [valid, B) goes byte by byte on
+// the chunk's last tile of each row group, a slot's bytes past its avail reading as zero.
+template <int R, int U, bool W, int KBX>
+__device__ __forceinline__ void repair_main(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                            const sec::RepDesc &d, const sec::Tile &tl, u32 t,
+                                            const u32 *__restrict__ tabs, const sec::RepSlots sl)
+{
+    const u32 k = d.k, valid = d.valid;
+    const u32 step = blockDim.x * sec::kLaneBytes;
+    u32 pos[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        pos[u] = min(t + u * step, valid - sec::kLaneBytes);
+    const u32 *tj = tabs + d.tab + tl.r0 * sec::kTabDwords;
+    const u32 tstep = d.nt * sec::kTabDwords;
+
+    u32x4 acc[R][U];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            acc[r][u] = u32x4{0u, 0u, 0u, 0u};
+
+    // slots in batches of KB, every load of a batch before its arithmetic (decode_main)
+    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
+    auto batch = [&](u32 c0) {
+        constexpr bool LT = lds_tab<R, true>();
+        const u32x2 *vt = wave_tabs<KB, R, LT>(tj, tstep, c0, k);
+        u64 so[KB];  // (the plan pads sl.off by kBatchVecs entries)
+        const u64 *sop = sl.off + d.slot0 + c0;
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+            so[c] = sop[c];
+        u32x4 xs[KB][U];
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+            if (c0 + c < k) {
+                const u8 *s = blocks + so[c];
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    xs[c][u] = load16(s + pos[u]);
+            }
+        if constexpr (kPairRows<R, W>()) {
+#pragma unroll
+            for (int c = 0; c < KB; c += 2) {
+                if (c + 1 < KB && c0 + c + 1 < k)
+                    gf_mac2<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R, xs[c + 1],
+                                      tj + (c0 + c + 1) * tstep, vt + (c + 1) * R);
+                else if (c0 + c < k)
+                    gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < KB; ++c)
+                if (c0 + c < k)
+                    gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
+        }
+    };
+    if constexpr (W) {  // wide k: several batches (see encode_main)
+#pragma unroll 1
+        for (u32 c0 = 0; c0 < k; c0 += KB)
+            batch(c0);
+    } else {
+        batch(0);  // the plan guarantees k <= KB here
+    }
+    const u64 *to = sl.tgt_off + d.tgt0 + tl.r0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        u8 *o = out + to[r];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            store16<SEC_DEC_ST>(o + pos[u], acc[r][u]);
+    }
+}
+
+// The chunk's ragged end [valid, valid + ntail) = [valid, B), byte by byte, for this tile's R
+// target rows: every slot's byte loaded once, kBatch slots at a time, zero past the slot's avail.
+template <int R>
+__device__ __forceinline__ void repair_ragged(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                              const sec::RepDesc &d, const sec::Tile &tl,
+                                              const u32 *__restrict__ tabs, const sec::RepSlots sl)
+{
+    const u64 *to = sl.tgt_off + d.tgt0 + tl.r0;
+    for (u32 i = ragged_lane0(d.valid, tl.t0); i < tl.ntail; i += blockDim.x) {
+        const u32 tp = d.valid + i;
+        u32 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            acc[r] = 0;
+        for (u32 c0 = 0; c0 < d.k; c0 += kBatch) {
+            u32 x[kBatch];
+#pragma unroll
+            for (u32 q = 0; q < kBatch; ++q)
+                x[q] = (c0 + q < d.k && tp < sl.avail[d.slot0 + c0 + q]) ? (u32)blocks[sl.off[d.slot0 + c0 + q] + tp] : 0u;
+#pragma unroll
+            for (u32 q = 0; q < kBatch; ++q)
+                if (c0 + q < d.k) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+                        acc[r] ^= gf_mul_byte(tabs + d.tab + ((c0 + q) * d.nt + tl.r0 + r) * sec::kTabDwords, x[q]);
+                }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            out[to[r] + tp] = (u8)acc[r];
+    }
+}
+
+// KBX > 0: slots per load batch fixed at KBX, as sec_decode_kernel's (api.cpp dec_small_kb)
+template <int R, int U, bool W, int KBX = 0>
+__global__ __launch_bounds__(sec::max_lanes(R, U)) void sec_repair_kernel(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                         const sec::RepDesc *__restrict__ descs,
+                                                         const sec::Tile *__restrict__ tiles,
+                                                         const u32 *__restrict__ tabs,
+                                                         const sec::RepSlots sl)
+{
+    static_assert(R >= 1, "a repair tile has target rows: nothing is copied");
+    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::RepDesc d = descs[tl.chunk];
+    const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
+    if (t < d.valid)
+        repair_main<R, U, W, KBX>(blocks, out, d, tl, t, tabs, sl);
+    if (tl.ntail)
+        repair_ragged<R>(blocks, out, d, tl, tabs, sl);
+}
+
+// One thread per (chunk, position) of the chunks too small for a tile (valid < 16): every
+// target row's byte there.
+__global__ __launch_bounds__(256) void sec_repair_tail(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                       const sec::RepDesc *__restrict__ descs,
+                                                       const sec::TailItem *__restrict__ items, u32 nitems,
+                                                       const u32 *__restrict__ tabs,
+                                                       const sec::RepSlots sl)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nitems)
+        return;
+    const sec::TailItem it = items[i];
+    const sec::RepDesc d = descs[it.chunk];
+    auto slot_byte = [&](u32 c) -> u32 {  // bytes past the slot's avail read as zero
+        return it.t < sl.avail[d.slot0 + c] ? (u32)blocks[sl.off[d.slot0 + c] + it.t] : 0u;
+    };
+    for (u32 r = 0; r < d.nt; ++r) {
+        u32 acc = 0;
+        for (u32 c = 0; c < d.k; ++c)
+            acc ^= gf_mul_byte(tabs + d.tab + (c * d.nt + r) * sec::kTabDwords, slot_byte(c));
+        out[sl.tgt_off[d.tgt0 + r] + it.t] = (u8)acc;
+    }
+}
+
 // ---- SHA-1 of pieces (storb piece ids, /root/reference/storb/util/piece.py:54-68) ----
 // One lane per message: SHA-1 is a sequential chain of 64-byte compressions, so a
 // message cannot be split; the kernel is latency-bound on each lane's round chain
@@ -1162,6 +1320,32 @@ hipError_t dispatch_dec(int rows, const u8 *b, u8 *o, const sec::DecDesc *d, con
     }
 }
 
+template <int R, int U, bool W, int KBX>
+hipError_t launch_rep(const u8 *blocks, u8 *out, const sec::RepDesc *descs, const sec::Tile *tiles, u32 ntiles,
+                      const u32 *tabs, sec::RepSlots sl, u32 lanes, hipStream_t s)
+{
+    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
+    return launch_shm(sec_repair_kernel<R, U, W, KBX>, dim3(ntiles), dim3(lanes),
+                      lds_tab_bytes<KB, R, true>(lanes), s, blocks, out, descs, tiles, tabs, sl);
+}
+
+template <int U, bool W, int KBX = 0>
+hipError_t dispatch_rep(int rows, const u8 *b, u8 *o, const sec::RepDesc *d, const sec::Tile *t, u32 nt,
+                        const u32 *tabs, sec::RepSlots sl, u32 lanes, hipStream_t s)
+{
+    switch (rows) {
+    case 1: return launch_rep<1, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 2: return launch_rep<2, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 3: return launch_rep<3, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 4: return launch_rep<4, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 5: return launch_rep<5, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 6: return launch_rep<6, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 7: return launch_rep<7, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 8: return launch_rep<8, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace
 
 void sec_next_launch_events(void **start, void **stop)
@@ -1259,5 +1443,35 @@ int sec_launch_decode_tail(const uint8_t *blocks, uint8_t *out, const sec::DecDe
     if (nitems == 0)
         return hipSuccess;
     return launch(sec_decode_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out, descs,
+                  items, nitems, tabs, sl);
+}
+
+int sec_launch_repair(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
+                      const sec::RepDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
+                      sec::RepSlots sl, void *stream, int kb)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    if (rows < 1 || U != 1 || lanes < 64 || lanes % 64 || lanes > sec::max_lanes(rows, U))
+        return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const u32 L = (u32)lanes;
+    if (kb) {  // small load batches: tiles of chunks with k <= kb only
+        if (wide || kb != 4)
+            return hipErrorInvalidValue;
+        return dispatch_rep<1, false, 4>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
+    }
+    if (wide)
+        return dispatch_rep<1, true>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
+    return dispatch_rep<1, false>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
+}
+
+int sec_launch_repair_tail(const uint8_t *blocks, uint8_t *out, const sec::RepDesc *descs,
+                           const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::RepSlots sl,
+                           void *stream)
+{
+    if (nitems == 0)
+        return hipSuccess;
+    return launch(sec_repair_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out, descs,
                   items, nitems, tabs, sl);
 }

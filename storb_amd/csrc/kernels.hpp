@@ -66,6 +66,27 @@ struct DecSlots {
     const uint32_t *avail;  // bytes of the block that exist in memory; the rest read as zero
 };
 
+// One repair chunk, device copy (32 B): nt lost blocks (data or parity) recomputed from k source
+// blocks, each a full B-byte piece at an address of its own.
+struct RepDesc {
+    uint32_t B;
+    uint32_t k;
+    uint32_t nt;     // target rows
+    uint32_t tab;    // dword offset of tables, layout [slot][target][5]
+    uint32_t slot0;  // first entry in RepSlots::off / avail
+    uint32_t tgt0;   // first entry in RepSlots::tgt_off
+    uint32_t valid;  // positions [0, valid) where every slot is readable: min(B, every slot's avail)
+    uint32_t pad;
+};
+
+// Per-slot and per-target metadata of a repair launch (device arrays).  Slot c of a chunk is entry
+// slot0 + c (normalised order), its target row r entry tgt0 + r (the caller's order).
+struct RepSlots {
+    const uint64_t *off;      // block address: blocks + off[slot]
+    const uint32_t *avail;    // bytes of the block that exist in memory; the rest read as zero
+    const uint64_t *tgt_off;  // target address: out + tgt_off[target], any byte alignment
+};
+
 // One chunk of a syndrome decode (kernels_bs.hip sec_syndrome_bs_kernel, sec_decode_bs_kernel; 56 B).  Block j of
 // the chunk (data j < k, parity row r at j = k + r) is at blocks + off[slot0 + j] with
 // avail[slot0 + j] readable bytes, when its bit in dmask / pmask is set.
@@ -197,5 +218,13 @@ int sec_launch_sha1(const uint8_t *base0, const uint8_t *base1, const sec::MsgDe
                     uint8_t *digests, void *stream, int split = 0);
 int sec_launch_decode_tail(const uint8_t *blocks, uint8_t *out, const sec::DecDesc *descs,
                            const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::DecSlots slots,
+                           void *stream);
+// Repair (sec_repair_kernel): tiles and arguments as the copy-free decode's (rows 1..8 target rows
+// of the tile's group, kb as sec_launch_decode), every target row stored whole at its own address
+int sec_launch_repair(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
+                      const sec::RepDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
+                      sec::RepSlots slots, void *stream, int kb = 0);
+int sec_launch_repair_tail(const uint8_t *blocks, uint8_t *out, const sec::RepDesc *descs,
+                           const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::RepSlots slots,
                            void *stream);
 }

@@ -1,6 +1,7 @@
 """Host-side engine over libstorbec.so: one HIP context per (device, thread).
 
-Two ways in:
+Two ways in (``repair_batch`` / ``repair_host``, lost blocks regenerated from any k survivors,
+come in both):
   * device-resident batches (``encode_batch`` / ``decode_batch``): descriptor arrays +
     device addresses (torch tensors, or any integer address) — the bench and the GPU parity
     tests use these;
@@ -23,8 +24,8 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (COPY_DTYPE, DEC_DTYPE, ENC_DTYPE, MSG_DTYPE, SEC_F_ASYNC, SEC_F_GPU_PARITY_IDS, SEC_F_HOST,
-                   SEC_F_RECOVER, SEC_F_STAGED)
+from ._lib import (COPY_DTYPE, DEC_DTYPE, ENC_DTYPE, MSG_DTYPE, REP_DTYPE, SEC_F_ASYNC, SEC_F_GPU_PARITY_IDS,
+                   SEC_F_HOST, SEC_F_RECOVER, SEC_F_STAGED)
 
 
 class Error(Exception):
@@ -77,7 +78,7 @@ def device_count() -> int:
     return n.value if rc == 0 else 0
 
 
-_TIMING_KINDS = {"encode": 0, "decode": 1, "sha1": 2, "bignum": 3}
+_TIMING_KINDS = {"encode": 0, "decode": 1, "sha1": 2, "bignum": 3, "repair": 4}
 
 
 class Engine:
@@ -126,7 +127,7 @@ class Engine:
 
     def collect_timing(self, kind: str) -> tuple[float, int]:
         """(summed kernel ms, launch count) recorded since the last collect;
-        kind 'encode' | 'decode' | 'sha1' | 'bignum'."""
+        kind 'encode' | 'decode' | 'sha1' | 'bignum' | 'repair'."""
         ms = ctypes.c_double(0)
         n = ctypes.c_int64(0)
         self._check(self.lib.sec_timing_collect(self._ctx, _TIMING_KINDS[kind], ctypes.byref(ms),
@@ -186,6 +187,82 @@ class Engine:
                  (SEC_F_RECOVER if recover_only else 0) | (SEC_F_STAGED if staged else 0))
         self._check(self.lib.sec_decode_batch_ex(self._ctx, _ptr(descs), len(descs), _ptr(sn), _ptr(bo),
                                                  None if av is None else _ptr(av), b or None, o or None, flags))
+
+    def repair_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
+                     target_nums: np.ndarray, target_offs: np.ndarray, out, *, block_avail: np.ndarray | None = None,
+                     digests=None, host: bool = False, asynchronous: bool = False) -> None:
+        """sec_repair_batch: block target_nums[tgt0 + j] of each chunk (REP_DTYPE descriptors)
+        written whole at out + target_offs[tgt0 + j] from the chunk's k source blocks.
+        block_avail as decode_batch; digests (optional): 20 bytes per target slot, the repaired
+        piece's SHA-1, where the targets live.  host: host buffers, always staged."""
+        descs = np.ascontiguousarray(descs, dtype=REP_DTYPE)
+        sn = np.ascontiguousarray(sharenums, dtype=np.int32)
+        bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
+        tn = np.ascontiguousarray(target_nums, dtype=np.int32)
+        to = np.ascontiguousarray(target_offs, dtype=np.uint64)
+        av = None if block_avail is None else np.ascontiguousarray(block_avail, dtype=np.uint64)
+        if av is not None and av.size < bo.size:
+            raise ValueError("block_avail needs one entry per slot")
+        if tn.size != to.size:
+            raise ValueError("one target address per target")
+        b, _kb = addr(blocks)
+        o, _ko = addr(out)
+        g, _kg = addr(digests)
+        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
+        self._check(self.lib.sec_repair_batch(self._ctx, _ptr(descs), len(descs), _ptr(sn) or None, _ptr(bo) or None,
+                                              None if av is None else _ptr(av), b or None, _ptr(tn) or None,
+                                              _ptr(to) or None, o or None, g or None, flags))
+
+    def repair_host(self, items, digests: bool = False):
+        """Lost blocks of host chunks, regenerated from k survivors each, in one call.
+
+        items: [(k, m, blocks, sharenums, targets)] with exactly k equal-length blocks per chunk
+        and the block numbers to regenerate.  Returns, per chunk, the target blocks as bytes in
+        the order of `targets`; with ``digests=True`` also, per chunk, each one's SHA-1 digest
+        (20 bytes, GPU-computed on the repaired piece)."""
+        from ._hostbytes import _finalize, _new_bytes
+
+        for it in items:
+            check_repair_item(*it)
+        n = len(items)
+        descs = np.zeros(n, dtype=REP_DTYPE)
+        nslots = sum(it[0] for it in items)
+        ntg = sum(len(it[4]) for it in items)
+        sn = np.zeros(max(nslots, 1), dtype=np.int32)
+        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
+        tn = np.zeros(max(ntg, 1), dtype=np.int32)
+        to = np.zeros(max(ntg, 1), dtype=np.uint64)
+        keep, objs = [], []
+        slot = tgt = 0
+        for j, (k, m, blocks, sharenums, targets) in enumerate(items):
+            B = len(blocks[0])
+            for q, b in enumerate(blocks):
+                a, kp = addr(b)
+                keep.append(kp)
+                bo[slot + q] = a
+                sn[slot + q] = int(sharenums[q])
+            row = []
+            for q, t in enumerate(targets):
+                b, v = _new_bytes(B)
+                row.append(b)
+                tn[tgt + q] = int(t)
+                to[tgt + q] = v.ctypes.data if B else 0
+                keep.append(v)
+            objs.append(row)
+            descs[j] = (B, slot, tgt, len(targets), k, m, 0)
+            slot += k
+            tgt += len(targets)
+        dig = np.zeros(max(20 * ntg, 1), dtype=np.uint8) if digests else None
+        if ntg:
+            self.repair_batch(descs, sn, bo, 0, tn, to, 0, digests=dig, host=True)
+        out = [[_finalize(b) for b in row] for row in objs]
+        if not digests:
+            return out
+        dv, digs, f = memoryview(dig), [], 0
+        for row in out:
+            digs.append([bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(len(row))])
+            f += len(row)
+        return out, digs
 
     def encode_digest_batch(self, descs: np.ndarray, src, parity, digests, *, host: bool = False,
                             asynchronous: bool = False) -> None:
@@ -566,7 +643,40 @@ def check_decode_item(k: int, m: int, blocks, sharenums, padlen: int) -> None:
         raise Error(_lib.strerror(_lib.SEC_EPADLEN))
 
 
+def check_repair_item(k: int, m: int, blocks, sharenums, targets) -> None:
+    """The repair preconditions for one chunk (the library's own checks, raised before any GPU
+    work): exactly k equal-length blocks and k sharenums, 1 <= k <= m <= 256, sources and
+    targets in [0, m), all distinct, no target among the sources.  Raises Error."""
+    if len(blocks) != k or len(sharenums) != k:
+        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
+    B = len(blocks[0]) if blocks else 0
+    for b in blocks:
+        if len(b) != B:
+            raise Error(_lib.strerror(_lib.SEC_EBLOCKLEN))
+    if not (1 <= k <= m <= 256):
+        raise Error(_lib.strerror(_lib.SEC_EKM))
+    sn, tg = [int(x) for x in sharenums], [int(x) for x in targets]
+    if any(x < 0 or x >= m for x in sn + tg):
+        raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
+    if len(set(sn + tg)) != k + len(tg):
+        raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
+
+
 # -- matrices (host arithmetic; no device needed) ------------------------------
+def repair_matrix(k: int, m: int, sharenums, targets) -> bytes:
+    """len(targets) x k bytes, row-major: block targets[r] = XOR_j row[r][j] * block
+    sharenums[j] (sec_repair_matrix; columns in the order of `sharenums`)."""
+    lib = _lib.load()
+    sn = np.ascontiguousarray([int(x) for x in sharenums], dtype=np.int32)
+    tg = np.ascontiguousarray([int(x) for x in targets], dtype=np.int32)
+    if sn.size != k:
+        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
+    out = np.zeros(max(tg.size * k, 1), dtype=np.uint8)
+    check(lib.sec_repair_matrix(int(k), int(m), _ptr(sn) or None, _ptr(tg) or None, tg.size, _ptr(out)), lib)
+    return out[: tg.size * k].tobytes()
+
+
+
 def encode_matrix(k: int, m: int) -> bytes:
     """Rows k..m-1 of zfec's systematic encode matrix, as produced by libstorbec."""
     lib = _lib.load()

@@ -20,6 +20,9 @@ Deliberate differences (documented in DESIGN.md §Boundary):
   logs here.
 * extra batch entry points ``encode_chunks`` / ``decode_chunks`` for callers that can hand
   over many chunks at once (the validator's upload loop, validator.py:1352-1431).
+* ``repair_chunks`` / ``repair_pieces`` (no reference counterpart) regenerate lost pieces, data
+  or parity, from a chunk's surviving pieces, with their piece ids on request: what a validator
+  needs to seed a failed miner's pieces elsewhere without reconstructing and re-encoding.
 * ``reconstruct_data_stream`` decodes window w+1 on a worker thread (its own HIP context)
   while the caller consumes window w's chunks; ``encode_chunks_stream`` does the same for the
   upload loop's produce/consume pattern (validator.py:1338-1446, 1630-1638).
@@ -62,7 +65,7 @@ __all__ = [
     "PieceType", "Piece", "EncodedChunk", "ProcessedPieceInfo", "EncodedPieces", "piece_hash", "piece_length",
     "encode_chunk", "decode_chunk", "reconstruct_data", "reconstruct_data_stream", "encode_chunks",
     "decode_chunks", "chunk_shape", "piece_hashes", "encode_chunks_with_ids", "encode_chunks_stream", "Encoder",
-    "Decoder", "Error", "use_devices",
+    "Decoder", "Error", "use_devices", "repair_chunks", "repair_pieces",
 ]
 
 PREFETCH_PIECE_IDS = True  # encode_chunk hashes its pieces on a thread pool (see module doc)
@@ -698,6 +701,59 @@ def reconstruct_data(pieces: list[Piece], chunks: list[EncodedChunk], *, devices
             raise ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
         chunk.pieces = relevant
     return decode_chunks(chunks, devices=devices)
+
+
+def repair_chunks(chunks: typing.Sequence[EncodedChunk], targets=None, *, piece_ids: bool = False) -> list[list[Piece]]:
+    """Regenerate lost pieces, data or parity, from each chunk's surviving pieces: one GPU call.
+
+    ``chunk.pieces`` holds the survivors, at least k of them (with more, the k that
+    ``choose_blocks`` picks are read).  targets: per chunk the piece indices to regenerate, or
+    None for every ``piece_idx`` in ``range(m)`` that is absent (``targets=None``: that for all
+    chunks).  Returns, per chunk, the regenerated pieces in target order, each keeping the
+    chunk's ``chunk_idx``; with ``piece_ids=True`` they are ``ProcessedPieceInfo`` carrying the
+    piece's id (its SHA-1, hashed on the GPU while the piece is there), to be checked against
+    the id recorded at upload.  No reference counterpart: piece.py would reconstruct the chunk
+    and encode it again."""
+    if targets is not None and len(targets) != len(chunks):
+        raise ValueError("repair_chunks: one target list (or None) per chunk")
+    items = []
+    for i, ch in enumerate(chunks):
+        if not (1 <= ch.k <= ch.m <= 256):
+            raise Error(f"Precondition violation: 1 <= k <= m <= 256 required (k={ch.k}, m={ch.m})")
+        have: dict[int, Piece] = {}
+        for p in ch.pieces or []:
+            have.setdefault(p.piece_idx, p)
+        use = sorted(have.values(), key=lambda p: p.piece_idx)
+        if len(use) < ch.k:
+            raise ValueError(f"Not enough pieces to repair chunk {ch.chunk_idx}")
+        if len(use) > ch.k:
+            pick = choose_blocks(ch.k, ch.m, [p.piece_idx for p in use])
+            use = [use[j] for j in pick] if pick is not None else use[:ch.k]
+        tg = targets[i] if targets is not None and targets[i] is not None else None
+        if tg is None:
+            tg = [t for t in range(ch.m) if t not in have]
+        items.append((ch.k, ch.m, [p.data for p in use], [p.piece_idx for p in use], [int(t) for t in tg]))
+    if not items:
+        return []
+    res = get_engine().repair_host(items, digests=piece_ids)
+    blocks, digs = res if piece_ids else (res, None)
+    out = []
+    for i, (ch, it) in enumerate(zip(chunks, items)):
+        row = []
+        for j, t in enumerate(it[4]):
+            kind = PieceType.Data if t < ch.k else PieceType.Parity
+            if piece_ids:
+                row.append(ProcessedPieceInfo(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind,
+                                              data=blocks[i][j], piece_id=digs[i][j].hex()))
+            else:
+                row.append(Piece(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind, data=blocks[i][j]))
+        out.append(row)
+    return out
+
+
+def repair_pieces(chunk: EncodedChunk, targets=None, *, piece_ids: bool = False) -> list[Piece]:
+    """``repair_chunks`` for one chunk: its lost pieces (`targets`, default every absent one)."""
+    return repair_chunks([chunk], None if targets is None else [targets], piece_ids=piece_ids)[0]
 
 
 def _windows(chunks, nbytes, size_of) -> Iterator[list]:
