@@ -23,6 +23,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <thread>
 #include <utility>
@@ -606,23 +607,50 @@ void flatten(const Bins &bins, std::vector<Group> &groups, std::vector<sec::Tile
     }
 }
 
-// Contiguous chunk ranges of at most `slab` input bytes (at least one chunk each).
-std::vector<std::pair<int64_t, int64_t>> slabs_of(const std::vector<uint64_t> &in_bytes, size_t slab)
+// A plan's launch units as chunk ranges: all chunks (device mode), or (host mode) contiguous
+// ranges of at most `slab` staged input bytes, at least one chunk each (in_bytes(i): chunk i's).
+template <class InBytes>
+std::vector<std::pair<int64_t, int64_t>> slab_ranges(bool host, int64_t nchunks, InBytes in_bytes, size_t slab)
 {
     std::vector<std::pair<int64_t, int64_t>> r;
+    if (!host) {
+        r.emplace_back(0, nchunks);
+        return r;
+    }
     int64_t c0 = 0;
     uint64_t acc = 0;
-    for (int64_t i = 0; i < (int64_t)in_bytes.size(); ++i) {
-        if (i > c0 && acc + in_bytes[i] > slab) {
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const uint64_t b = in_bytes(i);
+        if (i > c0 && acc + b > slab) {
             r.emplace_back(c0, i);
             c0 = i;
             acc = 0;
         }
-        acc += in_bytes[i];
+        acc += b;
     }
-    if (c0 < (int64_t)in_bytes.size())
-        r.emplace_back(c0, (int64_t)in_bytes.size());
+    if (c0 < nchunks)
+        r.emplace_back(c0, nchunks);
     return r;
+}
+
+// A plan's key: the bytes of everything the plan depends on, compared whole against the next
+// call's (which fields, per mode, is each caller's choice).
+struct PlanKey {
+    std::vector<uint8_t> bytes;
+    PlanKey() { bytes.reserve(256); }  // a small call's key in one allocation
+    void put(const void *p, size_t n)
+    {
+        const uint8_t *b = (const uint8_t *)p;
+        bytes.insert(bytes.end(), b, b + n);
+    }
+    template <class T>
+    void put(const T &v) { put(&v, sizeof(T)); }
+};
+
+// Whether the last plan serves this call too: same key, and the table cache not reset since
+bool plan_reusable(const Plan &plan, const TableCache &tc, const PlanKey &key)
+{
+    return plan.valid && plan.gen == tc.gen && plan.key == key.bytes;
 }
 
 // ---- host pipeline slots ----------------------------------------------------
@@ -773,24 +801,6 @@ int pin_wait(sec_ctx *ctx)
     return SEC_OK;
 }
 
-int table_ensure(TableCache &tc, const std::string &key, std::vector<uint8_t> &&coef,
-                 std::vector<PendingExpand> &pending, uint32_t *off)
-{
-    auto it = tc.index.find(key);
-    if (it != tc.index.end()) {
-        *off = it->second;
-        return SEC_OK;
-    }
-    const size_t need = coef.size() * sec::kTabDwords;
-    if ((tc.used + need) * 4 > tc.buf.cap)
-        return 1;  // caller resets the cache and retries
-    *off = (uint32_t)tc.used;
-    tc.index.emplace(key, *off);
-    pending.push_back(PendingExpand{std::move(coef), *off});
-    tc.used += need;
-    return SEC_OK;
-}
-
 int table_reset(sec_ctx *ctx, TableCache &tc, size_t need_dwords)
 {
     RC(drain_all(ctx));  // nothing may still read the old buffer
@@ -803,9 +813,77 @@ int table_reset(sec_ctx *ctx, TableCache &tc, size_t need_dwords)
     return SEC_OK;
 }
 
+// A failed plan build forgets the tables it queued but never expanded: they are the cache's
+// newest, from the first pending one on
+void drop_pending(TableCache &tc, const std::vector<PendingExpand> &pending)
+{
+    if (pending.empty())
+        return;
+    const uint32_t first = pending.front().dst;
+    for (auto it = tc.index.begin(); it != tc.index.end();)
+        it = it->second >= first ? tc.index.erase(it) : std::next(it);
+    tc.used = first;
+}
+
+// The tables of a batch's chunks (the three plan builders): tab_of[i] = dword offset of chunk i's
+// tables in the cache, `pending` = the tables that are new, for upload_plan to expand.
+//   want(i, key): 0 when chunk i needs no table, else its coefficient count, with the table's
+//                 cache key (matrix identity) in `key`
+//   coef(i, out): the table's coefficient bytes, layout [input slot][output row], or an error
+//                 (SEC_ESINGULAR)
+// When a table does not fit, the cache is reset once, to a buffer sized by every distinct table
+// of the batch (slack(their dwords): each caller's margin), so the second pass always fits and
+// SEC_ENOMEM means a failed allocation only.
+template <class Want, class Coef>
+int resolve_tables(sec_ctx *ctx, TableCache &tc, int64_t nchunks, size_t (*slack)(size_t), Want want, Coef coef,
+                   std::vector<uint32_t> &tab_of, std::vector<PendingExpand> &pending)
+{
+    tab_of.assign((size_t)nchunks, 0);
+    std::string key;
+    for (int attempt = 0;; ++attempt) {
+        pending.clear();
+        int64_t i = 0;
+        for (; i < nchunks; ++i) {
+            key.clear();
+            const size_t ncoef = want(i, key);
+            if (!ncoef)
+                continue;
+            auto it = tc.index.find(key);
+            if (it == tc.index.end()) {
+                if ((tc.used + ncoef * sec::kTabDwords) * 4 > tc.buf.cap)
+                    break;
+                std::vector<uint8_t> cf;
+                if (int e = coef(i, cf)) {
+                    drop_pending(tc, pending);
+                    return e;
+                }
+                it = tc.index.emplace(key, (uint32_t)tc.used).first;
+                pending.push_back(PendingExpand{std::move(cf), it->second});
+                tc.used += ncoef * sec::kTabDwords;
+            }
+            tab_of[i] = it->second;
+        }
+        if (i == nchunks)
+            return SEC_OK;
+        if (attempt == 1)
+            return SEC_ENOMEM;  // (not reached: the buffer was sized for every table)
+        size_t need = 0;
+        std::set<std::string> seen;
+        for (i = 0; i < nchunks; ++i) {
+            key.clear();
+            const size_t ncoef = want(i, key);
+            if (ncoef && seen.insert(key).second)
+                need += ncoef * sec::kTabDwords;
+        }
+        RC(table_reset(ctx, tc, slack(need)));
+    }
+}
+size_t slack_none(size_t dwords) { return dwords; }
+size_t slack_double(size_t dwords) { return dwords * 2 + ((size_t)1 << 18); }
+
 // Uploads the image with one H2D from pinned memory and expands new tables from
 // the coefficient bytes placed at the end of the image.
-int upload_plan(sec_ctx *ctx, Plan &plan, Image &img, TableCache &tc, const std::vector<PendingExpand> &pending)
+int upload_plan_(sec_ctx *ctx, Plan &plan, Image &img, TableCache &tc, const std::vector<PendingExpand> &pending)
 {
     std::vector<size_t> coef_off;
     for (const auto &pe : pending)
@@ -824,6 +902,14 @@ int upload_plan(sec_ctx *ctx, Plan &plan, Image &img, TableCache &tc, const std:
             return hip_fail((hipError_t)e, "sec_expand_tables");
     }
     return SEC_OK;
+}
+
+int upload_plan(sec_ctx *ctx, Plan &plan, Image &img, TableCache &tc, const std::vector<PendingExpand> &pending)
+{
+    const int e = upload_plan_(ctx, plan, img, tc, pending);
+    if (e)
+        drop_pending(tc, pending);
+    return e;
 }
 
 // Kernel timing (sec_ctx_set_timing).  Around the EC launchers (`attached`), the events ride
@@ -930,54 +1016,28 @@ int build_encode_plan(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks
     Plan &plan = ctx->enc_plan;
     TableCache &tc = ctx->enc_tabs;
     std::vector<PendingExpand> pending;
-    std::vector<uint32_t> tab_of((size_t)nchunks, 0);
-    for (int attempt = 0;; ++attempt) {
-        pending.clear();
-        size_t need = 0;
-        bool overflow = false;
-        std::map<std::pair<int, int>, uint32_t> local;
-        for (int64_t i = 0; i < nchunks && !overflow; ++i) {
-            const int k = chunks[i].k, m = chunks[i].m;
-            if (m == k)
-                continue;
-            auto lk = local.find({k, m});
-            if (lk != local.end()) {
-                tab_of[i] = lk->second;
-                continue;
-            }
-            const std::vector<uint8_t> enc = sec::encode_matrix(k, m);
-            const int p = m - k;
-            std::vector<uint8_t> coef((size_t)k * p);
-            for (int j = 0; j < k; ++j)
-                for (int r = 0; r < p; ++r)
-                    coef[(size_t)j * p + r] = enc[(size_t)(k + r) * k + j];
-            need += coef.size() * sec::kTabDwords;
-            uint32_t off = 0;
-            if (table_ensure(tc, std::to_string(k) + "/" + std::to_string(m), std::move(coef), pending, &off)) {
-                overflow = true;
-                break;
-            }
-            local[{k, m}] = off;
-            tab_of[i] = off;
-        }
-        if (!overflow)
-            break;
-        if (attempt == 1)
-            return SEC_ENOMEM;
-        RC(table_reset(ctx, tc, need));
-    }
+    std::vector<uint32_t> tab_of;
+    auto want = [&](int64_t i, std::string &key) {  // the parity rows of the (k, m) code
+        const int k = chunks[i].k, m = chunks[i].m;
+        if (m > k)
+            key = std::to_string(k) + "/" + std::to_string(m);
+        return (size_t)k * (m - k);
+    };
+    auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
+        const int k = chunks[i].k, p = chunks[i].m - k;
+        const std::vector<uint8_t> enc = sec::encode_matrix(k, chunks[i].m);
+        cf.resize((size_t)k * p);
+        for (int j = 0; j < k; ++j)
+            for (int r = 0; r < p; ++r)
+                cf[(size_t)j * p + r] = enc[(size_t)(k + r) * k + j];
+        return (int)SEC_OK;
+    };
+    RC(resolve_tables(ctx, tc, nchunks, slack_none, want, coef, tab_of, pending));
 
-    std::vector<std::pair<int64_t, int64_t>> ranges;
-    if (host) {
-        std::vector<uint64_t> ib((size_t)nchunks);
-        for (int64_t i = 0; i < nchunks; ++i)
-            ib[i] = chunks[i].n;
-        // SHA-1 is one sequential chain per piece: a slab's hashing takes as long as
-        // one piece, whatever the slab size, so digest mode uses few large slabs
-        ranges = slabs_of(ib, (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
-    } else {
-        ranges.emplace_back(0, nchunks);
-    }
+    // SHA-1 is one sequential chain per piece: a slab's hashing takes as long as
+    // one piece, whatever the slab size, so digest mode uses few large slabs
+    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return chunks[i].n; },
+                                    (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
     Image img;
     plan.subs.clear();
     bool narrow = true;  // every block of the batch >= 64 KiB: one-wave encode tiles (full_lanes)
@@ -1076,18 +1136,20 @@ int launch_encode_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
 // ---- decode plan ------------------------------------------------------------
 // Normalised slot order of every chunk (zfec's _fecmodule.c: primaries moved to
 // their own slot); perm[i] = caller position of the block in normalised slot i.
-struct DecLayout {
+// (decode and repair chunks alike: both carry k, slot0 and B)
+struct SlotLayout {
     std::vector<int> perm, idx;
     std::vector<uint64_t> first;  // per chunk: start in perm/idx
 };
 
-DecLayout dec_layout(const sec_dec_chunk *chunks, int64_t nchunks, const int32_t *sharenums)
+template <class Chunk>
+SlotLayout slot_layout(const Chunk *chunks, int64_t nchunks, const int32_t *sharenums)
 {
-    DecLayout L;
+    SlotLayout L;
     L.first.resize((size_t)nchunks);
     std::vector<int> idx, perm;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const sec_dec_chunk &c = chunks[i];
+        const Chunk &c = chunks[i];
         idx.assign(sharenums + c.slot0, sharenums + c.slot0 + c.k);
         sec::normalise_slots(c.k, idx, perm);
         L.first[i] = L.perm.size();
@@ -1097,10 +1159,60 @@ DecLayout dec_layout(const sec_dec_chunk *chunks, int64_t nchunks, const int32_t
     return L;
 }
 
-// Readable bytes of caller slot `j` of chunk c (sec_decode_batch_ex's block_avail; B if none).
-uint64_t slot_avail(const sec_dec_chunk &c, const uint64_t *block_avail, int j)
+// Readable bytes of caller slot `j` of chunk c (the calls' block_avail; B if none).
+template <class Chunk>
+uint64_t slot_avail(const Chunk &c, const uint64_t *block_avail, int j)
 {
     return block_avail ? std::min<uint64_t>(block_avail[c.slot0 + j], c.B) : c.B;
+}
+
+// The cache key of a table made from the k blocks idx[0..k) of a (k, m) code
+std::string slots_key(int k, int m, const int *idx)
+{
+    std::string key = std::to_string(k) + "/" + std::to_string(m) + ":";
+    for (int s = 0; s < k; ++s)
+        key += std::to_string(idx[s]) + ",";
+    return key;
+}
+
+// The k slots of chunks [c0, c1) into a host slab, densely and in normalised order, each
+// zero-filled from its avail to B (the staged plans' layout: slot s of a chunk at s * B)
+template <class Chunk>
+void gather_slots(const Chunk *chunks, int64_t c0, int64_t c1, const SlotLayout &L, const uint64_t *block_offs,
+                  const uint64_t *block_avail, const uint8_t *blocks, char *stage, std::vector<sec::CopyJob> &jobs)
+{
+    uint64_t o = 0;
+    for (int64_t i = c0; i < c1; ++i) {
+        const Chunk &c = chunks[i];
+        for (int s = 0; s < c.k; ++s) {
+            const int from = L.perm[L.first[i] + s];
+            const uint64_t av = slot_avail(c, block_avail, from);
+            jobs.push_back(sec::CopyJob{stage + o, (const void *)((uintptr_t)blocks + block_offs[c.slot0 + from]), av});
+            if (av < c.B)  // the slot's bytes past its avail are zero
+                jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
+            o += c.B;
+        }
+    }
+}
+
+// The present primaries of decode chunk c that reach its output (a host join's copies):
+// visit(dst, src, av, row) for primary j in caller slot q, dst = its row in `out`, src = the
+// caller's block, row = the row's bytes (clipped to the chunk's n bytes), av <= row = those the
+// slot holds (the rest of the row is zero).
+template <class Visit>
+void for_present_rows(const sec_dec_chunk &c, const int32_t *sharenums, const uint64_t *block_offs,
+                      const uint64_t *block_avail, const uint8_t *blocks, uint8_t *out, Visit visit)
+{
+    const uint64_t n = (uint64_t)c.k * c.B - c.padlen;
+    for (int q = 0; q < c.k; ++q) {
+        const int j = sharenums[c.slot0 + q];
+        if (j >= c.k || (uint64_t)j * c.B >= n)
+            continue;
+        const uint64_t row = std::min<uint64_t>(c.B, n - (uint64_t)j * c.B);
+        visit((uint8_t *)((uintptr_t)out + c.out_off + (uint64_t)j * c.B),
+              (const uint8_t *)((uintptr_t)blocks + block_offs[c.slot0 + q]),
+              std::min<uint64_t>(row, slot_avail(c, block_avail, q)), row);
+    }
 }
 
 // Output bytes of a decode chunk: the reassembled chunk, or (recover-only) its e recovered
@@ -1119,74 +1231,55 @@ uint64_t dec_nout(const sec_dec_chunk &c, const int32_t *sharenums, bool recover
 // nocopy (reassembly of host buffers, see sec_decode_batch_ex): recovered rows at their output
 // rows as in a reassembly, but no present primary copied (the host copies those)
 int build_decode_plan(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks, const uint64_t *block_offs,
-                      const uint64_t *block_avail, const DecLayout &L, bool host, bool recover, bool nocopy = false)
+                      const uint64_t *block_avail, const SlotLayout &L, bool host, bool recover, bool nocopy = false)
 {
     Plan &plan = ctx->dec_plan;
     TableCache &tc = ctx->dec_tabs;
     std::vector<PendingExpand> pending;
-    std::vector<uint32_t> tab_of((size_t)nchunks, 0), e_of((size_t)nchunks, 0);
+    std::vector<uint32_t> tab_of, e_of((size_t)nchunks, 0);
     std::vector<int> syn_of((size_t)nchunks, -1);  // syndrome-decode shape, or -1 (syn_choice)
     std::vector<char> fuse_of((size_t)nchunks, 0);  // ... its SynMethod
-    for (int attempt = 0;; ++attempt) {
-        pending.clear();
-        size_t need = 0;
-        bool overflow = false;
-        for (int64_t i = 0; i < nchunks && !overflow; ++i) {
-            const sec_dec_chunk &c = chunks[i];
-            const int k = c.k;
-            const int *idx = &L.idx[L.first[i]];
-            std::vector<int> miss;
-            for (int s = 0; s < k; ++s)
-                if (idx[s] >= k)
-                    miss.push_back(s);
-            e_of[i] = (uint32_t)miss.size();
-            if (miss.empty())
-                continue;
-            // the syndrome kernel reads every slot but data block k-1 whole (that one may be short:
-            // zfec's padded block read in place)
-            bool whole = true;
-            for (int s = 0; s < k && whole && !host; ++s)
-                whole = idx[s] == k - 1 || slot_avail(c, block_avail, L.perm[L.first[i] + s]) >= c.B;
-            int fz = kSynTwo;
-            const int sh = syn_of[i] =
-                whole ? syn_choice(ctx->opt, c, idx, (int)miss.size(), !recover && !nocopy, fz) : -1;
-            fuse_of[i] = fz;
-            if (sh >= 0)
-                continue;  // the syndrome path's matrices are compile-time (its scalings: the plan image)
-            std::string key = std::to_string(k) + "/" + std::to_string(c.m) + ":";
-            for (int s = 0; s < k; ++s)
-                key += std::to_string(idx[s]) + ",";
-            auto it = tc.index.find(key);
-            if (it != tc.index.end()) {
-                tab_of[i] = it->second;
-                continue;
+    // a chunk's method; the direct path's table: the missing primaries' rows of the inverse
+    auto want = [&](int64_t i, std::string &key) -> size_t {
+        const sec_dec_chunk &c = chunks[i];
+        const int k = c.k;
+        const int *idx = &L.idx[L.first[i]];
+        int e = 0;
+        for (int s = 0; s < k; ++s)
+            e += idx[s] >= k;
+        e_of[i] = (uint32_t)e;
+        if (!e)
+            return 0;
+        // the syndrome kernel reads every slot but data block k-1 whole (that one may be short:
+        // zfec's padded block read in place)
+        bool whole = true;
+        for (int s = 0; s < k && whole && !host; ++s)
+            whole = idx[s] == k - 1 || slot_avail(c, block_avail, L.perm[L.first[i] + s]) >= c.B;
+        int fz = kSynTwo;
+        syn_of[i] = whole ? syn_choice(ctx->opt, c, idx, e, !recover && !nocopy, fz) : -1;
+        fuse_of[i] = fz;
+        if (syn_of[i] >= 0)
+            return 0;  // the syndrome path's matrices are compile-time (its scalings: the plan image)
+        key = slots_key(k, c.m, idx);
+        return (size_t)k * e;
+    };
+    auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
+        const int k = chunks[i].k, e = (int)e_of[i];
+        const int *idx = &L.idx[L.first[i]];
+        std::vector<int> iv(idx, idx + k);
+        std::vector<uint8_t> minv;
+        if (!sec::decode_matrix(k, chunks[i].m, iv, minv))
+            return (int)SEC_ESINGULAR;
+        cf.resize((size_t)k * e);
+        for (int s = 0, r = 0; s < k; ++s)  // row r: the r-th missing primary, slot s
+            if (idx[s] >= k) {
+                for (int j = 0; j < k; ++j)
+                    cf[(size_t)j * e + r] = minv[(size_t)s * k + j];
+                ++r;
             }
-            const int e = (int)miss.size();
-            std::vector<uint8_t> coef;
-            {
-                std::vector<int> iv(idx, idx + k);
-                std::vector<uint8_t> minv;
-                if (!sec::decode_matrix(k, c.m, iv, minv))
-                    return SEC_ESINGULAR;
-                coef.resize((size_t)k * e);
-                for (int s = 0; s < k; ++s)
-                    for (int r = 0; r < e; ++r)
-                        coef[(size_t)s * e + r] = minv[(size_t)miss[r] * k + s];
-            }
-            need += coef.size() * sec::kTabDwords;
-            uint32_t off = 0;
-            if (table_ensure(tc, key, std::move(coef), pending, &off)) {
-                overflow = true;
-                break;
-            }
-            tab_of[i] = off;
-        }
-        if (!overflow)
-            break;
-        if (attempt == 1)
-            return SEC_ENOMEM;
-        RC(table_reset(ctx, tc, need * 2 + ((size_t)1 << 18)));
-    }
+        return (int)SEC_OK;
+    };
+    RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
 
     plan.nsyn = plan.ndirect = plan.nfused = 0;
     for (int64_t i = 0; i < nchunks; ++i)
@@ -1194,15 +1287,8 @@ int build_decode_plan(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks
             ++(syn_of[i] >= 0 ? plan.nsyn : plan.ndirect);
             plan.nfused += syn_of[i] >= 0 && fuse_of[i] == kSynFused;
         }
-    std::vector<std::pair<int64_t, int64_t>> ranges;
-    if (host) {
-        std::vector<uint64_t> ib((size_t)nchunks);
-        for (int64_t i = 0; i < nchunks; ++i)
-            ib[i] = (uint64_t)chunks[i].k * chunks[i].B;
-        ranges = slabs_of(ib, (size_t)ctx->opt[O_SLAB_BYTES]);
-    } else {
-        ranges.emplace_back(0, nchunks);
-    }
+    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return (uint64_t)chunks[i].k * chunks[i].B; },
+                                    (size_t)ctx->opt[O_SLAB_BYTES]);
     Image img;
     plan.subs.clear();
     for (auto [c0, c1] : ranges) {
@@ -1494,93 +1580,42 @@ int launch_decode_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
 // repair matrix's tables (layout [slot][target][5], cached by sources and targets), the k slots
 // in normalised order, one address per target, tiles as a copy-free decode's (add_work), and one
 // SHA-1 message per target when digests are asked for.
-struct RepLayout {
-    std::vector<int> perm, idx;
-    std::vector<uint64_t> first;  // per chunk: start in perm / idx
-};
-
-RepLayout rep_layout(const sec_rep_chunk *chunks, int64_t nchunks, const int32_t *sharenums)
-{
-    RepLayout L;
-    L.first.resize((size_t)nchunks);
-    std::vector<int> idx, perm;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const sec_rep_chunk &c = chunks[i];
-        idx.assign(sharenums + c.slot0, sharenums + c.slot0 + c.k);
-        sec::normalise_slots(c.k, idx, perm);
-        L.first[i] = L.perm.size();
-        L.perm.insert(L.perm.end(), perm.begin(), perm.end());
-        L.idx.insert(L.idx.end(), idx.begin(), idx.end());
-    }
-    return L;
-}
-
-uint64_t rep_avail(const sec_rep_chunk &c, const uint64_t *block_avail, int j)
-{
-    return block_avail ? std::min<uint64_t>(block_avail[c.slot0 + j], c.B) : c.B;
-}
-
 int build_repair_plan(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks, const uint64_t *block_offs,
                       const uint64_t *block_avail, const int32_t *target_nums, const uint64_t *target_offs,
-                      const RepLayout &L, bool host, bool digest)
+                      const SlotLayout &L, bool host, bool digest)
 {
     Plan &plan = ctx->rep_plan;
     TableCache &tc = ctx->rep_tabs;
     std::vector<PendingExpand> pending;
-    std::vector<uint32_t> tab_of((size_t)nchunks, 0);
-    for (int attempt = 0;; ++attempt) {
-        pending.clear();
-        size_t need = 0;
-        bool overflow = false;
-        for (int64_t i = 0; i < nchunks && !overflow; ++i) {
-            const sec_rep_chunk &c = chunks[i];
-            const int k = c.k, nt = c.ntargets;
-            if (nt == 0)
-                continue;
-            const int *idx = &L.idx[L.first[i]];
-            std::string key = std::to_string(k) + "/" + std::to_string(c.m) + ":";
-            for (int s = 0; s < k; ++s)
-                key += std::to_string(idx[s]) + ",";
-            key += "|";
+    std::vector<uint32_t> tab_of;
+    auto want = [&](int64_t i, std::string &key) -> size_t {
+        const sec_rep_chunk &c = chunks[i];
+        if (c.ntargets == 0)
+            return 0;
+        key = slots_key(c.k, c.m, &L.idx[L.first[i]]) + "|";
+        for (int r = 0; r < c.ntargets; ++r)
+            key += std::to_string(target_nums[c.tgt0 + r]) + ",";
+        return (size_t)c.k * c.ntargets;
+    };
+    auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
+        const sec_rep_chunk &c = chunks[i];
+        const int k = c.k, nt = c.ntargets;
+        const int *idx = &L.idx[L.first[i]];
+        std::vector<uint8_t> rm;
+        if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k),
+                                std::vector<int>(target_nums + c.tgt0, target_nums + c.tgt0 + nt), rm))
+            return (int)SEC_ESINGULAR;
+        cf.resize((size_t)k * nt);
+        for (int s = 0; s < k; ++s)
             for (int r = 0; r < nt; ++r)
-                key += std::to_string(target_nums[c.tgt0 + r]) + ",";
-            auto it = tc.index.find(key);
-            if (it != tc.index.end()) {
-                tab_of[i] = it->second;
-                continue;
-            }
-            std::vector<uint8_t> rm, coef((size_t)k * nt);
-            if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k),
-                                    std::vector<int>(target_nums + c.tgt0, target_nums + c.tgt0 + nt), rm))
-                return SEC_ESINGULAR;
-            for (int s = 0; s < k; ++s)
-                for (int r = 0; r < nt; ++r)
-                    coef[(size_t)s * nt + r] = rm[(size_t)r * k + s];
-            need += coef.size() * sec::kTabDwords;
-            uint32_t off = 0;
-            if (table_ensure(tc, key, std::move(coef), pending, &off)) {
-                overflow = true;
-                break;
-            }
-            tab_of[i] = off;
-        }
-        if (!overflow)
-            break;
-        if (attempt == 1)
-            return SEC_ENOMEM;
-        RC(table_reset(ctx, tc, need * 2 + ((size_t)1 << 18)));
-    }
+                cf[(size_t)s * nt + r] = rm[(size_t)r * k + s];
+        return (int)SEC_OK;
+    };
+    RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
 
-    std::vector<std::pair<int64_t, int64_t>> ranges;
-    if (host) {
-        std::vector<uint64_t> ib((size_t)nchunks);
-        for (int64_t i = 0; i < nchunks; ++i)
-            ib[i] = (uint64_t)chunks[i].k * chunks[i].B;
-        // with digests few large slabs, as the encode's digest mode (one SHA-1 chain per piece)
-        ranges = slabs_of(ib, (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
-    } else {
-        ranges.emplace_back(0, nchunks);
-    }
+    // with digests few large slabs, as the encode's digest mode (one SHA-1 chain per piece)
+    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return (uint64_t)chunks[i].k * chunks[i].B; },
+                                    (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
     Image img;
     plan.subs.clear();
     for (auto [c0, c1] : ranges) {
@@ -1608,7 +1643,7 @@ int build_repair_plan(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks
             for (int s = 0; s < c.k; ++s) {
                 const int from = L.perm[base + s];
                 soff.push_back(host ? sp.in_bytes + (uint64_t)s * c.B : block_offs[c.slot0 + from]);
-                const uint64_t av = host ? c.B : rep_avail(c, block_avail, from);  // staged slots are zero-filled
+                const uint64_t av = host ? c.B : slot_avail(c, block_avail, from);  // staged slots are zero-filled
                 savail.push_back((uint32_t)av);
                 min_avail = std::min(min_avail, av);
             }
@@ -1810,32 +1845,23 @@ int msg_batch(sec_ctx *ctx, Plan &plan, const sec_msg *msgs, int64_t nmsgs, uint
         return SEC_OK;
     const bool host = flags & SEC_F_HOST;
     RC(set_dev(ctx));
-    std::vector<uint8_t> key;
+    PlanKey key;
     if (host) {  // dense staging: only lengths matter
-        key.resize((size_t)nmsgs * 16);
+        key.bytes.reserve((size_t)nmsgs * 16 + 24);
         for (int64_t i = 0; i < nmsgs; ++i) {
-            const uint64_t av = std::min(msgs[i].avail, msgs[i].len);
-            memcpy(key.data() + i * 16, &msgs[i].len, 8);
-            memcpy(key.data() + i * 16 + 8, &av, 8);
+            key.put(msgs[i].len);
+            key.put(std::min(msgs[i].avail, msgs[i].len));
         }
     } else {
-        key.assign((const uint8_t *)msgs, (const uint8_t *)(msgs + nmsgs));
+        key.put(msgs, sizeof(sec_msg) * (size_t)nmsgs);
     }
-    const unsigned kflags = flags & ~SEC_F_ASYNC;  // ASYNC does not change the plan
-    key.insert(key.end(), (const uint8_t *)&kflags, (const uint8_t *)&kflags + sizeof(unsigned));
-    key.insert(key.end(), (const uint8_t *)&slab, (const uint8_t *)&slab + sizeof(size_t));
-    key.insert(key.end(), (const uint8_t *)&seg_bytes, (const uint8_t *)&seg_bytes + sizeof(uint64_t));
-    if (!(plan.valid && plan.key == key)) {
+    key.put(flags & ~SEC_F_ASYNC);  // ASYNC does not change the plan
+    key.put(slab);
+    key.put(seg_bytes);
+    if (!(plan.valid && plan.key == key.bytes)) {
         plan.valid = false;
-        std::vector<std::pair<int64_t, int64_t>> ranges;
-        if (host) {
-            std::vector<uint64_t> ib((size_t)nmsgs);
-            for (int64_t i = 0; i < nmsgs; ++i)
-                ib[i] = std::min(msgs[i].avail, msgs[i].len);
-            ranges = slabs_of(ib, slab);
-        } else {
-            ranges.emplace_back(0, nmsgs);
-        }
+        const auto ranges =
+            slab_ranges(host, nmsgs, [&](int64_t i) { return std::min(msgs[i].avail, msgs[i].len); }, slab);
         Image img;
         plan.subs.clear();
         for (auto [c0, c1] : ranges) {
@@ -1871,7 +1897,7 @@ int msg_batch(sec_ctx *ctx, Plan &plan, const sec_msg *msgs, int64_t nmsgs, uint
         }
         std::vector<PendingExpand> none;
         RC(upload_plan(ctx, plan, img, ctx->enc_tabs, none));
-        plan.key.swap(key);
+        plan.key.swap(key.bytes);
         plan.valid = true;
     }
     if (!host) {
@@ -2533,25 +2559,23 @@ int encode_impl(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks, cons
     // host mode (its device layout is dense, caller addresses are used by the
     // gather / scatter alone), so repeated per-chunk calls reuse one plan.
     Plan &plan = ctx->enc_plan;
-    std::vector<uint8_t> key;
+    PlanKey key;
     if (host) {
-        key.resize((size_t)nchunks * 16);
+        key.bytes.reserve((size_t)nchunks * 16 + 4);
         for (int64_t i = 0; i < nchunks; ++i) {
-            memcpy(key.data() + i * 16, &chunks[i].n, 8);
-            memcpy(key.data() + i * 16 + 8, &chunks[i].k, 4);
-            memcpy(key.data() + i * 16 + 12, &chunks[i].m, 4);
+            key.put(chunks[i].n);
+            key.put(chunks[i].k);
+            key.put(chunks[i].m);
         }
     } else {
-        key.resize(sizeof(sec_enc_chunk) * (size_t)nchunks);
-        memcpy(key.data(), chunks, sizeof(sec_enc_chunk) * (size_t)nchunks);
+        key.put(chunks, sizeof(sec_enc_chunk) * (size_t)nchunks);
     }
     // ASYNC and STAGED do not change the plan
-    const unsigned kflags = (flags & ~(SEC_F_ASYNC | SEC_F_STAGED)) | ((unsigned)digest << 16);
-    key.insert(key.end(), (const uint8_t *)&kflags, (const uint8_t *)&kflags + sizeof(unsigned));
-    if (!(plan.valid && plan.gen == ctx->enc_tabs.gen && plan.key == key)) {
+    key.put((flags & ~(SEC_F_ASYNC | SEC_F_STAGED)) | ((unsigned)digest << 16));
+    if (!plan_reusable(plan, ctx->enc_tabs, key)) {
         plan.valid = false;
         RC(build_encode_plan(ctx, chunks, nchunks, host, digest));
-        plan.key.swap(key);
+        plan.key.swap(key.bytes);
         plan.valid = true;
     }
 
@@ -3087,32 +3111,24 @@ bool primary_lost(const sec_dec_chunk &c, const int32_t *sharenums)
     return false;
 }
 
-// The present primaries of chunk c, from the caller's blocks to their rows in `out` (rows
-// clipped to the chunk's n bytes, zero past a slot's avail), as 1 MiB tasks on the pool.
+// The present primaries of chunk c (for_present_rows) copied as 1 MiB tasks on the pool.
 void submit_row_copies(sec::TaskPool &tp, sec::TaskPool::Group &g, const sec_dec_chunk &c, const int32_t *sharenums,
                        const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks, uint8_t *out)
 {
-    const uint64_t n = (uint64_t)c.k * c.B - c.padlen;
-    for (int q = 0; q < c.k; ++q) {
-        const int j = sharenums[c.slot0 + q];
-        if (j >= c.k || (uint64_t)j * c.B >= n)
-            continue;
-        const uint64_t row = std::min<uint64_t>(c.B, n - (uint64_t)j * c.B);
-        const uint64_t av = std::min<uint64_t>(row, slot_avail(c, block_avail, q));
-        uint8_t *dst = (uint8_t *)((uintptr_t)out + c.out_off + (uint64_t)j * c.B);
-        const uint8_t *src = (const uint8_t *)((uintptr_t)blocks + block_offs[c.slot0 + q]);
-        for (uint64_t o = 0; o < row; o += kJoinPiece) {
-            const uint64_t len = std::min<uint64_t>(kJoinPiece, row - o);
-            const uint64_t cp = o < av ? std::min<uint64_t>(len, av - o) : 0;
-            tp.submit(g, [=] {
-                if (cp)
-                    memcpy(dst + o, src + o, cp);
-                if (cp < len)
-                    memset(dst + o + cp, 0, len - cp);
-                return true;
-            });
-        }
-    }
+    for_present_rows(c, sharenums, block_offs, block_avail, blocks, out,
+                     [&](uint8_t *dst, const uint8_t *src, uint64_t av, uint64_t row) {
+                         for (uint64_t o = 0; o < row; o += kJoinPiece) {
+                             const uint64_t len = std::min<uint64_t>(kJoinPiece, row - o);
+                             const uint64_t cp = o < av ? std::min<uint64_t>(len, av - o) : 0;
+                             tp.submit(g, [=] {
+                                 if (cp)
+                                     memcpy(dst + o, src + o, cp);
+                                 if (cp < len)
+                                     memset(dst + o + cp, 0, len - cp);
+                                 return true;
+                             });
+                         }
+                     });
 }
 
 // A staged reassembly of host buffers (decode_core found them neither pinned nor lockable: e.g.
@@ -3252,21 +3268,13 @@ int decode_core(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks, cons
     // primary j, up to that slot's avail (zero past it), rows clipped to the chunk's n bytes
     std::vector<sec::CopyJob> joins;
     if (join && !rows_only) {
-        for (int64_t i = 0; i < nchunks; ++i) {
-            const sec_dec_chunk &c = chunks[i];
-            const uint64_t n = (uint64_t)c.k * c.B - c.padlen;
-            for (int q = 0; q < c.k; ++q) {
-                const int j = sharenums[c.slot0 + q];
-                if (j >= c.k || (uint64_t)j * c.B >= n)
-                    continue;
-                const uint64_t row = std::min<uint64_t>(c.B, n - (uint64_t)j * c.B);
-                const uint64_t av = std::min<uint64_t>(row, slot_avail(c, block_avail, q));
-                uint8_t *dst = out + c.out_off + (uint64_t)j * c.B;
-                joins.push_back(sec::CopyJob{dst, blocks + block_offs[c.slot0 + q], av});
-                if (av < row)
-                    joins.push_back(sec::CopyJob{dst + av, nullptr, row - av});
-            }
-        }
+        for (int64_t i = 0; i < nchunks; ++i)
+            for_present_rows(chunks[i], sharenums, block_offs, block_avail, blocks, out,
+                             [&](uint8_t *dst, const uint8_t *src, uint64_t av, uint64_t row) {
+                                 joins.push_back(sec::CopyJob{dst, src, av});
+                                 if (av < row)
+                                     joins.push_back(sec::CopyJob{dst + av, nullptr, row - av});
+                             });
     }
     // staged joining calls run the kernels in recover mode (dense rows); direct ones write the
     // recovered rows in place with the copies switched off (nocopy)
@@ -3277,41 +3285,36 @@ int decode_core(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks, cons
     // are staged densely, zero-filled past their avail); device mode on every descriptor,
     // sharenum, block offset and avail.
     Plan &plan = ctx->dec_plan;
-    std::vector<uint8_t> key;
+    PlanKey key;
     if (host) {
         for (int64_t i = 0; i < nchunks; ++i) {
             const sec_dec_chunk &c = chunks[i];
-            const size_t o = key.size();
-            key.resize(o + 24 + (size_t)c.k * 4);
-            memcpy(key.data() + o, &c.B, 8);
-            memcpy(key.data() + o + 8, &c.padlen, 8);
-            memcpy(key.data() + o + 16, &c.k, 4);
-            memcpy(key.data() + o + 20, &c.m, 4);
-            memcpy(key.data() + o + 24, sharenums + c.slot0, (size_t)c.k * 4);
+            key.put(c.B);
+            key.put(c.padlen);
+            key.put(c.k);
+            key.put(c.m);
+            key.put(sharenums + c.slot0, (size_t)c.k * 4);
         }
     } else {
-        const size_t kc = sizeof(sec_dec_chunk) * (size_t)nchunks;
-        const size_t ka = block_avail ? total_slots * 8 : 0;
-        key.resize(kc + total_slots * (4 + 8) + ka);
-        memcpy(key.data(), chunks, kc);
-        memcpy(key.data() + kc, sharenums, total_slots * 4);
-        memcpy(key.data() + kc + total_slots * 4, block_offs, total_slots * 8);
-        if (ka)
-            memcpy(key.data() + kc + total_slots * 12, block_avail, ka);
+        key.bytes.reserve(sizeof(sec_dec_chunk) * (size_t)nchunks + total_slots * 20 + 4);
+        key.put(chunks, sizeof(sec_dec_chunk) * (size_t)nchunks);
+        key.put(sharenums, total_slots * 4);
+        key.put(block_offs, total_slots * 8);
+        if (block_avail)
+            key.put(block_avail, total_slots * 8);
     }
     // ASYNC does not change the plan; whether an avail array came does (0x10000), and how a
     // joining call runs the kernels (recover 0x4 / nocopy 0x20000)
-    const unsigned kflags = (flags & ~(SEC_F_ASYNC | SEC_F_STAGED)) | (!host && block_avail ? 0x10000u : 0u) |
-                            (prec ? SEC_F_RECOVER : 0u) | (nocopy ? 0x20000u : 0u);
-    key.insert(key.end(), (const uint8_t *)&kflags, (const uint8_t *)&kflags + sizeof(unsigned));
-    const bool reuse = plan.valid && plan.gen == ctx->dec_tabs.gen && plan.key == key;
-    DecLayout L;
+    key.put((flags & ~(SEC_F_ASYNC | SEC_F_STAGED)) | (!host && block_avail ? 0x10000u : 0u) |
+            (prec ? SEC_F_RECOVER : 0u) | (nocopy ? 0x20000u : 0u));
+    const bool reuse = plan_reusable(plan, ctx->dec_tabs, key);
+    SlotLayout L;
     if (!reuse || host)
-        L = dec_layout(chunks, nchunks, sharenums);
+        L = slot_layout(chunks, nchunks, sharenums);
     if (!reuse) {
         plan.valid = false;
         RC(build_decode_plan(ctx, chunks, nchunks, block_offs, block_avail, L, host, prec, nocopy));
-        plan.key.swap(key);
+        plan.key.swap(key.bytes);
         plan.valid = true;
     }
     ctx->syn_chunks += plan.nsyn;
@@ -3331,18 +3334,7 @@ int decode_core(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks, cons
         return SEC_OK;
     }
     auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        uint64_t o = 0;
-        for (int64_t i = sp.c0; i < sp.c1; ++i) {
-            const sec_dec_chunk &c = chunks[i];
-            for (int s = 0; s < c.k; ++s) {
-                const int from = L.perm[L.first[i] + s];
-                const uint64_t av = slot_avail(c, block_avail, from);
-                jobs.push_back(sec::CopyJob{stage + o, blocks + block_offs[c.slot0 + from], av});
-                if (av < c.B)  // the slot's bytes past its avail are zero
-                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
-                o += c.B;
-            }
-        }
+        gather_slots(chunks, sp.c0, sp.c1, L, block_offs, block_avail, blocks, stage, jobs);
     };
     auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
         uint64_t o = 0;
@@ -3426,41 +3418,36 @@ int sec_repair_batch(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks,
     // zero-filled past their avail, its targets dense in the slab); device mode on every descriptor,
     // sharenum, target, address and avail.
     Plan &plan = ctx->rep_plan;
-    std::vector<uint8_t> key;
-    auto put = [&](const void *p, size_t n) {
-        const uint8_t *b = (const uint8_t *)p;
-        key.insert(key.end(), b, b + n);
-    };
+    PlanKey key;
     if (host) {
         for (int64_t i = 0; i < nchunks; ++i) {
             const sec_rep_chunk &c = chunks[i];
-            put(&c.B, 8);
-            put(&c.ntargets, 4);
-            put(&c.k, 4);
-            put(&c.m, 4);
-            put(sharenums + c.slot0, (size_t)c.k * 4);
+            key.put(c.B);
+            key.put(c.ntargets);
+            key.put(c.k);
+            key.put(c.m);
+            key.put(sharenums + c.slot0, (size_t)c.k * 4);
             if (c.ntargets)
-                put(target_nums + c.tgt0, (size_t)c.ntargets * 4);
+                key.put(target_nums + c.tgt0, (size_t)c.ntargets * 4);
         }
     } else {
-        put(chunks, sizeof(sec_rep_chunk) * (size_t)nchunks);
-        put(sharenums, total_slots * 4);
-        put(block_offs, total_slots * 8);
+        key.put(chunks, sizeof(sec_rep_chunk) * (size_t)nchunks);
+        key.put(sharenums, total_slots * 4);
+        key.put(block_offs, total_slots * 8);
         if (block_avail)
-            put(block_avail, total_slots * 8);
-        put(target_nums, total_tgts * 4);
-        put(target_offs, total_tgts * 8);
+            key.put(block_avail, total_slots * 8);
+        key.put(target_nums, total_tgts * 4);
+        key.put(target_offs, total_tgts * 8);
     }
-    const unsigned kflags = (host ? SEC_F_HOST : 0u) | (!host && block_avail ? 0x10000u : 0u) | (digest ? 0x20000u : 0u);
-    put(&kflags, sizeof(kflags));
-    const bool reuse = plan.valid && plan.gen == ctx->rep_tabs.gen && plan.key == key;
-    RepLayout L;
+    key.put((host ? SEC_F_HOST : 0u) | (!host && block_avail ? 0x10000u : 0u) | (digest ? 0x20000u : 0u));
+    const bool reuse = plan_reusable(plan, ctx->rep_tabs, key);
+    SlotLayout L;
     if (!reuse || host)
-        L = rep_layout(chunks, nchunks, sharenums);
+        L = slot_layout(chunks, nchunks, sharenums);
     if (!reuse) {
         plan.valid = false;
         RC(build_repair_plan(ctx, chunks, nchunks, block_offs, block_avail, target_nums, target_offs, L, host, digest));
-        plan.key.swap(key);
+        plan.key.swap(key.bytes);
         plan.valid = true;
     }
 
@@ -3478,18 +3465,7 @@ int sec_repair_batch(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks,
     // place.
     ++ctx->staged_calls;
     auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        uint64_t o = 0;
-        for (int64_t i = sp.c0; i < sp.c1; ++i) {
-            const sec_rep_chunk &c = chunks[i];
-            for (int s = 0; s < c.k; ++s) {
-                const int from = L.perm[L.first[i] + s];
-                const uint64_t av = rep_avail(c, block_avail, from);
-                jobs.push_back(sec::CopyJob{stage + o, (const void *)((uintptr_t)blocks + block_offs[c.slot0 + from]), av});
-                if (av < c.B)  // the slot's bytes past its avail are zero
-                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
-                o += c.B;
-            }
-        }
+        gather_slots(chunks, sp.c0, sp.c1, L, block_offs, block_avail, blocks, stage, jobs);
     };
     auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
         uint64_t o = 0, g = sp.dig_off;

@@ -300,12 +300,6 @@ constexpr u32 lds_tab_bytes(u32 lanes) { return lds_tab<R, DEC>() ? lanes / 64 *
 #ifndef SEC_DEC_BATCH
 #define SEC_DEC_BATCH sec::kBatchVecs
 #endif
-//   SEC_DEC_LATE                decode: store a batch's present primaries after its GF work
-//                               (1) or as each slot arrives (0): C4 decode +5 %, C2 / C5
-//                               within noise (profiles/r01_sweep_declate.jsonl)
-#ifndef SEC_DEC_LATE
-#define SEC_DEC_LATE 1
-#endif
 #ifndef SEC_ENC_BATCH
 #define SEC_ENC_BATCH sec::kBatchVecs
 #endif
@@ -315,7 +309,9 @@ constexpr u32 lds_tab_bytes(u32 lanes) { return lds_tab<R, DEC>() ? lanes / 64 *
 #define SEC_WIDE_BATCH 8
 #endif
 //   (Rounds 1-5 also tried, and archived: a compile-time k for single-shape workloads, VGPR caps
-//   through amdgpu_waves_per_eu, LDS padding to cap the decode's workgroups per CU.)
+//   through amdgpu_waves_per_eu, LDS padding to cap the decode's workgroups per CU.  SEC_DEC_LATE,
+//   the decode's copies as each slot arrives instead of after the batch's arithmetic, is gone too:
+//   after the arithmetic measured C4 decode +5 %, profiles/r01_sweep_declate.jsonl.)
 // Blocks (slots) per batch of a tile kernel: KB * U = the batch's 16 B vectors per lane
 template <int U, bool W, bool DEC>
 constexpr int batch_blocks()
@@ -352,6 +348,31 @@ __device__ __forceinline__ u32 gf_mul_byte(const u32 *__restrict__ t, u32 x)
             __builtin_amdgcn_perm(t[4], t[4], x >> 6)) & 0xFFu;
 }
 
+// ---- the parts the tile kernels' bodies share ----
+// (Only what compiles to the instruction streams of the code it replaced.  The accumulator
+// zeroing, the batched slot load and the pair / single dispatch stay written out in encode_main,
+// decode_main and repair_main: as helpers, each of the three changed register allocation and
+// instruction counts of the kernels, by a few instructions up to 36 of about 5000.)
+// The lane's U positions, one per u-step of the workgroup, clamped so its 16 bytes end at `valid`
+template <int U>
+__device__ __forceinline__ void tile_pos(u32 (&pos)[U], u32 t, u32 valid)
+{
+    const u32 step = blockDim.x * sec::kLaneBytes;  // bytes one u-step of the workgroup covers
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        pos[u] = min(t + u * step, valid - sec::kLaneBytes);
+}
+
+// acc[r] ^= coefficient(row0 + r) * x for one byte of one slot (tab: the chunk's tables, row0:
+// the slot's first table of this row group)
+template <int R, int N>
+__device__ __forceinline__ void gf_mac_bytes(u32 (&acc)[N], const u32 *__restrict__ tab, u32 row0, u32 x)
+{
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        acc[r] ^= gf_mul_byte(tab + (row0 + r) * sec::kTabDwords, x);
+}
+
 // ---- encode ----------------------------------------------------------------
 // Tile = (chunk, t0, r0): lanes cover t0 + 16*lane + 4096*u.  Every position handled here
 // is < `valid` (all k blocks fully readable there, including the last, shorter data
@@ -385,12 +406,9 @@ template <int R, int U, bool W>
 __device__ __forceinline__ void encode_main(const u8 *__restrict__ in, u8 *__restrict__ par, const sec::EncDesc &d,
                                             const sec::Tile &tl, const u32 *__restrict__ tabs, u32 t)
 {
-    const u32 B = d.B, k = d.k, valid = d.valid;
-    const u32 step = blockDim.x * sec::kLaneBytes;  // bytes one u-step of the workgroup covers
+    const u32 B = d.B, k = d.k;
     u32 pos[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-        pos[u] = min(t + u * step, valid - sec::kLaneBytes);
+    tile_pos(pos, t, d.valid);
     const u8 *row = in + d.in_off;
     u8 *dst = par + d.par_off + (u64)tl.r0 * d.par_stride;
     const u32 *tj = tabs + d.tab + tl.r0 * sec::kTabDwords;
@@ -465,6 +483,17 @@ __device__ __forceinline__ u32 ragged_lane0(u32 valid, u32 t0)
 // Each lane issues its bytes' loads kBatch at a time before using any (a loop of dependent
 // single-byte loads costs one memory latency per block).
 constexpr u32 kBatch = 16;
+
+// Byte tp of slots c0 .. c0 + kBatch - 1 of a decode / repair chunk: zero for slots >= k and for
+// bytes past a slot's avail
+template <class Slots>
+__device__ __forceinline__ void load_slot_bytes(u32 (&x)[kBatch], const u8 *__restrict__ blocks, const Slots &sl,
+                                                u32 slot0, u32 c0, u32 k, u32 tp)
+{
+#pragma unroll
+    for (u32 q = 0; q < kBatch; ++q)
+        x[q] = (c0 + q < k && tp < sl.avail[slot0 + c0 + q]) ? (u32)blocks[sl.off[slot0 + c0 + q] + tp] : 0u;
+}
 
 template <int R>
 __device__ __forceinline__ void encode_ragged(const u8 *__restrict__ in, u8 *__restrict__ par, const sec::EncDesc &d,
@@ -574,9 +603,7 @@ __device__ __forceinline__ void decode_ragged(const u8 *__restrict__ blocks, u8 
             acc[r] = 0;
         for (u32 c0 = 0; c0 < d.k; c0 += kBatch) {
             u32 x[kBatch];
-#pragma unroll
-            for (u32 q = 0; q < kBatch; ++q)
-                x[q] = (c0 + q < d.k && tp < sl.avail[d.slot0 + c0 + q]) ? (u32)blocks[sl.off[d.slot0 + c0 + q] + tp] : 0u;
+            load_slot_bytes(x, blocks, sl, d.slot0, c0, d.k, tp);
 #pragma unroll
             for (u32 q = 0; q < kBatch; ++q)
                 if (c0 + q < d.k) {
@@ -584,9 +611,7 @@ __device__ __forceinline__ void decode_ragged(const u8 *__restrict__ blocks, u8 
                     const u32 orow = sl.row[d.slot0 + c];
                     if (tl.r0 == 0 && orow != 0xFFFFFFFFu && (u64)orow * d.B + tp < d.n)
                         dst[(u64)orow * d.B] = (u8)x[q];
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                        acc[r] ^= gf_mul_byte(tabs + d.tab + (c * d.e + tl.r0 + r) * sec::kTabDwords, x[q]);
+                    gf_mac_bytes<R>(acc, tabs + d.tab, c * d.e + tl.r0, x[q]);
                 }
         }
 #pragma unroll
@@ -604,12 +629,9 @@ __device__ __forceinline__ void decode_main(const u8 *__restrict__ blocks, u8 *_
                                             const u32 *__restrict__ tabs,
                                                          const sec::DecSlots sl)
 {
-    const u32 B = d.B, k = d.k, valid = d.valid;
-    const u32 step = blockDim.x * sec::kLaneBytes;  // bytes one u-step of the workgroup covers
+    const u32 B = d.B, k = d.k;
     u32 pos[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-        pos[u] = min(t + u * step, valid - sec::kLaneBytes);
+    tile_pos(pos, t, d.valid);
     u8 *dst = out + d.out_off;
     const bool copies = tl.r0 == 0;  // row group 0 also copies the present primaries
     const u32 *tj = tabs + d.tab + tl.r0 * sec::kTabDwords;
@@ -623,8 +645,9 @@ __device__ __forceinline__ void decode_main(const u8 *__restrict__ blocks, u8 *_
             acc[r][u] = u32x4{0u, 0u, 0u, 0u};
 
     // Slots go in batches of KB, as in encode_main: every load of a batch before any store
-    // or arithmetic, then the batch in order — each present primary copied to its output
-    // row, every slot fed to the R accumulators.  C2 / C4 are one batch (all loads in flight).
+    // or arithmetic, then every slot fed to the R accumulators, then each present primary
+    // copied to its output row (copies as each slot arrives measured C4 decode -5 %).  C2 / C4
+    // are one batch (all loads in flight).
     constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
     auto batch = [&](u32 c0) {
         constexpr bool LT = lds_tab<R, true>();
@@ -645,49 +668,32 @@ __device__ __forceinline__ void decode_main(const u8 *__restrict__ blocks, u8 *_
                 for (int u = 0; u < U; ++u)
                     xs[c][u] = load16(s + pos[u]);
             }
-        if constexpr (SEC_DEC_LATE) {  // slots in pairs (gf_mac2)
-            if constexpr (R > 0 && kPairRows<R, W>()) {
+        if constexpr (R > 0 && kPairRows<R, W>()) {
 #pragma unroll
-                for (int c = 0; c < KB; c += 2) {
-                    if (c + 1 < KB && c0 + c + 1 < k)
-                        gf_mac2<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R, xs[c + 1],
+            for (int c = 0; c < KB; c += 2) {
+                if (c + 1 < KB && c0 + c + 1 < k)
+                    gf_mac2<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R, xs[c + 1],
                                       tj + (c0 + c + 1) * tstep, vt + (c + 1) * R);
-                    else if (c0 + c < k)
-                        gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
-                }
-            } else if constexpr (R > 0) {
-#pragma unroll
-                for (int c = 0; c < KB; ++c)
-                    if (c0 + c < k)
-                        gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
+                else if (c0 + c < k)
+                    gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
             }
-        } else {
+        } else if constexpr (R > 0) {
 #pragma unroll
             for (int c = 0; c < KB; ++c)
-                if (c0 + c < k) {
-                    const u32 orow = sl.row[d.slot0 + c0 + c];
-                    if (copies && orow != 0xFFFFFFFFu) {
-                        u8 *o = dst + (u64)orow * B;
-#pragma unroll
-                        for (int u = 0; u < U; ++u)
-                            store16<SEC_DEC_ST>(o + pos[u], xs[c][u]);
-                    }
-                    if constexpr (R > 0)
-                        gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
-                }
+                if (c0 + c < k)
+                    gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
         }
-        if (SEC_DEC_LATE)  // the batch's copies after its arithmetic
 #pragma unroll
-            for (int c = 0; c < KB; ++c)
-                if (c0 + c < k) {
-                    const u32 orow = sl.row[d.slot0 + c0 + c];
-                    if (copies && orow != 0xFFFFFFFFu) {
-                        u8 *o = dst + (u64)orow * B;
+        for (int c = 0; c < KB; ++c)
+            if (c0 + c < k) {
+                const u32 orow = sl.row[d.slot0 + c0 + c];
+                if (copies && orow != 0xFFFFFFFFu) {
+                    u8 *o = dst + (u64)orow * B;
 #pragma unroll
-                        for (int u = 0; u < U; ++u)
-                            store16<SEC_DEC_ST>(o + pos[u], xs[c][u]);
-                    }
+                    for (int u = 0; u < U; ++u)
+                        store16<SEC_DEC_ST>(o + pos[u], xs[c][u]);
                 }
+            }
     };
     if constexpr (W) {  // wide k: several batches (see encode_main)
 #pragma unroll 1
@@ -755,12 +761,9 @@ __device__ __forceinline__ void repair_main(const u8 *__restrict__ blocks, u8 *_
                                             const sec::RepDesc &d, const sec::Tile &tl, u32 t,
                                             const u32 *__restrict__ tabs, const sec::RepSlots sl)
 {
-    const u32 k = d.k, valid = d.valid;
-    const u32 step = blockDim.x * sec::kLaneBytes;
+    const u32 k = d.k;
     u32 pos[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-        pos[u] = min(t + u * step, valid - sec::kLaneBytes);
+    tile_pos(pos, t, d.valid);
     const u32 *tj = tabs + d.tab + tl.r0 * sec::kTabDwords;
     const u32 tstep = d.nt * sec::kTabDwords;
 
@@ -839,16 +842,11 @@ __device__ __forceinline__ void repair_ragged(const u8 *__restrict__ blocks, u8 
             acc[r] = 0;
         for (u32 c0 = 0; c0 < d.k; c0 += kBatch) {
             u32 x[kBatch];
+            load_slot_bytes(x, blocks, sl, d.slot0, c0, d.k, tp);
 #pragma unroll
             for (u32 q = 0; q < kBatch; ++q)
-                x[q] = (c0 + q < d.k && tp < sl.avail[d.slot0 + c0 + q]) ? (u32)blocks[sl.off[d.slot0 + c0 + q] + tp] : 0u;
-#pragma unroll
-            for (u32 q = 0; q < kBatch; ++q)
-                if (c0 + q < d.k) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                        acc[r] ^= gf_mul_byte(tabs + d.tab + ((c0 + q) * d.nt + tl.r0 + r) * sec::kTabDwords, x[q]);
-                }
+                if (c0 + q < d.k)
+                    gf_mac_bytes<R>(acc, tabs + d.tab, (c0 + q) * d.nt + tl.r0, x[q]);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r)

@@ -2,7 +2,7 @@
 """Static resource usage and instruction mix of the tile kernels for build-knob variants
 (cross-compiled here, no GPU).  Not product code.
 
-    python tools/kres.py [-DKNOB=V ...] [--filter REGEX] [--mix]
+    python tools/kres.py [-DKNOB=V ...] [--filter REGEX] [--mix] [--save-asm PATH]
 
 Prints per kernel: VGPRs, SGPRs, occupancy (waves/SIMD), static LDS, spills; with --mix the
 top VALU / LDS / scalar-memory instruction counts of each matching kernel's body.
@@ -22,9 +22,12 @@ SRC = os.path.join(ROOT, "storb_amd", "csrc", "kernels.hip")
 
 
 def demangle(n: str) -> str:
-    m = re.search(r"(sec_\w+?kernel)ILi(\d+)ELi(\d+)ELb(\d)E", n)
+    """sec_decode_kernel<4,2,false,0> from _Z17sec_decode_kernelILi4ELi2ELb0ELi0EEv...: every
+    template parameter (int or bool), so the KBX variants of a decode / repair kernel differ."""
+    m = re.search(r"(sec_\w+?kernel)I((?:L[ib]\d+E)+)E", n)
     if m:
-        return f"{m.group(1)}<{m.group(2)},{m.group(3)},{'true' if m.group(4) == '1' else 'false'}>"
+        ps = [v if t == "i" else ("true" if v == "1" else "false") for t, v in re.findall(r"L([ib])(\d+)E", m.group(2))]
+        return f"{m.group(1)}<{','.join(ps)}>"
     m = re.search(r"(sec_\w+)", n)
     return m.group(1) if m else n
 
@@ -32,8 +35,9 @@ def demangle(n: str) -> str:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("defs", nargs="*")
-    ap.add_argument("--filter", default=r"encode_kernel|decode_kernel")
+    ap.add_argument("--filter", default=r"encode_kernel|decode_kernel|repair_kernel")
     ap.add_argument("--mix", action="store_true")
+    ap.add_argument("--save-asm", metavar="PATH", help="also keep the gfx950 assembly there")
     ap.add_argument("--src", default=SRC, help="kernel source (default storb_amd/csrc/kernels.hip)")
     a, extra = ap.parse_known_args()
     a.defs += extra
@@ -56,6 +60,9 @@ def main():
                 cur[k.strip()] = v.strip()
         stem = os.path.splitext(os.path.basename(a.src))[0]
         asm = open(os.path.join(td, f"{stem}-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+        if a.save_asm:
+            with open(a.save_asm, "w") as f:
+                f.write(asm)
     for r in rows:
         nm = demangle(r["name"])
         if not re.search(a.filter, nm):

@@ -44,7 +44,6 @@ VARIANTS = {
     "db8": {"SEC_DEC_BATCH": 8},  # decode KB = 8 / U (valid only for k * U <= 8)
     "db8eb8": {"SEC_DEC_BATCH": 8, "SEC_ENC_BATCH": 8},
     "b4": {"SEC_DEC_BATCH": 4, "SEC_ENC_BATCH": 4},  # KB = 4 / U: valid for k * U <= 4 only
-    "decearly": {"SEC_DEC_LATE": 0},  # decode: copies stored as each slot arrives
     # wide k (W kernels): the earlier 16-vector batches without block pairs for 8-row groups;
     # 4-vector batches; pairs for 8-row groups in the k <= 16 kernels too
     "prevwide": {"SEC_WIDE_BATCH": 16, "SEC_WIDE_PAIR_ROWS": 4},
