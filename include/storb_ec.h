@@ -135,7 +135,7 @@ int sec_sync(sec_ctx *ctx);
 int sec_ctx_set_timing(sec_ctx *ctx, int enable);
 /* Waits for recorded pairs, returns the summed milliseconds and launch count of
  * kind 0 = encode, 1 = decode, 2 = SHA-1, 3 = bignum (APDP), 4 = repair (its kernels and,
- * with digests, their SHA-1), and clears them. */
+ * with digests, their SHA-1), 5 = check, and clears them. */
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches);
 
 /* ---- context options --------------------------------------------------------
@@ -264,6 +264,68 @@ int sec_repair_batch(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks,
                      const uint64_t *block_avail, const uint8_t *blocks,
                      const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out,
                      uint8_t *digests, unsigned flags);
+
+/* ---- check: do the held pieces of a chunk agree with each other ---------------------------
+ * A Reed-Solomon code word carries its own check: of the n > k blocks a caller holds, each one
+ * past any k of them is a fixed GF(2^8) combination of those k (a row of sec_repair_matrix).  The
+ * check predicts every such extra block from k basis blocks and compares it with what is stored:
+ * any corruption confined to at most n - k of the n blocks is detected with certainty, n*B bytes
+ * are read and nothing is written but the results.  No zfec counterpart. */
+typedef struct sec_chk_chunk {
+    uint64_t B;      /* block bytes                                                     */
+    uint64_t slot0;  /* first of the chunk's n entries in sharenums[] / block_offs[] /
+                        block_avail[]                                                   */
+    int32_t n;       /* blocks held, k <= n <= m                                        */
+    int32_t k;
+    int32_t m;
+    int32_t pad;
+} sec_chk_chunk; /* 32 bytes */
+
+typedef struct sec_chk_result {
+    uint64_t first;  /* lowest byte position at which a check row disagrees with its
+                        prediction; UINT64_MAX: the chunk is consistent                 */
+    uint32_t nbad;   /* check rows that disagree anywhere in the chunk                  */
+    uint32_t pad;
+} sec_chk_result; /* 16 bytes */
+
+/* Entries slot0 .. slot0+k-1 of a chunk are its basis (any order; normalised as repair's sources
+ * are), entries slot0+k .. slot0+n-1 its check rows.  Each check row's block as predicted from the
+ * basis is compared with the stored block over all B bytes.
+ * results[c] (8-byte aligned): `first` and `nbad` of chunk c.
+ * row_bad (nullable): one byte per slot entry, indexed as sharenums[]: 1 for a check row that
+ * disagrees somewhere, 0 for one that agrees and for every basis entry.
+ * column (nullable): one byte per slot entry; for an inconsistent chunk the byte of each of its n
+ * entries at position `first` (zero for a position past the entry's avail): the input of
+ * sec_check_locate.  Untouched for a consistent chunk.
+ * block_avail (nullable) as in sec_repair_batch, for basis entries and check rows alike: that many
+ * bytes of the block exist, the rest read as zero (so the prediction there must be zero), and
+ * nothing past them is read.
+ * A chunk with n == k has nothing to check: it is consistent and launches nothing.  More than 8
+ * check rows take ceil((n - k) / 8) passes over the basis.
+ * results, row_bad and column live where the blocks live: device memory, or host memory with
+ * SEC_F_HOST.  Nothing is ever written to the blocks.  Every call starts from clean state.
+ * Flags: none (device pointers; SEC_F_ASYNC allowed) or SEC_F_HOST (host pointers, always staged
+ * through pinned slabs as sec_repair_batch's: n*B bytes per chunk gathered, only the results
+ * scattered back; SEC_F_ASYNC is then SEC_EINVAL); any other flag is SEC_EINVAL.
+ * Errors, all before any device work, in this order: SEC_EINVAL a NULL array, NULL results or
+ * n < 0; SEC_EKM; SEC_ENBLOCKS n < k or n > m; SEC_ESHARENUM; SEC_EDUPSHARE any repeat among the
+ * n sharenums; SEC_ESIZE B >= 2^31. */
+int sec_check_batch(sec_ctx *ctx, const sec_chk_chunk *chunks, int64_t nchunks,
+                    const int32_t *sharenums, const uint64_t *block_offs,
+                    const uint64_t *block_avail, const uint8_t *blocks, sec_chk_result *results,
+                    uint8_t *row_bad, uint8_t *column, unsigned flags);
+
+/* Which single entry explains an inconsistent column (host arithmetic, no device needed).
+ * sharenums: the n block numbers, the first k the basis; column: the n bytes sec_check_batch
+ * returned.  *culprit = -1: the column is a code word; i in [0, n): changing entry i alone makes
+ * it one; -2: inconsistent and no single entry explains it, which is also the answer whenever
+ * n - k < 2 (one check row cannot tell itself from the basis).  The code is MDS, so with two or
+ * more check rows a single-entry explanation is unique; it names the corrupt piece only if one
+ * piece is corrupt at that position.
+ * Errors: sec_repair_matrix's for (k, m, sharenums[0..k), sharenums[k..n), n - k); SEC_EINVAL
+ * also for a NULL column or culprit. */
+int sec_check_locate(int k, int m, const int32_t *sharenums, int n, const uint8_t *column,
+                     int32_t *culprit);
 
 /* ---- piece ids: SHA-1 (piece_hash, /root/reference/storb/util/piece.py:54-68) ----
  * A message is `len` bytes at `addr`, of which the first `avail` exist in

@@ -57,6 +57,15 @@ class sec_rep_chunk(ctypes.Structure):
                 ("ntargets", ctypes.c_int32), ("k", ctypes.c_int32), ("m", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class sec_chk_chunk(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_uint64), ("slot0", ctypes.c_uint64), ("n", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("m", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class sec_chk_result(ctypes.Structure):
+    _fields_ = [("first", ctypes.c_uint64), ("nbad", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
 # numpy mirrors of the descriptor structs (same layout: 4 x u64 + 2 x i32 = 40 B)
 ENC_DTYPE = np.dtype([("in_off", "<u8"), ("n", "<u8"), ("parity_off", "<u8"), ("parity_stride", "<u8"),
                       ("k", "<i4"), ("m", "<i4")], align=True)
@@ -64,6 +73,10 @@ DEC_DTYPE = np.dtype([("out_off", "<u8"), ("B", "<u8"), ("padlen", "<u8"), ("slo
                       ("k", "<i4"), ("m", "<i4")], align=True)
 REP_DTYPE = np.dtype([("B", "<u8"), ("slot0", "<u8"), ("tgt0", "<u8"), ("ntargets", "<i4"), ("k", "<i4"), ("m", "<i4"),
                       ("pad", "<i4")], align=True)  # sec_rep_chunk
+CHK_DTYPE = np.dtype([("B", "<u8"), ("slot0", "<u8"), ("n", "<i4"), ("k", "<i4"), ("m", "<i4"), ("pad", "<i4")],
+                     align=True)  # sec_chk_chunk
+CHK_RESULT_DTYPE = np.dtype([("first", "<u8"), ("nbad", "<u4"), ("pad", "<u4")], align=True)  # sec_chk_result
+CHK_CONSISTENT = 0xFFFFFFFFFFFFFFFF  # sec_chk_result.first of a consistent chunk
 MSG_DTYPE = np.dtype([("addr", "<u8"), ("len", "<u8"), ("avail", "<u8")], align=True)
 COPY_DTYPE = np.dtype([("dst", "<u8"), ("src", "<u8"), ("len", "<u8")], align=True)  # sec_copy
 
@@ -76,6 +89,8 @@ assert ENC_DTYPE.itemsize == ctypes.sizeof(sec_enc_chunk) == 40
 assert MSG_DTYPE.itemsize == ctypes.sizeof(sec_msg) == 24
 assert DEC_DTYPE.itemsize == ctypes.sizeof(sec_dec_chunk) == 40
 assert REP_DTYPE.itemsize == ctypes.sizeof(sec_rep_chunk) == 40
+assert CHK_DTYPE.itemsize == ctypes.sizeof(sec_chk_chunk) == 32
+assert CHK_RESULT_DTYPE.itemsize == ctypes.sizeof(sec_chk_result) == 16
 
 # every symbol include/storb_ec.h declares: name -> (restype, argtypes)
 _vp = ctypes.c_void_p
@@ -103,6 +118,9 @@ _SIGS = {
     "sec_repair_matrix": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp]),
     "sec_repair_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         ctypes.c_uint]),
+    "sec_check_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint]),
+    "sec_check_locate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,
+                                        ctypes.POINTER(ctypes.c_int32)]),
     "sec_sha1_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_uint]),
     "sec_encode_digest_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_uint]),
     "sec_encode_pieces": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_uint]),

@@ -293,6 +293,9 @@ struct SubPlan {
     uint64_t dig_first = 0;                // first digest slot of this unit
     uint64_t dig_off = 0;                  // host mode: digests' offset in the slab output
     size_t off_toff = 0;                   // repair: the targets' addresses (RepSlots::tgt_off)
+    size_t off_cpos = 0, off_echunk = 0;   // check: the entries' caller positions and chunks (ChkSlots)
+    uint32_t nentries = 0;                 // check: entries of the unit's chunks
+    uint64_t chk_rows = 0, chk_col = 0;    // check, host mode: row_bad and column in the slab output
     // repair digests: runs of consecutive digest slots, (first message, count, first slot)
     std::vector<std::array<uint64_t, 3>> sha_runs;
     // syndrome decodes (decode): phase 1 launches (bit-sliced syndromes) and phase 2 launches
@@ -312,6 +315,7 @@ struct Plan {
     DevBuf meta;  // device copy of the metadata image of every sub-plan
     bool valid = false;
     int64_t nsyn = 0, ndirect = 0, nfused = 0;  // decode: chunks with a lost primary, by method
+    uint64_t nflags = 0;                        // check: flag words of the whole call
 };
 
 // Device-resident GF coefficient tables (5 dwords per coefficient), keyed by
@@ -673,13 +677,14 @@ struct sec_ctx {
     hipStream_t own = nullptr;
     hipStream_t ext = nullptr;
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[5];
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[6];  // by timing kind
     std::vector<hipEvent_t> ev_pool;
     hipEvent_t stop_ev = nullptr;  // between timing_begin and timing_end of an attached launch
     PinBuf pin{nullptr, 0, false};  // metadata image staging (its own, not pooled: small, every call)
     hipEvent_t pin_ev = nullptr, meta_ev = nullptr;
-    TableCache enc_tabs, dec_tabs, rep_tabs;
-    Plan enc_plan, dec_plan, sha_plan, bn_plan, rep_plan;
+    TableCache enc_tabs, dec_tabs, rep_tabs, chk_tabs;
+    Plan enc_plan, dec_plan, sha_plan, bn_plan, rep_plan, chk_plan;
+    DevBuf chk_flags;   // check: the flag words of the call in flight (ChkDesc::flag0)
     DevBuf bn_scratch;  // host-mode staging of sec_bn_modexp / mulmod operands
     DevBuf bn_part;     // partial residues of segmented reductions (one region per slot)
     DevBuf syn;         // syndrome rows of device-mode syndrome decodes
@@ -1718,6 +1723,169 @@ int launch_repair_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
     return SEC_OK;
 }
 
+// ---- check plan ---------------------------------------------------------------
+// Preconditions of a check (sec_check_batch): n held blocks, k <= n <= m, all in [0, m) and
+// distinct.  The basis is the first k.
+int check_check(int k, int m, const int32_t *sharenums, int n)
+{
+    if (n < 0 || !sharenums)
+        return SEC_EINVAL;
+    if (k < 1 || m < k || m > 256)
+        return SEC_EKM;
+    if (n < k || n > m)
+        return SEC_ENBLOCKS;
+    for (int i = 0; i < n; ++i)
+        if (sharenums[i] < 0 || sharenums[i] >= m)
+            return SEC_ESHARENUM;
+    bool seen[256] = {false};
+    for (int i = 0; i < n; ++i) {
+        if (seen[sharenums[i]])
+            return SEC_EDUPSHARE;
+        seen[sharenums[i]] = true;
+    }
+    return SEC_OK;
+}
+
+// The repair plan with check rows in place of targets: per chunk the tables of the repair matrix
+// of its check rows over its basis (layout [slot][row][5], cached by basis and check rows), its
+// n entries (the basis in normalised order, then the check rows in the caller's), tiles as a
+// repair's (add_work) over valid = the least avail of all n, and its flag words in ctx->chk_flags:
+// one for the first differing position, one per check row (ChkDesc::flag0).  Host mode stages
+// all n entries densely and returns results, row_bad and column through the slab output.
+int build_check_plan(sec_ctx *ctx, const sec_chk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                     const uint64_t *block_offs, const uint64_t *block_avail, const SlotLayout &L, bool host)
+{
+    Plan &plan = ctx->chk_plan;
+    TableCache &tc = ctx->chk_tabs;
+    std::vector<PendingExpand> pending;
+    std::vector<uint32_t> tab_of;
+    auto want = [&](int64_t i, std::string &key) -> size_t {
+        const sec_chk_chunk &c = chunks[i];
+        if (c.n == c.k)
+            return 0;
+        key = slots_key(c.k, c.m, &L.idx[L.first[i]]) + "|";
+        for (int r = c.k; r < c.n; ++r)
+            key += std::to_string(sharenums[c.slot0 + r]) + ",";
+        return (size_t)c.k * (c.n - c.k);
+    };
+    auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
+        const sec_chk_chunk &c = chunks[i];
+        const int k = c.k, nr = c.n - c.k;
+        const int *idx = &L.idx[L.first[i]];
+        std::vector<uint8_t> rm;
+        if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k),
+                                std::vector<int>(sharenums + c.slot0 + k, sharenums + c.slot0 + c.n), rm))
+            return (int)SEC_ESINGULAR;
+        cf.resize((size_t)k * nr);
+        for (int s = 0; s < k; ++s)
+            for (int r = 0; r < nr; ++r)
+                cf[(size_t)s * nr + r] = rm[(size_t)r * k + s];
+        return (int)SEC_OK;
+    };
+    RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
+
+    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return (uint64_t)chunks[i].n * chunks[i].B; },
+                                    (size_t)ctx->opt[O_SLAB_BYTES]);
+    Image img;
+    plan.subs.clear();
+    plan.nflags = 0;
+    for (auto [c0, c1] : ranges) {
+        SubPlan sp;
+        sp.c0 = c0;
+        sp.c1 = c1;
+        std::vector<sec::ChkDesc> descs((size_t)(c1 - c0));
+        std::vector<uint64_t> soff;
+        std::vector<uint32_t> savail, cpos, echunk;
+        Bins bins;
+        std::vector<sec::TailItem> tail;
+        for (int64_t i = c0; i < c1; ++i) {
+            const sec_chk_chunk &c = chunks[i];
+            const uint64_t base = L.first[i];
+            sec::ChkDesc &d = descs[i - c0];
+            d.B = (uint32_t)c.B;
+            d.k = (uint32_t)c.k;
+            d.nr = (uint32_t)(c.n - c.k);
+            d.tab = tab_of[i];
+            d.slot0 = (uint32_t)soff.size();
+            d.flag0 = (uint32_t)plan.nflags;
+            d.res = (uint32_t)(host ? i - c0 : i);
+            d.cslot0 = (uint32_t)(host ? soff.size() : c.slot0);
+            d.pad = 0;
+            plan.nflags += 1 + d.nr;
+            uint64_t min_avail = c.B;
+            for (int e = 0; e < c.n; ++e) {
+                const int from = e < c.k ? L.perm[base + e] : e;
+                soff.push_back(host ? sp.in_bytes + (uint64_t)e * c.B : block_offs[c.slot0 + from]);
+                const uint64_t av = host ? c.B : slot_avail(c, block_avail, from);  // staged entries are zero-filled
+                savail.push_back((uint32_t)av);
+                cpos.push_back((uint32_t)from);
+                echunk.push_back((uint32_t)(i - c0));
+                min_avail = std::min(min_avail, av);
+            }
+            d.valid = (uint32_t)min_avail;
+            sp.in_bytes += (uint64_t)c.n * c.B;
+            if (d.nr > 0)
+                add_work(bins, tail, (uint32_t)(i - c0), c.B, (int64_t)min_avail, (int)d.nr, c.k, true, false,
+                         dec_small_kb(c.k));
+        }
+        std::vector<sec::Tile> tiles;
+        flatten(bins, sp.groups, tiles, true);
+        sp.ntail = (uint32_t)tail.size();
+        // host mode's slab output: the results, then row_bad and column, one byte per entry each
+        sp.chk_rows = (uint64_t)(c1 - c0) * sizeof(sec::ChkResult);
+        sp.chk_col = sp.chk_rows + soff.size();
+        sp.out_bytes = sp.chk_col + soff.size();
+        sp.off_desc = img.put(descs.data(), descs.size() * sizeof(sec::ChkDesc));
+        sp.off_tiles = img.put(tiles.data(), tiles.size() * sizeof(sec::Tile));
+        sp.off_tail = img.put(tail.data(), tail.size() * sizeof(sec::TailItem));
+        sp.off_savail = img.put(savail.data(), savail.size() * 4);
+        sp.off_cpos = img.put(cpos.data(), cpos.size() * 4);
+        sp.off_echunk = img.put(echunk.data(), echunk.size() * 4);
+        sp.nentries = (uint32_t)echunk.size();
+        soff.resize(soff.size() + sec::kBatchVecs, 0);  // the kernel loads a batch's offsets unconditionally
+        sp.off_soff = img.put(soff.data(), soff.size() * 8);
+        plan.subs.push_back(std::move(sp));
+    }
+    if (plan.nflags >= UINT32_MAX)
+        return SEC_EINVAL;
+    RC(upload_plan(ctx, plan, img, tc, pending));
+    plan.gen = tc.gen;
+    return SEC_OK;
+}
+
+// The check kernels of one launch unit, then its results (timed as kind 5 by the caller's stream
+// events only when there is a check row: a unit of n == k chunks launches the results alone)
+int launch_check_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const uint8_t *blocks,
+                     sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, hipStream_t s)
+{
+    const sec::ChkDesc *dd = plan.meta.as<sec::ChkDesc>(sp.off_desc);
+    const sec::Tile *dt = plan.meta.as<sec::Tile>(sp.off_tiles);
+    const uint32_t *tabs = ctx->chk_tabs.buf.as<uint32_t>();
+    const sec::ChkSlots sl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
+                           plan.meta.as<uint32_t>(sp.off_cpos), plan.meta.as<uint32_t>(sp.off_echunk),
+                           ctx->chk_flags.as<uint32_t>()};
+    const bool work = !sp.groups.empty() || sp.ntail;
+    hipEvent_t t0 = nullptr;
+    if (work)
+        RC(timing_begin(ctx, &t0, s));
+    for (const Group &g : sp.groups) {
+        int e = sec_launch_check(g.rows, g.U, g.wide, g.lanes, blocks, dd, dt + g.first, g.count, tabs, sl, s, g.mfma);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_check_kernel");
+    }
+    if (sp.ntail) {
+        int e = sec_launch_check_tail(blocks, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_check_tail");
+    }
+    int e = sec_launch_check_final(blocks, dd, sp.nentries, sl, results, row_bad, column, s);
+    if (e)
+        return hip_fail((hipError_t)e, "sec_check_final");
+    if (work)
+        RC(timing_end(ctx, t0, 5, s));
+    return SEC_OK;
+}
+
 // ---- pinned caller memory: the zero-copy host path ----------------------------
 // A SEC_F_HOST encode / decode whose caller buffers all lie in page-locked host memory the
 // HIP runtime maps at the same address on the device (hipHostMalloc / sec_host_alloc,
@@ -2087,11 +2255,14 @@ void sec_ctx_destroy(sec_ctx *ctx)
     ctx->enc_tabs.buf.release();
     ctx->dec_tabs.buf.release();
     ctx->rep_tabs.buf.release();
+    ctx->chk_tabs.buf.release();
     ctx->enc_plan.meta.release();
     ctx->dec_plan.meta.release();
     ctx->sha_plan.meta.release();
     ctx->bn_plan.meta.release();
     ctx->rep_plan.meta.release();
+    ctx->chk_plan.meta.release();
+    ctx->chk_flags.release();
     ctx->bn_scratch.release();
     ctx->bn_part.release();
     ctx->syn.release();
@@ -2141,7 +2312,7 @@ int sec_ctx_set_option(sec_ctx *ctx, const char *name, int64_t value)
     RC(set_dev(ctx));
     RC(drain_all(ctx));  // nothing in flight may still use a plan or pool built the old way
     ctx->opt.v[i] = value;
-    for (Plan *p : {&ctx->enc_plan, &ctx->dec_plan, &ctx->sha_plan, &ctx->bn_plan, &ctx->rep_plan})
+    for (Plan *p : {&ctx->enc_plan, &ctx->dec_plan, &ctx->sha_plan, &ctx->bn_plan, &ctx->rep_plan, &ctx->chk_plan})
         p->valid = false;
     if (i == O_COPY_THREADS) {
         ctx->tasks.reset();
@@ -2166,7 +2337,7 @@ const char *sec_option_name(int index)
 
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches)
 {
-    if (!ctx || kind < 0 || kind > 4 || !total_ms || !launches)
+    if (!ctx || kind < 0 || kind > 5 || !total_ms || !launches)
         return SEC_EINVAL;
     RC(set_dev(ctx));
     double tot = 0;
@@ -3485,6 +3656,134 @@ int sec_repair_batch(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks,
         return launch_repair_sub(ctx, plan, sp, din, dout, dout + sp.dig_off, s);
     };
     return run_pipeline(ctx, plan, gather, scatter, launch);
+}
+
+// ---- check: the held pieces of a chunk against each other ---------------------------------
+int sec_check_batch(sec_ctx *ctx, const sec_chk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                    const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
+                    sec_chk_result *results, uint8_t *row_bad, uint8_t *column, unsigned flags)
+{
+    static_assert(sizeof(sec_chk_result) == sizeof(sec::ChkResult) && sizeof(sec_chk_chunk) == 32, "ABI layout");
+    if (!ctx || nchunks < 0 || (nchunks > 0 && (!chunks || !sharenums || !block_offs || !results)) ||
+        (flags & ~(SEC_F_HOST | SEC_F_ASYNC)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
+        return SEC_EINVAL;
+    if (nchunks == 0)
+        return SEC_OK;
+    if (nchunks >= (int64_t)UINT32_MAX)
+        return SEC_EINVAL;
+    const bool host = flags & SEC_F_HOST;
+    RC(set_dev(ctx));
+
+    // preconditions of every chunk before any device work
+    uint64_t total_slots = 0;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const sec_chk_chunk &c = chunks[i];
+        RC(check_check(c.k, c.m, sharenums + c.slot0, c.n));
+        if (c.B >= (1ull << 31))
+            return SEC_ESIZE;
+        total_slots = std::max<uint64_t>(total_slots, c.slot0 + (uint64_t)c.n);
+    }
+    if (total_slots >= UINT32_MAX)
+        return SEC_EINVAL;
+    // (blocks may be NULL: block_offs are then absolute addresses)
+
+    // Plan key: host mode keys on shapes and sharenums only (its entries are staged densely,
+    // zero-filled past their avail); device mode on every descriptor, sharenum, address and avail.
+    // The outputs' addresses are launch arguments, not part of the plan.
+    Plan &plan = ctx->chk_plan;
+    PlanKey key;
+    if (host) {
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const sec_chk_chunk &c = chunks[i];
+            key.put(c.B);
+            key.put(c.n);
+            key.put(c.k);
+            key.put(c.m);
+            key.put(sharenums + c.slot0, (size_t)c.n * 4);
+        }
+    } else {
+        key.put(chunks, sizeof(sec_chk_chunk) * (size_t)nchunks);
+        key.put(sharenums, total_slots * 4);
+        key.put(block_offs, total_slots * 8);
+        if (block_avail)
+            key.put(block_avail, total_slots * 8);
+    }
+    key.put((host ? SEC_F_HOST : 0u) | (!host && block_avail ? 0x10000u : 0u));
+    const bool reuse = plan_reusable(plan, ctx->chk_tabs, key);
+    SlotLayout L;
+    if (!reuse || host)
+        L = slot_layout(chunks, nchunks, sharenums);
+    if (!reuse) {
+        plan.valid = false;
+        RC(build_check_plan(ctx, chunks, nchunks, sharenums, block_offs, block_avail, L, host));
+        plan.key.swap(key.bytes);
+        plan.valid = true;
+    }
+    // every call starts from clean flag words (0xFFFFFFFF: no position yet, row agrees), whatever
+    // the last call on this plan found
+    RC(ctx->chk_flags.ensure((size_t)plan.nflags * 4));
+    CK(hipMemsetAsync(ctx->chk_flags.p, 0xFF, (size_t)plan.nflags * 4, ctx->stream()));
+
+    if (!host) {
+        RC(launch_check_sub(ctx, plan, plan.subs[0], blocks, (sec::ChkResult *)results, row_bad, column,
+                            ctx->stream()));
+        if (!(flags & SEC_F_ASYNC))
+            CK(hipStreamSynchronize(ctx->stream()));
+        return SEC_OK;
+    }
+    // Host mode is always staged, as repair's: all n entries are gathered into pinned slabs, only
+    // the results come back.  column passes through a buffer of its own so that a consistent
+    // chunk's bytes stay untouched.
+    ++ctx->staged_calls;
+    std::vector<uint8_t> col(column ? (size_t)total_slots : 0);
+    auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        uint64_t o = 0;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const sec_chk_chunk &c = chunks[i];
+            for (int e = 0; e < c.n; ++e) {
+                const int from = e < c.k ? L.perm[L.first[i] + e] : e;
+                const uint64_t av = slot_avail(c, block_avail, from);
+                jobs.push_back(sec::CopyJob{stage + o, (const void *)((uintptr_t)blocks + block_offs[c.slot0 + from]), av});
+                if (av < c.B)  // the entry's bytes past its avail are zero
+                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
+                o += c.B;
+            }
+        }
+    };
+    auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        jobs.push_back(sec::CopyJob{results + sp.c0, stage, (uint64_t)(sp.c1 - sp.c0) * sizeof(sec_chk_result)});
+        uint64_t o = 0;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const sec_chk_chunk &c = chunks[i];
+            if (row_bad)
+                jobs.push_back(sec::CopyJob{row_bad + c.slot0, stage + sp.chk_rows + o, (uint64_t)c.n});
+            if (column)
+                jobs.push_back(sec::CopyJob{col.data() + c.slot0, stage + sp.chk_col + o, (uint64_t)c.n});
+            o += (uint64_t)c.n;
+        }
+    };
+    auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
+        return launch_check_sub(ctx, plan, sp, din, (sec::ChkResult *)dout, row_bad ? dout + sp.chk_rows : nullptr,
+                                column ? dout + sp.chk_col : nullptr, s);
+    };
+    RC(run_pipeline(ctx, plan, gather, scatter, launch));
+    if (column)
+        for (int64_t i = 0; i < nchunks; ++i)
+            if (results[i].first != UINT64_MAX)
+                memcpy(column + chunks[i].slot0, col.data() + chunks[i].slot0, (size_t)chunks[i].n);
+    return SEC_OK;
+}
+
+int sec_check_locate(int k, int m, const int32_t *sharenums, int n, const uint8_t *column, int32_t *culprit)
+{
+    RC(check_repair(k, m, sharenums, sharenums ? sharenums + k : nullptr, n - k));
+    if (!column || !culprit)
+        return SEC_EINVAL;
+    int who = -2;
+    if (!sec::check_locate(k, m, std::vector<int>(sharenums, sharenums + n), column, &who))
+        return SEC_ESINGULAR;
+    *culprit = who;
+    return SEC_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -224,4 +224,53 @@ inline bool repair_matrix(int k, int m, const std::vector<int> &idx, const std::
     return true;
 }
 
+// Which single entry explains an inconsistent column of a check (sec_check_locate).  sharenums:
+// the n held blocks in the caller's order, the first k the basis; column: their n bytes at one
+// position.  With d_j = (check row j as predicted from the basis) ^ (its stored byte):
+//   every d_j zero                      -1: the column is a code word
+//   fewer than two check rows           -2: one row cannot tell itself from the basis
+//   exactly one d_j nonzero             k + j: a basis error would reach every row (R[j][s] != 0, MDS)
+//   every d_j = R[j][s] * e for one s   the caller's position of basis slot s (error value e)
+//   else                                -2: no single entry explains it
+// false if the basis' decode matrix is singular (never, for distinct sharenums of this code).
+inline bool check_locate(int k, int m, const std::vector<int> &sharenums, const uint8_t *column, int *culprit)
+{
+    const Gf &g = gf();
+    const int n = (int)sharenums.size(), r = n - k;
+    std::vector<int> idx(sharenums.begin(), sharenums.begin() + k), perm;
+    normalise_slots(k, idx, perm);
+    std::vector<uint8_t> rm;
+    if (!repair_matrix(k, m, idx, std::vector<int>(sharenums.begin() + k, sharenums.end()), rm))
+        return false;
+    std::vector<uint8_t> d((size_t)r, 0);
+    int nonzero = 0, last = -1;
+    for (int j = 0; j < r; ++j) {
+        uint8_t p = column[k + j];
+        for (int s = 0; s < k; ++s)
+            p ^= g.mul(rm[(size_t)j * k + s], column[perm[s]]);
+        d[j] = p;
+        if (p) {
+            ++nonzero;
+            last = j;
+        }
+    }
+    *culprit = -2;
+    if (nonzero == 0)
+        *culprit = -1;
+    else if (r >= 2 && nonzero == 1)
+        *culprit = k + last;
+    else if (r >= 2 && nonzero == r)
+        for (int s = 0; s < k && *culprit == -2; ++s) {
+            if (!rm[s])
+                continue;
+            const uint8_t e = g.mul(d[0], g.inv[rm[s]]);
+            bool all = true;
+            for (int j = 1; j < r && all; ++j)
+                all = g.mul(rm[(size_t)j * k + s], e) == d[j];
+            if (all)
+                *culprit = perm[s];
+        }
+    return true;
+}
+
 }  // namespace sec

@@ -896,6 +896,261 @@ __global__ __launch_bounds__(256) void sec_repair_tail(const u8 *__restrict__ bl
     }
 }
 
+// ---- check: the held pieces of a chunk against each other ---------------------------------------
+// Check row r of a chunk, as predicted from its k basis slots (XOR_c Rm[r][c] * slot_c, the repair
+// matrix's row for that block), must equal the stored block.  The decomposition, the tables and
+// the slot loads are repair_main's (a sibling, not a shared body: see DESIGN §5 "Check"); what
+// differs is both ends.  The accumulators start as the stored rows instead of zero (kRowsFirst), so
+// those loads are the first the lane issues and their latency lies under the slots' loads and the
+// arithmetic; after the last slot an accumulator IS predicted ^ stored.
+// The epilogue ORs the accumulators: all zero (the clean path) ends the lane with no store at all.
+// Otherwise the row's flag word is cleared (plain store; every writer stores the same 0) and the
+// position of its first differing byte goes into the chunk's word by atomicMin.
+// Positions < valid = min(B, every entry's avail) are the tiles'; [valid, B) goes byte by byte on
+// the chunk's last tile of each row group, an entry's bytes past its avail reading as zero.
+//
+// When a tile loads its stored rows.  Loaded ahead of the slots, the compiler keeps them in
+// registers of their own through the arithmetic and XORs them in last (it reorders the XOR chain):
+// 4 VGPRs per row on top of repair's.  Where that no longer fits the 128 VGPRs of a 1024-lane
+// workgroup (8 rows over the wide-k batches; 7 and 8 rows over a 16-slot batch: 10, 4 and 20 VGPRs
+// spilled, tools/kres.py) they are loaded later, into registers the slots have freed: over a
+// 16-slot batch half-way through it (kRowsMid), with the other half's arithmetic still ahead of
+// them; in the wide-k loop after the last slot (kRowsLast).
+constexpr int kRowsFirst = 0, kRowsMid = 1, kRowsLast = 2;
+template <int R, bool W, int KB>
+constexpr int check_rows_when()
+{
+    return W ? (R <= 7 ? kRowsFirst : kRowsLast) : (KB <= 4 || R <= 6 ? kRowsFirst : kRowsMid);
+}
+
+__device__ __forceinline__ void check_report(const sec::ChkDesc &d, const sec::ChkSlots sl, u32 row, u32 at)
+{
+    atomicMin(sl.flags + d.flag0, at);
+    sl.flags[d.flag0 + 1 + row] = 0u;
+}
+
+template <int R, int U, bool W, int KBX>
+__device__ __forceinline__ void check_main(const u8 *__restrict__ blocks, const sec::ChkDesc &d, const sec::Tile &tl,
+                                           u32 t, const u32 *__restrict__ tabs, const sec::ChkSlots sl)
+{
+    const u32 k = d.k;
+    u32 pos[U];
+    tile_pos(pos, t, d.valid);
+    const u32 *tj = tabs + d.tab + tl.r0 * sec::kTabDwords;
+    const u32 tstep = d.nr * sec::kTabDwords;
+
+    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
+    constexpr int WHEN = check_rows_when<R, W, KB>();
+    const u64 *ro = sl.off + d.slot0 + k + tl.r0;  // the stored rows of this group
+    u32x4 acc[R][U];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const u8 *s = blocks + ro[r];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            acc[r][u] = WHEN == kRowsFirst ? load16(s + pos[u]) : u32x4{0u, 0u, 0u, 0u};
+    }
+    // kRowsMid / kRowsLast: the stored rows into registers the slots have left.  The empty asm
+    // makes the lane's position wait for an accumulator as it stands at that point, so the loads
+    // cannot be hoisted above the arithmetic before it, where they would spill.
+    u32x4 st[R][U];
+    auto load_rows = [&]() {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            asm volatile("" : "+v"(pos[u]) : "v"(acc[R - 1][u][3]));
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const u8 *s = blocks + ro[r];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                st[r][u] = load16(s + pos[u]);
+        }
+    };
+
+    // slots in batches of KB, every load of a batch before its arithmetic (decode_main)
+    auto batch = [&](u32 c0) {
+        constexpr bool LT = lds_tab<R, true>();
+        const u32x2 *vt = wave_tabs<KB, R, LT>(tj, tstep, c0, k);
+        u64 so[KB];  // (the plan pads sl.off by kBatchVecs entries)
+        const u64 *sop = sl.off + d.slot0 + c0;
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+            so[c] = sop[c];
+        u32x4 xs[KB][U];
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+            if (c0 + c < k) {
+                const u8 *s = blocks + so[c];
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    xs[c][u] = load16(s + pos[u]);
+            }
+        if constexpr (kPairRows<R, W>()) {
+#pragma unroll
+            for (int c = 0; c < KB; c += 2) {
+                if (c + 1 < KB && c0 + c + 1 < k)
+                    gf_mac2<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R, xs[c + 1],
+                                      tj + (c0 + c + 1) * tstep, vt + (c + 1) * R);
+                else if (c0 + c < k)
+                    gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < KB; ++c) {
+                if (c0 + c < k)
+                    gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
+                if constexpr (WHEN == kRowsMid)
+                    if (c == KB / 2 - 1)
+                        load_rows();
+            }
+        }
+    };
+    static_assert(WHEN != kRowsMid || (!W && !kPairRows<R, W>()), "kRowsMid: one batch, slots one by one");
+    if constexpr (W) {  // wide k: several batches (see encode_main)
+#pragma unroll 1
+        for (u32 c0 = 0; c0 < k; c0 += KB)
+            batch(c0);
+    } else {
+        batch(0);  // the plan guarantees k <= KB here
+    }
+    if constexpr (WHEN == kRowsLast)
+        load_rows();
+    if constexpr (WHEN != kRowsFirst) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                acc[r][u] ^= st[r][u];
+    }
+    u32 any = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            any |= acc[r][u][0] | acc[r][u][1] | acc[r][u][2] | acc[r][u][3];
+    if (any == 0)
+        return;
+    // (one pointer and constant offsets: a word address per row, formed ahead of the branch, cost
+    // the 8-row kernels scalar registers they do not have)
+    u32 *first = sl.flags + d.flag0, *rows = first + 1 + tl.r0;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const u64 lo = acc[r][u][0] | (u64)acc[r][u][1] << 32, hi = acc[r][u][2] | (u64)acc[r][u][3] << 32;
+            if (lo | hi) {
+                atomicMin(first, pos[u] + (lo ? (u32)__builtin_ctzll(lo) >> 3 : 8u + ((u32)__builtin_ctzll(hi) >> 3)));
+                rows[r] = 0u;
+            }
+        }
+}
+
+// Byte tp of check row r of a chunk as predicted from its basis, XOR the stored byte: nonzero when
+// they differ.  An entry's bytes past its avail read as zero.
+__device__ __forceinline__ u32 check_byte(const u8 *__restrict__ blocks, const sec::ChkDesc &d,
+                                          const u32 *__restrict__ tabs, const sec::ChkSlots sl, u32 r, u32 tp)
+{
+    auto entry_byte = [&](u32 e) -> u32 {
+        return tp < sl.avail[d.slot0 + e] ? (u32)blocks[sl.off[d.slot0 + e] + tp] : 0u;
+    };
+    u32 acc = entry_byte(d.k + r);
+    for (u32 c = 0; c < d.k; ++c)
+        acc ^= gf_mul_byte(tabs + d.tab + (c * d.nr + r) * sec::kTabDwords, entry_byte(c));
+    return acc;
+}
+
+// The chunk's ragged end [valid, B), byte by byte, for this tile's R check rows: the stored rows'
+// bytes first, then every slot's byte loaded once, kBatch slots at a time (repair_ragged; a loop
+// of dependent single-byte loads cost C4, 4 ragged positions per chunk, 2.3x the whole kernel).
+template <int R>
+__device__ __forceinline__ void check_ragged(const u8 *__restrict__ blocks, const sec::ChkDesc &d, const sec::Tile &tl,
+                                             const u32 *__restrict__ tabs, const sec::ChkSlots sl)
+{
+    const u32 row0 = d.slot0 + d.k + tl.r0;
+    for (u32 i = ragged_lane0(d.valid, tl.t0); i < tl.ntail; i += blockDim.x) {
+        const u32 tp = d.valid + i;
+        u32 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            acc[r] = tp < sl.avail[row0 + r] ? (u32)blocks[sl.off[row0 + r] + tp] : 0u;
+        for (u32 c0 = 0; c0 < d.k; c0 += kBatch) {
+            u32 x[kBatch];
+            load_slot_bytes(x, blocks, sl, d.slot0, c0, d.k, tp);
+#pragma unroll
+            for (u32 q = 0; q < kBatch; ++q)
+                if (c0 + q < d.k)
+                    gf_mac_bytes<R>(acc, tabs + d.tab, (c0 + q) * d.nr + tl.r0, x[q]);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (acc[r])
+                check_report(d, sl, tl.r0 + r, tp);
+    }
+}
+
+// KBX > 0: slots per load batch fixed at KBX, as sec_repair_kernel's
+template <int R, int U, bool W, int KBX = 0>
+__global__ __launch_bounds__(sec::max_lanes(R, U)) void sec_check_kernel(const u8 *__restrict__ blocks,
+                                                        const sec::ChkDesc *__restrict__ descs,
+                                                        const sec::Tile *__restrict__ tiles,
+                                                        const u32 *__restrict__ tabs,
+                                                        const sec::ChkSlots sl)
+{
+    static_assert(R >= 1, "a check tile has check rows");
+    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::ChkDesc d = descs[tl.chunk];
+    const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
+    if (t < d.valid)
+        check_main<R, U, W, KBX>(blocks, d, tl, t, tabs, sl);
+    if (tl.ntail)
+        check_ragged<R>(blocks, d, tl, tabs, sl);
+}
+
+// One thread per (chunk, position) of the chunks too small for a tile (valid < 16): every check
+// row's byte there.
+__global__ __launch_bounds__(256) void sec_check_tail(const u8 *__restrict__ blocks,
+                                                      const sec::ChkDesc *__restrict__ descs,
+                                                      const sec::TailItem *__restrict__ items, u32 nitems,
+                                                      const u32 *__restrict__ tabs, const sec::ChkSlots sl)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nitems)
+        return;
+    const sec::TailItem it = items[i];
+    const sec::ChkDesc d = descs[it.chunk];
+    for (u32 r = 0; r < d.nr; ++r)
+        if (check_byte(blocks, d, tabs, sl, r, it.t))
+            check_report(d, sl, r, it.t);
+}
+
+// One thread per entry, after the kernels above: a check row's flag into row_bad (basis entries 0)
+// and, for an inconsistent chunk, the entry's byte at the first differing position into column,
+// both indexed in the caller's order; the chunk's first entry also turns the flag words into the
+// chunk's result.  (One thread per chunk, looping over its entries, took a third of C4's time.)
+__global__ __launch_bounds__(256) void sec_check_final(const u8 *__restrict__ blocks,
+                                                       const sec::ChkDesc *__restrict__ descs, u32 nentries,
+                                                       const sec::ChkSlots sl, sec::ChkResult *__restrict__ results,
+                                                       u8 *__restrict__ row_bad, u8 *__restrict__ column)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nentries)
+        return;
+    const sec::ChkDesc d = descs[sl.echunk[i]];
+    const u32 e = i - d.slot0;
+    const u32 first = sl.flags[d.flag0];  // 0xFFFFFFFF: no row differs
+    const u32 at = d.cslot0 + sl.cpos[i];
+    if (row_bad)
+        row_bad[at] = e >= d.k && sl.flags[d.flag0 + 1 + e - d.k] == 0u;
+    if (column && first != ~0u)
+        column[at] = first < sl.avail[i] ? blocks[sl.off[i] + first] : (u8)0;
+    if (e == 0) {
+        u32 nbad = 0;
+        for (u32 r = 0; r < d.nr; ++r)
+            nbad += sl.flags[d.flag0 + 1 + r] == 0u;
+        results[d.res] = sec::ChkResult{nbad ? (u64)first : ~(u64)0, nbad, 0u};
+    }
+}
+
 // ---- SHA-1 of pieces (storb piece ids, /root/reference/storb/util/piece.py:54-68) ----
 // One lane per message: SHA-1 is a sequential chain of 64-byte compressions, so a
 // message cannot be split; the kernel is latency-bound on each lane's round chain
@@ -1344,6 +1599,32 @@ hipError_t dispatch_rep(int rows, const u8 *b, u8 *o, const sec::RepDesc *d, con
     }
 }
 
+template <int R, int U, bool W, int KBX>
+hipError_t launch_chk(const u8 *blocks, const sec::ChkDesc *descs, const sec::Tile *tiles, u32 ntiles, const u32 *tabs,
+                      sec::ChkSlots sl, u32 lanes, hipStream_t s)
+{
+    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
+    return launch_shm(sec_check_kernel<R, U, W, KBX>, dim3(ntiles), dim3(lanes), lds_tab_bytes<KB, R, true>(lanes), s,
+                      blocks, descs, tiles, tabs, sl);
+}
+
+template <int U, bool W, int KBX = 0>
+hipError_t dispatch_chk(int rows, const u8 *b, const sec::ChkDesc *d, const sec::Tile *t, u32 nt, const u32 *tabs,
+                        sec::ChkSlots sl, u32 lanes, hipStream_t s)
+{
+    switch (rows) {
+    case 1: return launch_chk<1, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
+    case 2: return launch_chk<2, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
+    case 3: return launch_chk<3, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
+    case 4: return launch_chk<4, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
+    case 5: return launch_chk<5, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
+    case 6: return launch_chk<6, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
+    case 7: return launch_chk<7, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
+    case 8: return launch_chk<8, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace
 
 void sec_next_launch_events(void **start, void **stop)
@@ -1472,4 +1753,42 @@ int sec_launch_repair_tail(const uint8_t *blocks, uint8_t *out, const sec::RepDe
         return hipSuccess;
     return launch(sec_repair_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out, descs,
                   items, nitems, tabs, sl);
+}
+
+int sec_launch_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, const sec::ChkDesc *descs,
+                     const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs, sec::ChkSlots sl, void *stream,
+                     int kb)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    if (rows < 1 || U != 1 || lanes < 64 || lanes % 64 || lanes > sec::max_lanes(rows, U))
+        return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const u32 L = (u32)lanes;
+    if (kb) {  // small load batches: tiles of chunks with k <= kb only
+        if (wide || kb != 4)
+            return hipErrorInvalidValue;
+        return dispatch_chk<1, false, 4>(rows, blocks, descs, tiles, ntiles, tabs, sl, L, s);
+    }
+    if (wide)
+        return dispatch_chk<1, true>(rows, blocks, descs, tiles, ntiles, tabs, sl, L, s);
+    return dispatch_chk<1, false>(rows, blocks, descs, tiles, ntiles, tabs, sl, L, s);
+}
+
+int sec_launch_check_tail(const uint8_t *blocks, const sec::ChkDesc *descs, const sec::TailItem *items,
+                          uint32_t nitems, const uint32_t *tabs, sec::ChkSlots sl, void *stream)
+{
+    if (nitems == 0)
+        return hipSuccess;
+    return launch(sec_check_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, descs, items,
+                  nitems, tabs, sl);
+}
+
+int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uint32_t nentries, sec::ChkSlots sl,
+                           sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, void *stream)
+{
+    if (nentries == 0)
+        return hipSuccess;
+    return launch(sec_check_final, dim3((nentries + 255) / 256), dim3(256), (hipStream_t)stream, blocks, descs,
+                  nentries, sl, results, row_bad, column);
 }

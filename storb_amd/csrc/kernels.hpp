@@ -87,6 +87,38 @@ struct RepSlots {
     const uint64_t *tgt_off;  // target address: out + tgt_off[target], any byte alignment
 };
 
+// One check chunk, device copy (40 B): nr check rows predicted from k basis blocks and compared
+// with the stored rows.  Its n = k + nr entries in ChkSlots::off / avail / cpos are the basis in
+// normalised order, then the check rows in the caller's order.
+struct ChkDesc {
+    uint32_t B;
+    uint32_t k;
+    uint32_t nr;      // check rows
+    uint32_t tab;     // dword offset of tables, layout [slot][row][5]
+    uint32_t slot0;   // first of the n entries in ChkSlots::off / avail / cpos
+    uint32_t flag0;   // ChkSlots::flags[flag0]: the chunk's first differing position (atomicMin);
+                      // flags[flag0 + 1 + r]: check row r, 0 once it differs (all 0xFFFFFFFF when clean)
+    uint32_t valid;   // positions [0, valid) where all n entries are readable: min(B, every avail)
+    uint32_t res;     // the chunk's index in the launch's results[]
+    uint32_t cslot0;  // the chunk's first entry in the launch's row_bad[] / column[]
+    uint32_t pad;
+};
+
+struct ChkSlots {
+    const uint64_t *off;    // block address: blocks + off[entry]
+    const uint32_t *avail;  // bytes of the block that exist in memory; the rest read as zero
+    const uint32_t *cpos;   // the entry's position among the chunk's n in the caller's order
+    const uint32_t *echunk; // the entry's chunk (descriptor index)
+    uint32_t *flags;        // see ChkDesc::flag0
+};
+
+// sec_chk_result's device mirror (include/storb_ec.h)
+struct ChkResult {
+    uint64_t first;
+    uint32_t nbad;
+    uint32_t pad;
+};
+
 // One chunk of a syndrome decode (kernels_bs.hip sec_syndrome_bs_kernel, sec_decode_bs_kernel; 56 B).  Block j of
 // the chunk (data j < k, parity row r at j = k + r) is at blocks + off[slot0 + j] with
 // avail[slot0 + j] readable bytes, when its bit in dmask / pmask is set.
@@ -227,4 +259,15 @@ int sec_launch_repair(int rows, int U, int wide, int lanes, const uint8_t *block
 int sec_launch_repair_tail(const uint8_t *blocks, uint8_t *out, const sec::RepDesc *descs,
                            const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::RepSlots slots,
                            void *stream);
+// Check (sec_check_kernel): tiles and arguments as repair's (rows 1..8 check rows of the tile's
+// group); nothing is stored unless a row differs, then only slots.flags words
+int sec_launch_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, const sec::ChkDesc *descs,
+                     const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs, sec::ChkSlots slots, void *stream,
+                     int kb = 0);
+int sec_launch_check_tail(const uint8_t *blocks, const sec::ChkDesc *descs, const sec::TailItem *items,
+                          uint32_t nitems, const uint32_t *tabs, sec::ChkSlots slots, void *stream);
+// One thread per entry of the launch's chunks: slots.flags into results[d.res], row_bad[d.cslot0 + ..]
+// and, for an inconsistent chunk, column[d.cslot0 + ..] (row_bad, column nullable)
+int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uint32_t nentries, sec::ChkSlots slots,
+                           sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, void *stream);
 }

@@ -1,7 +1,7 @@
 """Host-side engine over libstorbec.so: one HIP context per (device, thread).
 
 Two ways in (``repair_batch`` / ``repair_host``, lost blocks regenerated from any k survivors,
-come in both):
+and ``check_batch`` / ``check_host``, the held blocks checked against each other, come in both):
   * device-resident batches (``encode_batch`` / ``decode_batch``): descriptor arrays +
     device addresses (torch tensors, or any integer address) — the bench and the GPU parity
     tests use these;
@@ -24,8 +24,8 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (COPY_DTYPE, DEC_DTYPE, ENC_DTYPE, MSG_DTYPE, REP_DTYPE, SEC_F_ASYNC, SEC_F_GPU_PARITY_IDS,
-                   SEC_F_HOST, SEC_F_RECOVER, SEC_F_STAGED)
+from ._lib import (CHK_DTYPE, CHK_RESULT_DTYPE, COPY_DTYPE, DEC_DTYPE, ENC_DTYPE, MSG_DTYPE, REP_DTYPE, SEC_F_ASYNC,
+                   SEC_F_GPU_PARITY_IDS, SEC_F_HOST, SEC_F_RECOVER, SEC_F_STAGED)
 
 
 class Error(Exception):
@@ -78,7 +78,7 @@ def device_count() -> int:
     return n.value if rc == 0 else 0
 
 
-_TIMING_KINDS = {"encode": 0, "decode": 1, "sha1": 2, "bignum": 3, "repair": 4}
+_TIMING_KINDS = {"encode": 0, "decode": 1, "sha1": 2, "bignum": 3, "repair": 4, "check": 5}
 
 
 class Engine:
@@ -127,7 +127,7 @@ class Engine:
 
     def collect_timing(self, kind: str) -> tuple[float, int]:
         """(summed kernel ms, launch count) recorded since the last collect;
-        kind 'encode' | 'decode' | 'sha1' | 'bignum' | 'repair'."""
+        kind 'encode' | 'decode' | 'sha1' | 'bignum' | 'repair' | 'check'."""
         ms = ctypes.c_double(0)
         n = ctypes.c_int64(0)
         self._check(self.lib.sec_timing_collect(self._ctx, _TIMING_KINDS[kind], ctypes.byref(ms),
@@ -263,6 +263,71 @@ class Engine:
             digs.append([bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(len(row))])
             f += len(row)
         return out, digs
+
+    def check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks, results, *,
+                    block_avail: np.ndarray | None = None, row_bad=None, column=None, host: bool = False,
+                    asynchronous: bool = False) -> None:
+        """sec_check_batch: of each chunk's n held blocks (CHK_DTYPE descriptors; entries slot0 ..
+        slot0+k-1 the basis, the rest the check rows) every check row is predicted from the basis
+        and compared with the stored block.  results: one CHK_RESULT_DTYPE per chunk (first
+        differing position or CHK_CONSISTENT, differing rows); row_bad, column (optional): one
+        byte per slot entry; all three where the blocks live.  block_avail as decode_batch.
+        host: host buffers, always staged."""
+        descs = np.ascontiguousarray(descs, dtype=CHK_DTYPE)
+        sn = np.ascontiguousarray(sharenums, dtype=np.int32)
+        bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
+        av = None if block_avail is None else np.ascontiguousarray(block_avail, dtype=np.uint64)
+        if av is not None and av.size < bo.size:
+            raise ValueError("block_avail needs one entry per slot")
+        b, _kb = addr(blocks)
+        r, _kr = addr(results)
+        rb, _krb = addr(row_bad)
+        co, _kco = addr(column)
+        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
+        self._check(self.lib.sec_check_batch(self._ctx, _ptr(descs), len(descs), _ptr(sn) or None, _ptr(bo) or None,
+                                             None if av is None else _ptr(av), b or None, r or None, rb or None,
+                                             co or None, flags))
+
+    def check_host(self, items):
+        """Whether the held blocks of host chunks agree with each other, in one call.
+
+        items: [(k, m, blocks, sharenums)] with n >= k equal-length blocks per chunk, the first k
+        the basis, the others the check rows.  Returns, per chunk, ``(first, bad, column)``:
+        first = the lowest byte position at which a check row differs from its prediction (None:
+        the chunk is consistent), bad = the positions in `blocks` of the check rows that differ
+        anywhere, column = the n blocks' bytes at `first` (None when consistent), the input of
+        ``check_locate``."""
+        for it in items:
+            check_check_item(*it)
+        n = len(items)
+        if not n:
+            return []
+        descs = np.zeros(n, dtype=CHK_DTYPE)
+        nslots = sum(len(it[2]) for it in items)
+        sn = np.zeros(max(nslots, 1), dtype=np.int32)
+        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
+        keep = []
+        slot = 0
+        for j, (k, m, blocks, sharenums) in enumerate(items):
+            for q, b in enumerate(blocks):
+                a, kp = addr(b)
+                keep.append(kp)
+                bo[slot + q] = a
+                sn[slot + q] = int(sharenums[q])
+            descs[j] = (len(blocks[0]), slot, len(blocks), k, m, 0)
+            slot += len(blocks)
+        res = np.zeros(n, dtype=CHK_RESULT_DTYPE)
+        rb = np.zeros(max(nslots, 1), dtype=np.uint8)
+        col = np.zeros(max(nslots, 1), dtype=np.uint8)
+        self.check_batch(descs, sn, bo, 0, res, row_bad=rb, column=col, host=True)
+        out = []
+        for j in range(n):
+            s0, nb = int(descs[j]["slot0"]), int(descs[j]["n"])
+            if int(res[j]["first"]) == _lib.CHK_CONSISTENT:
+                out.append((None, [], None))
+            else:
+                out.append((int(res[j]["first"]), [q for q in range(nb) if rb[s0 + q]], col[s0:s0 + nb].tobytes()))
+        return out
 
     def encode_digest_batch(self, descs: np.ndarray, src, parity, digests, *, host: bool = False,
                             asynchronous: bool = False) -> None:
@@ -662,7 +727,43 @@ def check_repair_item(k: int, m: int, blocks, sharenums, targets) -> None:
         raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
 
 
+def check_check_item(k: int, m: int, blocks, sharenums) -> None:
+    """The check preconditions for one chunk (the library's own checks, raised before any GPU
+    work): n equal-length blocks and n sharenums, 1 <= k <= m <= 256, k <= n <= m, sharenums in
+    [0, m) and distinct.  Raises Error."""
+    if len(blocks) != len(sharenums):
+        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
+    B = len(blocks[0]) if blocks else 0
+    for b in blocks:
+        if len(b) != B:
+            raise Error(_lib.strerror(_lib.SEC_EBLOCKLEN))
+    if not (1 <= k <= m <= 256):
+        raise Error(_lib.strerror(_lib.SEC_EKM))
+    if not (k <= len(blocks) <= m):
+        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
+    sn = [int(x) for x in sharenums]
+    if any(x < 0 or x >= m for x in sn):
+        raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
+    if len(set(sn)) != len(sn):
+        raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
+
+
 # -- matrices (host arithmetic; no device needed) ------------------------------
+def check_locate(k: int, m: int, sharenums, column) -> int:
+    """Which single entry explains an inconsistent column (sec_check_locate): sharenums = the n
+    held block numbers, the first k the basis, column = their n bytes at one position (what a
+    check returns).  -1: the column is a code word; i: changing entry i alone makes it one; -2:
+    no single entry explains it (always so with fewer than two check rows)."""
+    lib = _lib.load()
+    sn = np.ascontiguousarray([int(x) for x in sharenums], dtype=np.int32)
+    col = np.frombuffer(bytes(column), dtype=np.uint8)
+    if col.size != sn.size:
+        raise ValueError("check_locate: one column byte per sharenum")
+    who = ctypes.c_int32(0)
+    check(lib.sec_check_locate(int(k), int(m), _ptr(sn) or None, sn.size, _ptr(col) or None, ctypes.byref(who)), lib)
+    return who.value
+
+
 def repair_matrix(k: int, m: int, sharenums, targets) -> bytes:
     """len(targets) x k bytes, row-major: block targets[r] = XOR_j row[r][j] * block
     sharenums[j] (sec_repair_matrix; columns in the order of `sharenums`)."""

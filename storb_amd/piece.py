@@ -23,6 +23,9 @@ Deliberate differences (documented in DESIGN.md §Boundary):
 * ``repair_chunks`` / ``repair_pieces`` (no reference counterpart) regenerate lost pieces, data
   or parity, from a chunk's surviving pieces, with their piece ids on request: what a validator
   needs to seed a failed miner's pieces elsewhere without reconstructing and re-encoding.
+* ``check_chunks`` / ``check_pieces`` (no reference counterpart) tell whether the pieces held of
+  a chunk agree with each other and, with two pieces beyond k, which one does not: the code's own
+  check, read once on the GPU, where the reference can only hash every piece.
 * ``reconstruct_data_stream`` decodes window w+1 on a worker thread (its own HIP context)
   while the caller consumes window w's chunks; ``encode_chunks_stream`` does the same for the
   upload loop's produce/consume pattern (validator.py:1338-1446, 1630-1638).
@@ -57,7 +60,8 @@ from pydantic import BaseModel, ConfigDict, Field
 
 from .constants import MAX_PIECE_SIZE, MIN_PIECE_SIZE, PIECE_LENGTH_OFFSET, PIECE_LENGTH_SCALING
 from .easyfec import Decoder, Encoder, Error
-from .engine import EngineGroup, check_decode_item, choose_blocks, device_count, get_engine, spread_threads
+from .engine import (EngineGroup, check_decode_item, check_locate, choose_blocks, device_count, get_engine,
+                     spread_threads)
 
 logger = logging.getLogger(__name__)
 
@@ -65,7 +69,7 @@ __all__ = [
     "PieceType", "Piece", "EncodedChunk", "ProcessedPieceInfo", "EncodedPieces", "piece_hash", "piece_length",
     "encode_chunk", "decode_chunk", "reconstruct_data", "reconstruct_data_stream", "encode_chunks",
     "decode_chunks", "chunk_shape", "piece_hashes", "encode_chunks_with_ids", "encode_chunks_stream", "Encoder",
-    "Decoder", "Error", "use_devices", "repair_chunks", "repair_pieces",
+    "Decoder", "Error", "use_devices", "repair_chunks", "repair_pieces", "ChunkCheck", "check_chunks", "check_pieces",
 ]
 
 PREFETCH_PIECE_IDS = True  # encode_chunk hashes its pieces on a thread pool (see module doc)
@@ -754,6 +758,91 @@ def repair_chunks(chunks: typing.Sequence[EncodedChunk], targets=None, *, piece_
 def repair_pieces(chunk: EncodedChunk, targets=None, *, piece_ids: bool = False) -> list[Piece]:
     """``repair_chunks`` for one chunk: its lost pieces (`targets`, default every absent one)."""
     return repair_chunks([chunk], None if targets is None else [targets], piece_ids=piece_ids)[0]
+
+
+class ChunkCheck(BaseModel):
+    """What ``check_chunks`` found for one chunk."""
+
+    chunk_idx: int
+    checked: int  # pieces checked (the distinct pieces held)
+    consistent: bool  # every held piece agrees with the others
+    first_bad_offset: typing.Optional[int] = None  # lowest byte offset at which a piece disagrees
+    bad_piece_idx: list[int] = Field(default_factory=list)  # the pieces named corrupt so far
+    located: bool = False  # bad_piece_idx is every corrupt piece: the rest was checked consistent
+
+
+def _check_item(ch: EncodedChunk, held: list[Piece]):
+    """(k, m, blocks, sharenums) of a check over `held` (ascending piece_idx, at least k): the
+    basis is the pick of ``choose_blocks`` (every held primary first, so with all primaries held
+    the check rows are plain encode rows), the other pieces are the check rows."""
+    basis = held[:ch.k]
+    if len(held) > ch.k:
+        pick = choose_blocks(ch.k, ch.m, [p.piece_idx for p in held])
+        if pick is not None:
+            basis = [held[j] for j in pick]
+    took = {p.piece_idx for p in basis}
+    use = basis + [p for p in held if p.piece_idx not in took]
+    return ch.k, ch.m, [p.data for p in use], [p.piece_idx for p in use]
+
+
+def check_chunks(chunks: typing.Sequence[EncodedChunk], *, locate: bool = True) -> list[ChunkCheck]:
+    """Whether each chunk's held pieces agree with each other, and which piece does not: GPU calls
+    that read every held piece once and hash nothing.
+
+    ``chunk.pieces`` holds at least k pieces.  k of them (``choose_blocks``' pick) predict every
+    other one, which is compared with what is held: any corruption confined to at most n - k of
+    the n held pieces is detected with certainty (a chunk with exactly k pieces has nothing to
+    compare and is reported consistent).  With ``locate`` an inconsistent chunk goes on: the bytes
+    of all pieces at the first bad offset name the one piece whose change explains them
+    (``check_locate``; needs two pieces beyond k), the chunk is checked again without that piece
+    (all such re-checks of a round in one call), and so on until the rest is consistent
+    (``located=True``: ``bad_piece_idx`` are the corrupt pieces, ready for
+    ``repair_pieces(rest, targets=bad_piece_idx)``) or no single piece explains what is left
+    (``located=False``, ``bad_piece_idx`` what was named so far).  No reference counterpart: the
+    reference's only integrity check is the SHA-1 piece id."""
+    out: list[ChunkCheck] = []
+    held: list[list[Piece]] = []
+    for ch in chunks:
+        if not (1 <= ch.k <= ch.m <= 256):
+            raise Error(f"Precondition violation: 1 <= k <= m <= 256 required (k={ch.k}, m={ch.m})")
+        have: dict[int, Piece] = {}
+        for p in ch.pieces or []:
+            have.setdefault(p.piece_idx, p)
+        use = sorted(have.values(), key=lambda p: p.piece_idx)
+        if len(use) < ch.k:
+            raise ValueError(f"Not enough pieces to check chunk {ch.chunk_idx}")
+        held.append(use)
+        out.append(ChunkCheck(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
+    todo = list(range(len(chunks)))  # chunks checked in the next call
+    first_round = True
+    while todo:
+        items = [_check_item(chunks[i], held[i]) for i in todo]
+        res = get_engine().check_host(items)
+        again = []
+        for i, it, (first, _bad, column) in zip(todo, items, res):
+            ck = out[i]
+            if first_round:
+                ck.consistent = first is None
+                ck.first_bad_offset = first
+            if first is None:
+                ck.located = not first_round
+                continue
+            if not locate:
+                continue
+            who = check_locate(it[0], it[1], it[3], column) if len(it[3]) - it[0] >= 2 else -2
+            if who < 0:  # no single piece explains the column: bad_piece_idx is what was named so far
+                continue
+            ck.bad_piece_idx.append(it[3][who])
+            held[i] = [p for p in held[i] if p.piece_idx != it[3][who]]
+            again.append(i)
+        todo = again
+        first_round = False
+    return out
+
+
+def check_pieces(chunk: EncodedChunk, *, locate: bool = True) -> ChunkCheck:
+    """``check_chunks`` for one chunk."""
+    return check_chunks([chunk], locate=locate)[0]
 
 
 def _windows(chunks, nbytes, size_of) -> Iterator[list]:

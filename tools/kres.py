@@ -4,7 +4,7 @@
 
     python tools/kres.py [-DKNOB=V ...] [--filter REGEX] [--mix] [--save-asm PATH]
 
-Prints per kernel: VGPRs, SGPRs, occupancy (waves/SIMD), static LDS, spills; with --mix the
+Prints per kernel: VGPRs, SGPRs, occupancy (waves/SIMD), static LDS, spills, scratch; with --mix the
 top VALU / LDS / scalar-memory instruction counts of each matching kernel's body.
 """
 
@@ -35,7 +35,7 @@ def demangle(n: str) -> str:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("defs", nargs="*")
-    ap.add_argument("--filter", default=r"encode_kernel|decode_kernel|repair_kernel")
+    ap.add_argument("--filter", default=r"encode_kernel|decode_kernel|repair_kernel|check_kernel")
     ap.add_argument("--mix", action="store_true")
     ap.add_argument("--save-asm", metavar="PATH", help="also keep the gfx950 assembly there")
     ap.add_argument("--src", default=SRC, help="kernel source (default storb_amd/csrc/kernels.hip)")
@@ -69,7 +69,8 @@ def main():
             continue
         print(f"{nm:40s} vgpr {r.get('VGPRs', '?'):>4s} sgpr {r.get('SGPRs', '?'):>4s} "
               f"occ {r.get('Occupancy [waves/SIMD]', '?'):>2s} lds {r.get('LDS Size [bytes/block]', '?'):>5s} "
-              f"vspill {r.get('VGPRs Spill', '?')} sspill {r.get('SGPRs Spill', '?')}")
+              f"vspill {r.get('VGPRs Spill', '?')} sspill {r.get('SGPRs Spill', '?')} "
+              f"scratch {r.get('ScratchSize [bytes/lane]', '?')}")
         if a.mix:
             i = asm.find(r["name"] + ":")
             j = asm.find(".Lfunc_end", i)
