@@ -135,7 +135,7 @@ int sec_sync(sec_ctx *ctx);
 int sec_ctx_set_timing(sec_ctx *ctx, int enable);
 /* Waits for recorded pairs, returns the summed milliseconds and launch count of
  * kind 0 = encode, 1 = decode, 2 = SHA-1, 3 = bignum (APDP), 4 = repair (its kernels and,
- * with digests, their SHA-1), 5 = check, and clears them. */
+ * with digests, their SHA-1), 5 = check, 6 = decode + check, and clears them. */
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches);
 
 /* ---- context options --------------------------------------------------------
@@ -314,6 +314,52 @@ int sec_check_batch(sec_ctx *ctx, const sec_chk_chunk *chunks, int64_t nchunks,
                     const int32_t *sharenums, const uint64_t *block_offs,
                     const uint64_t *block_avail, const uint8_t *blocks, sec_chk_result *results,
                     uint8_t *row_bad, uint8_t *column, unsigned flags);
+
+/* ---- decode + check: reassemble from k held pieces and check the spare ones in one pass -------
+ * A caller holding n > k blocks of a chunk (storb's validator fetches all m) gets the chunk's
+ * bytes and the code word's verdict from one read of the n blocks: n*B bytes read and k*B written,
+ * where sec_check_batch followed by sec_decode_batch_ex reads the k chosen blocks twice.  The
+ * contract is the COMPOSITION of those two calls on the same arrays:
+ *   - `out` receives exactly what sec_decode_batch_ex writes for entries slot0 .. slot0+k-1
+ *     (present primaries copied, missing ones recovered; k*B - padlen bytes at out + out_off and
+ *     nothing past them); with SEC_F_RECOVER only the e recovered rows, as that flag specifies.
+ *     `out` is written whether or not the chunk turns out consistent.
+ *   - results, row_bad (nullable) and column (nullable) receive exactly what sec_check_batch
+ *     reports for entries slot0 .. slot0+n-1: the first k are the basis, the rest the check rows.
+ * The first k entries may be any k distinct blocks in any order.  block_avail (nullable) has the
+ * meaning both calls give it, for basis entries and check rows alike.  A chunk with n == k is a
+ * plain decode and is reported consistent.  `blocks` may be NULL (absolute block_offs).  Nothing is
+ * ever written to the blocks; every call starts from clean state.  The call always takes the
+ * direct (v_perm) kernels, never the syndrome path; sec_ctx_decode_paths and
+ * sec_ctx_decode_methods do not count it, and sec_ctx_host_paths counts a SEC_F_HOST call as staged
+ * (as sec_check_batch's).
+ * Aliasing: sec_decode_batch's rule (no output range may overlap any block of the call).
+ * Flags: none or SEC_F_ASYNC (device pointers); SEC_F_RECOVER in either mode; SEC_F_HOST (host
+ * pointers) is ALWAYS staged through pinned slabs as sec_check_batch's: n*B bytes per chunk are
+ * gathered ONCE, and the output (with SEC_F_RECOVER only the recovered rows) and the results are
+ * scattered back.  SEC_F_HOST with SEC_F_ASYNC is SEC_EINVAL; any other flag is SEC_EINVAL.
+ * Errors, all before any device work, in this order: SEC_EINVAL a NULL array, NULL results, NULL
+ * `out` where a chunk has bytes to write, or n < 0; SEC_EKM; SEC_ENBLOCKS n < k or n > m;
+ * SEC_ESHARENUM; SEC_EDUPSHARE any repeat among the n sharenums; SEC_EPADLEN padlen > k*B;
+ * SEC_ESIZE B >= 2^31.
+ * sec_timing_collect kind 6 times this call's kernels. */
+typedef struct sec_dchk_chunk {
+    uint64_t out_off; /* as sec_dec_chunk                                                */
+    uint64_t B;
+    uint64_t padlen;
+    uint64_t slot0;   /* first of the chunk's n entries in sharenums[] / block_offs[] /
+                         block_avail[]                                                   */
+    int32_t n;        /* blocks held, k <= n <= m                                        */
+    int32_t k;
+    int32_t m;
+    int32_t pad;
+} sec_dchk_chunk; /* 48 bytes */
+
+int sec_decode_check_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t nchunks,
+                           const int32_t *sharenums, const uint64_t *block_offs,
+                           const uint64_t *block_avail, const uint8_t *blocks, uint8_t *out,
+                           sec_chk_result *results, uint8_t *row_bad, uint8_t *column,
+                           unsigned flags);
 
 /* Which single entry explains an inconsistent column (host arithmetic, no device needed).
  * sharenums: the n block numbers, the first k the basis; column: the n bytes sec_check_batch

@@ -296,6 +296,8 @@ struct SubPlan {
     size_t off_cpos = 0, off_echunk = 0;   // check: the entries' caller positions and chunks (ChkSlots)
     uint32_t nentries = 0;                 // check: entries of the unit's chunks
     uint64_t chk_rows = 0, chk_col = 0;    // check, host mode: row_bad and column in the slab output
+    size_t off_cdesc = 0;                  // decode + check: the chunks' ChkDesc (sec_check_final)
+    uint64_t dchk_out = 0;                 // decode + check, host mode: the decoded bytes in the slab output
     // repair digests: runs of consecutive digest slots, (first message, count, first slot)
     std::vector<std::array<uint64_t, 3>> sha_runs;
     // syndrome decodes (decode): phase 1 launches (bit-sliced syndromes) and phase 2 launches
@@ -677,14 +679,15 @@ struct sec_ctx {
     hipStream_t own = nullptr;
     hipStream_t ext = nullptr;
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[6];  // by timing kind
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[7];  // by timing kind
     std::vector<hipEvent_t> ev_pool;
     hipEvent_t stop_ev = nullptr;  // between timing_begin and timing_end of an attached launch
     PinBuf pin{nullptr, 0, false};  // metadata image staging (its own, not pooled: small, every call)
     hipEvent_t pin_ev = nullptr, meta_ev = nullptr;
-    TableCache enc_tabs, dec_tabs, rep_tabs, chk_tabs;
-    Plan enc_plan, dec_plan, sha_plan, bn_plan, rep_plan, chk_plan;
+    TableCache enc_tabs, dec_tabs, rep_tabs, chk_tabs, dchk_tabs;
+    Plan enc_plan, dec_plan, sha_plan, bn_plan, rep_plan, chk_plan, dchk_plan;
     DevBuf chk_flags;   // check: the flag words of the call in flight (ChkDesc::flag0)
+    DevBuf dchk_flags;  // decode + check: likewise
     DevBuf bn_scratch;  // host-mode staging of sec_bn_modexp / mulmod operands
     DevBuf bn_part;     // partial residues of segmented reductions (one region per slot)
     DevBuf syn;         // syndrome rows of device-mode syndrome decodes
@@ -1886,6 +1889,204 @@ int launch_check_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const ui
     return SEC_OK;
 }
 
+// ---- decode + check plan --------------------------------------------------------
+// The check plan with the decode's rows in front (a sibling of build_check_plan): per chunk one
+// table of the repair matrix over its basis, layout [slot][row][5], rows = its e missing primaries
+// in ascending order, then its check rows in the caller's order (cached by basis and check rows:
+// the basis fixes the missing primaries); its n entries as a check's (the basis in normalised
+// order, then the check rows), with the decode's per-slot output rows beside them; tiles as a
+// decode's (add_work) over all e + nr rows and valid = min(the last output row's length unless
+// recover-only, the least avail of all n); flag words as a check's, in ctx->dchk_flags.  Both a
+// DChkDesc (the tile kernels) and a ChkDesc (sec_check_final) per chunk.  Host mode stages all n
+// entries densely once and returns results, row_bad, column and the decoded bytes through the slab
+// output.
+int build_decode_check_plan(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                            const uint64_t *block_offs, const uint64_t *block_avail, const SlotLayout &L, bool host,
+                            bool recover)
+{
+    Plan &plan = ctx->dchk_plan;
+    TableCache &tc = ctx->dchk_tabs;
+    std::vector<PendingExpand> pending;
+    std::vector<uint32_t> tab_of, e_of((size_t)nchunks, 0);
+    auto want = [&](int64_t i, std::string &key) -> size_t {
+        const sec_dchk_chunk &c = chunks[i];
+        const int *idx = &L.idx[L.first[i]];
+        int e = 0;
+        for (int s = 0; s < c.k; ++s)
+            e += idx[s] >= c.k;
+        e_of[i] = (uint32_t)e;
+        const int rows = e + c.n - c.k;
+        if (!rows)
+            return 0;
+        key = slots_key(c.k, c.m, idx) + "|";
+        for (int r = c.k; r < c.n; ++r)
+            key += std::to_string(sharenums[c.slot0 + r]) + ",";
+        return (size_t)c.k * rows;
+    };
+    auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
+        const sec_dchk_chunk &c = chunks[i];
+        const int k = c.k;
+        const int *idx = &L.idx[L.first[i]];
+        std::vector<int> targets;
+        for (int s = 0; s < k; ++s)  // normalised slot s holds primary s, or stands in for it
+            if (idx[s] >= k)
+                targets.push_back(s);
+        targets.insert(targets.end(), sharenums + c.slot0 + k, sharenums + c.slot0 + c.n);
+        const int rows = (int)targets.size();
+        std::vector<uint8_t> rm;
+        if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k), targets, rm))
+            return (int)SEC_ESINGULAR;
+        cf.resize((size_t)k * rows);
+        for (int s = 0; s < k; ++s)
+            for (int r = 0; r < rows; ++r)
+                cf[(size_t)s * rows + r] = rm[(size_t)r * k + s];
+        return (int)SEC_OK;
+    };
+    RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
+
+    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return (uint64_t)chunks[i].n * chunks[i].B; },
+                                    (size_t)ctx->opt[O_SLAB_BYTES]);
+    Image img;
+    plan.subs.clear();
+    plan.nflags = 0;
+    for (auto [c0, c1] : ranges) {
+        SubPlan sp;
+        sp.c0 = c0;
+        sp.c1 = c1;
+        std::vector<sec::DChkDesc> descs((size_t)(c1 - c0));
+        std::vector<sec::ChkDesc> cdescs((size_t)(c1 - c0));
+        std::vector<uint64_t> soff;
+        std::vector<uint32_t> savail, cpos, echunk, srow, mrow;
+        Bins bins;
+        std::vector<sec::TailItem> tail;
+        // host mode's slab output: the results, row_bad and column (one byte per entry each), then
+        // the decoded bytes of every chunk
+        uint64_t nent = 0;
+        for (int64_t i = c0; i < c1; ++i)
+            nent += (uint64_t)chunks[i].n;
+        sp.chk_rows = (uint64_t)(c1 - c0) * sizeof(sec::ChkResult);
+        sp.chk_col = sp.chk_rows + nent;
+        sp.dchk_out = align_up(sp.chk_col + nent, 256);
+        sp.out_bytes = sp.dchk_out;
+        for (int64_t i = c0; i < c1; ++i) {
+            const sec_dchk_chunk &c = chunks[i];
+            const uint64_t base = L.first[i];
+            const int *idx = &L.idx[base];
+            const uint32_t slot0 = (uint32_t)soff.size();
+            std::vector<uint32_t> mr;
+            uint64_t min_avail = c.B;
+            for (int e = 0; e < c.n; ++e) {
+                const int from = e < c.k ? L.perm[base + e] : e;
+                soff.push_back(host ? sp.in_bytes + (uint64_t)e * c.B : block_offs[c.slot0 + from]);
+                const uint64_t av = host ? c.B : slot_avail(c, block_avail, from);  // staged entries are zero-filled
+                savail.push_back((uint32_t)av);
+                cpos.push_back((uint32_t)from);
+                echunk.push_back((uint32_t)(i - c0));
+                min_avail = std::min(min_avail, av);
+                // recover-only: no copies, and recovered row r goes to output row r
+                srow.push_back(e < c.k && !recover && idx[e] < c.k ? (uint32_t)idx[e] : 0xFFFFFFFFu);
+                if (e < c.k && idx[e] >= c.k)
+                    mr.push_back(recover ? (uint32_t)mr.size() : (uint32_t)e);
+            }
+            mr.resize((size_t)c.n, 0);
+            mrow.insert(mrow.end(), mr.begin(), mr.end());
+            const uint32_t e = e_of[i], nr = (uint32_t)(c.n - c.k);
+            const uint64_t nout = recover ? (uint64_t)e * c.B : (uint64_t)c.k * c.B - c.padlen;
+            const int64_t valid = std::max<int64_t>(
+                0, std::min<int64_t>(recover ? (int64_t)c.B : (int64_t)nout - (int64_t)(c.k - 1) * (int64_t)c.B,
+                                     (int64_t)min_avail));
+            sec::DChkDesc &d = descs[i - c0];
+            d.out_off = host ? sp.out_bytes : c.out_off;
+            d.n = nout;
+            d.B = (uint32_t)c.B;
+            d.k = (uint32_t)c.k;
+            d.e = e;
+            d.nr = nr;
+            d.tab = tab_of[i];
+            d.slot0 = slot0;
+            d.flag0 = (uint32_t)plan.nflags;
+            d.valid = (uint32_t)valid;
+            sec::ChkDesc &cd = cdescs[i - c0];
+            cd.B = d.B;
+            cd.k = d.k;
+            cd.nr = nr;
+            cd.tab = d.tab;
+            cd.slot0 = slot0;
+            cd.flag0 = d.flag0;
+            cd.valid = d.valid;
+            cd.res = (uint32_t)(host ? i - c0 : i);
+            cd.cslot0 = (uint32_t)(host ? slot0 : c.slot0);
+            cd.pad = 0;
+            plan.nflags += 1 + nr;
+            sp.in_bytes += (uint64_t)c.n * c.B;
+            sp.out_bytes += nout;
+            // (a chunk with no row and nothing to copy has no work: n == k, no primary lost, and
+            // recover-only or every byte cut by padlen)
+            if (e + nr > 0 || (!recover && nout > 0))
+                add_work(bins, tail, (uint32_t)(i - c0), c.B, valid, (int)(e + nr), c.k, true, false,
+                         dec_small_kb(c.k));
+        }
+        std::vector<sec::Tile> tiles;
+        flatten(bins, sp.groups, tiles, true);
+        sp.ntail = (uint32_t)tail.size();
+        sp.off_desc = img.put(descs.data(), descs.size() * sizeof(sec::DChkDesc));
+        sp.off_cdesc = img.put(cdescs.data(), cdescs.size() * sizeof(sec::ChkDesc));
+        sp.off_tiles = img.put(tiles.data(), tiles.size() * sizeof(sec::Tile));
+        sp.off_tail = img.put(tail.data(), tail.size() * sizeof(sec::TailItem));
+        sp.off_savail = img.put(savail.data(), savail.size() * 4);
+        sp.off_cpos = img.put(cpos.data(), cpos.size() * 4);
+        sp.off_echunk = img.put(echunk.data(), echunk.size() * 4);
+        sp.off_srow = img.put(srow.data(), srow.size() * 4);
+        sp.off_mrow = img.put(mrow.data(), mrow.size() * 4);
+        sp.nentries = (uint32_t)echunk.size();
+        soff.resize(soff.size() + sec::kBatchVecs, 0);  // the kernel loads a batch's offsets unconditionally
+        sp.off_soff = img.put(soff.data(), soff.size() * 8);
+        plan.subs.push_back(std::move(sp));
+    }
+    if (plan.nflags >= UINT32_MAX)
+        return SEC_EINVAL;
+    RC(upload_plan(ctx, plan, img, tc, pending));
+    plan.gen = tc.gen;
+    return SEC_OK;
+}
+
+// The decode + check kernels of one launch unit, then its results (timing kind 6)
+int launch_decode_check_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const uint8_t *blocks, uint8_t *out,
+                            sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, hipStream_t s)
+{
+    const sec::DChkDesc *dd = plan.meta.as<sec::DChkDesc>(sp.off_desc);
+    const sec::ChkDesc *cd = plan.meta.as<sec::ChkDesc>(sp.off_cdesc);
+    const sec::Tile *dt = plan.meta.as<sec::Tile>(sp.off_tiles);
+    const uint32_t *tabs = ctx->dchk_tabs.buf.as<uint32_t>();
+    uint32_t *flags = ctx->dchk_flags.as<uint32_t>();
+    const sec::DChkSlots sl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
+                            plan.meta.as<uint32_t>(sp.off_srow), plan.meta.as<uint32_t>(sp.off_mrow), flags};
+    const sec::ChkSlots csl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
+                            plan.meta.as<uint32_t>(sp.off_cpos), plan.meta.as<uint32_t>(sp.off_echunk), flags};
+    const bool work = !sp.groups.empty() || sp.ntail;
+    hipEvent_t t0 = nullptr;
+    if (work)
+        RC(timing_begin(ctx, &t0, s));
+    for (const Group &g : sp.groups) {
+        int e = sec_launch_decode_check(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl,
+                                        s, g.mfma);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_decode_check_kernel");
+    }
+    if (sp.ntail) {
+        int e = sec_launch_decode_check_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs,
+                                             sl, s);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_decode_check_tail");
+    }
+    int e = sec_launch_check_final(blocks, cd, sp.nentries, csl, results, row_bad, column, s);
+    if (e)
+        return hip_fail((hipError_t)e, "sec_check_final");
+    if (work)
+        RC(timing_end(ctx, t0, 6, s));
+    return SEC_OK;
+}
+
 // ---- pinned caller memory: the zero-copy host path ----------------------------
 // A SEC_F_HOST encode / decode whose caller buffers all lie in page-locked host memory the
 // HIP runtime maps at the same address on the device (hipHostMalloc / sec_host_alloc,
@@ -2256,6 +2457,7 @@ void sec_ctx_destroy(sec_ctx *ctx)
     ctx->dec_tabs.buf.release();
     ctx->rep_tabs.buf.release();
     ctx->chk_tabs.buf.release();
+    ctx->dchk_tabs.buf.release();
     ctx->enc_plan.meta.release();
     ctx->dec_plan.meta.release();
     ctx->sha_plan.meta.release();
@@ -2263,6 +2465,8 @@ void sec_ctx_destroy(sec_ctx *ctx)
     ctx->rep_plan.meta.release();
     ctx->chk_plan.meta.release();
     ctx->chk_flags.release();
+    ctx->dchk_plan.meta.release();
+    ctx->dchk_flags.release();
     ctx->bn_scratch.release();
     ctx->bn_part.release();
     ctx->syn.release();
@@ -2312,7 +2516,8 @@ int sec_ctx_set_option(sec_ctx *ctx, const char *name, int64_t value)
     RC(set_dev(ctx));
     RC(drain_all(ctx));  // nothing in flight may still use a plan or pool built the old way
     ctx->opt.v[i] = value;
-    for (Plan *p : {&ctx->enc_plan, &ctx->dec_plan, &ctx->sha_plan, &ctx->bn_plan, &ctx->rep_plan, &ctx->chk_plan})
+    for (Plan *p : {&ctx->enc_plan, &ctx->dec_plan, &ctx->sha_plan, &ctx->bn_plan, &ctx->rep_plan, &ctx->chk_plan,
+                    &ctx->dchk_plan})
         p->valid = false;
     if (i == O_COPY_THREADS) {
         ctx->tasks.reset();
@@ -2337,7 +2542,7 @@ const char *sec_option_name(int index)
 
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches)
 {
-    if (!ctx || kind < 0 || kind > 5 || !total_ms || !launches)
+    if (!ctx || kind < 0 || kind > 6 || !total_ms || !launches)
         return SEC_EINVAL;
     RC(set_dev(ctx));
     double tot = 0;
@@ -3765,6 +3970,150 @@ int sec_check_batch(sec_ctx *ctx, const sec_chk_chunk *chunks, int64_t nchunks, 
     auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
         return launch_check_sub(ctx, plan, sp, din, (sec::ChkResult *)dout, row_bad ? dout + sp.chk_rows : nullptr,
                                 column ? dout + sp.chk_col : nullptr, s);
+    };
+    RC(run_pipeline(ctx, plan, gather, scatter, launch));
+    if (column)
+        for (int64_t i = 0; i < nchunks; ++i)
+            if (results[i].first != UINT64_MAX)
+                memcpy(column + chunks[i].slot0, col.data() + chunks[i].slot0, (size_t)chunks[i].n);
+    return SEC_OK;
+}
+
+// ---- decode + check: reassemble and check the spare pieces in one pass ---------------------
+int sec_decode_check_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                           const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
+                           uint8_t *out, sec_chk_result *results, uint8_t *row_bad, uint8_t *column, unsigned flags)
+{
+    static_assert(sizeof(sec_dchk_chunk) == 48 && sizeof(sec::DChkDesc) == 48, "ABI layout");
+    if (!ctx || nchunks < 0 || (nchunks > 0 && (!chunks || !sharenums || !block_offs || !results)) ||
+        (flags & ~(SEC_F_HOST | SEC_F_ASYNC | SEC_F_RECOVER)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
+        return SEC_EINVAL;
+    if (nchunks == 0)
+        return SEC_OK;
+    if (nchunks >= (int64_t)UINT32_MAX)
+        return SEC_EINVAL;
+    const bool host = flags & SEC_F_HOST;
+    const bool recover = flags & SEC_F_RECOVER;
+    RC(set_dev(ctx));
+
+    // preconditions of every chunk before any device work; SEC_EINVAL's first: n < 0, and a NULL
+    // `out` where a chunk has bytes to write (judged only where the chunk's k sharenums can be read)
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const sec_dchk_chunk &c = chunks[i];
+        if (c.n < 0)
+            return SEC_EINVAL;
+        if (out || c.k < 1 || c.k > 256 || c.n < c.k || c.B == 0)
+            continue;
+        if (!recover && (uint64_t)c.k * c.B > c.padlen)
+            return SEC_EINVAL;
+        for (int j = 0; recover && j < c.k; ++j)
+            if (sharenums[c.slot0 + j] < 0 || sharenums[c.slot0 + j] >= c.k)
+                return SEC_EINVAL;  // a basis entry that is no primary: a primary is recovered
+    }
+    uint64_t total_slots = 0;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const sec_dchk_chunk &c = chunks[i];
+        RC(check_check(c.k, c.m, sharenums + c.slot0, c.n));
+        if (c.padlen > (uint64_t)c.k * c.B)
+            return SEC_EPADLEN;
+        if (c.B >= (1ull << 31))
+            return SEC_ESIZE;
+        total_slots = std::max<uint64_t>(total_slots, c.slot0 + (uint64_t)c.n);
+    }
+    if (total_slots >= UINT32_MAX)
+        return SEC_EINVAL;
+    // (blocks may be NULL: block_offs are then absolute addresses)
+
+    // Plan key, as sec_check_batch's with the decode's fields: host mode keys on shapes, padlen and
+    // sharenums only; device mode on every descriptor, sharenum, address and avail.
+    Plan &plan = ctx->dchk_plan;
+    PlanKey key;
+    if (host) {
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const sec_dchk_chunk &c = chunks[i];
+            key.put(c.B);
+            key.put(c.padlen);
+            key.put(c.n);
+            key.put(c.k);
+            key.put(c.m);
+            key.put(sharenums + c.slot0, (size_t)c.n * 4);
+        }
+    } else {
+        key.put(chunks, sizeof(sec_dchk_chunk) * (size_t)nchunks);
+        key.put(sharenums, total_slots * 4);
+        key.put(block_offs, total_slots * 8);
+        if (block_avail)
+            key.put(block_avail, total_slots * 8);
+    }
+    key.put((flags & (SEC_F_HOST | SEC_F_RECOVER)) | (!host && block_avail ? 0x10000u : 0u));
+    const bool reuse = plan_reusable(plan, ctx->dchk_tabs, key);
+    SlotLayout L;
+    if (!reuse || host)
+        L = slot_layout(chunks, nchunks, sharenums);
+    if (!reuse) {
+        plan.valid = false;
+        RC(build_decode_check_plan(ctx, chunks, nchunks, sharenums, block_offs, block_avail, L, host, recover));
+        plan.key.swap(key.bytes);
+        plan.valid = true;
+    }
+    // every call starts from clean flag words, whatever the last call on this plan found
+    RC(ctx->dchk_flags.ensure((size_t)plan.nflags * 4));
+    CK(hipMemsetAsync(ctx->dchk_flags.p, 0xFF, (size_t)plan.nflags * 4, ctx->stream()));
+
+    if (!host) {
+        RC(launch_decode_check_sub(ctx, plan, plan.subs[0], blocks, out, (sec::ChkResult *)results, row_bad, column,
+                                   ctx->stream()));
+        if (!(flags & SEC_F_ASYNC))
+            CK(hipStreamSynchronize(ctx->stream()));
+        return SEC_OK;
+    }
+    // Host mode is always staged, as sec_check_batch's: all n entries of a chunk are gathered into
+    // pinned slabs ONCE and feed both the decode and the check; the decoded bytes (recover-only:
+    // the recovered rows) and the results come back.  column passes through a buffer of its own so
+    // that a consistent chunk's bytes stay untouched.
+    ++ctx->staged_calls;
+    std::vector<uint8_t> col(column ? (size_t)total_slots : 0);
+    auto nout = [&](const sec_dchk_chunk &c) -> uint64_t {
+        if (!recover)
+            return (uint64_t)c.k * c.B - c.padlen;
+        uint64_t e = 0;
+        for (int j = 0; j < c.k; ++j)
+            e += sharenums[c.slot0 + j] >= c.k;
+        return e * c.B;
+    };
+    auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        uint64_t o = 0;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const sec_dchk_chunk &c = chunks[i];
+            for (int e = 0; e < c.n; ++e) {
+                const int from = e < c.k ? L.perm[L.first[i] + e] : e;
+                const uint64_t av = slot_avail(c, block_avail, from);
+                jobs.push_back(sec::CopyJob{stage + o, (const void *)((uintptr_t)blocks + block_offs[c.slot0 + from]), av});
+                if (av < c.B)  // the entry's bytes past its avail are zero
+                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
+                o += c.B;
+            }
+        }
+    };
+    auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        jobs.push_back(sec::CopyJob{results + sp.c0, stage, (uint64_t)(sp.c1 - sp.c0) * sizeof(sec_chk_result)});
+        uint64_t o = 0, b = sp.dchk_out;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const sec_dchk_chunk &c = chunks[i];
+            if (row_bad)
+                jobs.push_back(sec::CopyJob{row_bad + c.slot0, stage + sp.chk_rows + o, (uint64_t)c.n});
+            if (column)
+                jobs.push_back(sec::CopyJob{col.data() + c.slot0, stage + sp.chk_col + o, (uint64_t)c.n});
+            o += (uint64_t)c.n;
+            const uint64_t nb = nout(c);
+            if (nb)
+                jobs.push_back(sec::CopyJob{(void *)((uintptr_t)out + c.out_off), stage + b, nb});
+            b += nb;
+        }
+    };
+    auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
+        return launch_decode_check_sub(ctx, plan, sp, din, dout, (sec::ChkResult *)dout,
+                                       row_bad ? dout + sp.chk_rows : nullptr, column ? dout + sp.chk_col : nullptr, s);
     };
     RC(run_pipeline(ctx, plan, gather, scatter, launch));
     if (column)

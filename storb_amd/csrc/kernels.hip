@@ -1151,6 +1151,266 @@ __global__ __launch_bounds__(256) void sec_check_final(const u8 *__restrict__ bl
     }
 }
 
+// ---- decode + check: reassemble from k held pieces and check the spare ones in one pass ----------
+// A chunk's rows are one table over its k basis slots (the repair matrix, layout [slot][row][5]):
+// rows 0 .. e-1 its missing primaries in ascending order, rows e .. e+nr-1 its check rows.  A tile
+// (chunk, t0, r0) takes rows r0 .. r0+R-1 of them.  Those below `split` = e - r0 (clamped to
+// [0, R], uniform over the workgroup) are STORE rows: zero-started accumulators stored to output
+// row miss[...], as decode_main's.  The rest are COMPARE rows: the stored block is XORed in after
+// the last slot, into registers the slots have left (check_main's kRowsLast form, for every R: a
+// store row and a compare row then cost the same registers), and the OR epilogue and the report are
+// check_main's, so a clean chunk's compare rows store nothing.  The row group r0 == 0 also copies
+// the present primaries (row[] = 0xFFFFFFFF for every slot of a recover-only call).  Each unrolled
+// r tests r < split, so the accumulators keep static register indices.
+// Positions < valid = min(the last output row's length unless recover-only, every entry's avail)
+// are the tiles'; [valid, B) goes byte by byte on the chunk's last tile of each row group
+// (decode_ragged and check_ragged in one loop), an entry's bytes past its avail reading as zero.
+// A sibling of decode_main and check_main, not a shared body.
+__device__ __forceinline__ void dchk_report(const sec::DChkDesc &d, const sec::DChkSlots sl, u32 crow, u32 at)
+{
+    atomicMin(sl.flags + d.flag0, at);
+    sl.flags[d.flag0 + 1 + crow] = 0u;
+}
+
+template <int R, int U, bool W, int KBX>
+__device__ __forceinline__ void dchk_main(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                          const sec::DChkDesc &d, const sec::Tile &tl, u32 t,
+                                          const u32 *__restrict__ tabs, const sec::DChkSlots sl)
+{
+    const u32 B = d.B, k = d.k;
+    u32 pos[U];
+    tile_pos(pos, t, d.valid);
+    u8 *dst = out + d.out_off;
+    const bool copies = tl.r0 == 0;  // row group 0 also copies the present primaries
+    const u32 *tj = tabs + d.tab + tl.r0 * sec::kTabDwords;
+    const u32 tstep = (d.e + d.nr) * sec::kTabDwords;
+    const int split = d.e > tl.r0 ? (int)min(d.e - tl.r0, (u32)R) : 0;  // rows below it are stored
+
+    u32x4 acc[R > 0 ? R : 1][U];
+#pragma unroll
+    for (int r = 0; r < (R > 0 ? R : 1); ++r)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            acc[r][u] = u32x4{0u, 0u, 0u, 0u};
+
+    // slots in batches of KB: every load of a batch, its arithmetic, then the copies (decode_main)
+    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
+    auto batch = [&](u32 c0) {
+        constexpr bool LT = lds_tab<R, true>();
+        const u32x2 *vt = wave_tabs<KB, R, LT>(tj, tstep, c0, k);
+        u64 so[KB];  // (the plan pads sl.off by kBatchVecs entries)
+        const u64 *sop = sl.off + d.slot0 + c0;
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+            so[c] = sop[c];
+        u32x4 xs[KB][U];
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+            if (c0 + c < k) {
+                const u8 *s = blocks + so[c];
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    xs[c][u] = load16(s + pos[u]);
+            }
+        if constexpr (R > 0 && kPairRows<R, W>()) {
+#pragma unroll
+            for (int c = 0; c < KB; c += 2) {
+                if (c + 1 < KB && c0 + c + 1 < k)
+                    gf_mac2<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R, xs[c + 1],
+                                      tj + (c0 + c + 1) * tstep, vt + (c + 1) * R);
+                else if (c0 + c < k)
+                    gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
+            }
+        } else if constexpr (R > 0) {
+#pragma unroll
+            for (int c = 0; c < KB; ++c)
+                if (c0 + c < k)
+                    gf_mac<R, U, LT>(acc, xs[c], tj + (c0 + c) * tstep, vt + c * R);
+        }
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+            if (c0 + c < k) {
+                const u32 orow = sl.row[d.slot0 + c0 + c];
+                if (copies && orow != 0xFFFFFFFFu) {
+                    u8 *o = dst + (u64)orow * B;
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        store16<SEC_DEC_ST>(o + pos[u], xs[c][u]);
+                }
+            }
+    };
+    if constexpr (W) {  // wide k: several batches (see encode_main)
+#pragma unroll 1
+        for (u32 c0 = 0; c0 < k; c0 += KB)
+            batch(c0);
+    } else {
+        batch(0);  // the plan guarantees k <= KB here
+    }
+    if constexpr (R > 0) {
+        // compare row r of the tile is check row r0 + r - e: entry k + that, flag word 1 + that
+        const int crow0 = (int)tl.r0 - (int)d.e;
+        const u64 *ro = sl.off + d.slot0 + k;
+        // the stored rows into registers the slots have left: the empty asm makes the lane's position
+        // wait for an accumulator as it stands here, so the loads cannot be hoisted above the
+        // arithmetic, where they would spill (check_main)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            asm volatile("" : "+v"(pos[u]) : "v"(acc[R - 1][u][3]));
+        // Nothing but memory effects leaves a branch on `split`: accumulators or stored rows defined
+        // on one side of such a branch only (a load per compare row under its own test) became
+        // whole-array copies at every join and spilled hundreds of VGPRs.  So the R loads are
+        // unconditional wherever the tile has a compare row at all: store row r loads the tile's
+        // first compare row again (the same 16 bytes of the same lane, issued back to back), and its
+        // mask drops it from the OR.
+        const bool compares = split < R;
+        u32x4 st[R][U];
+        if (compares) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const u8 *s = blocks + ro[crow0 + max(r, split)];
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    st[r][u] = load16(s + pos[u]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (r < split) {
+                u8 *o = dst + (u64)sl.miss[d.slot0 + tl.r0 + r] * B;
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    store16<SEC_DEC_ST>(o + pos[u], acc[r][u]);
+            }
+        if (!compares)
+            return;
+        u32 any = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const u32 cmp = r >= split ? ~0u : 0u;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    acc[r][u][w] = (acc[r][u][w] ^ st[r][u][w]) & cmp;
+                    any |= acc[r][u][w];
+                }
+            }
+        }
+        if (any == 0)
+            return;
+        u32 *first = sl.flags + d.flag0;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const u64 lo = acc[r][u][0] | (u64)acc[r][u][1] << 32, hi = acc[r][u][2] | (u64)acc[r][u][3] << 32;
+                if (lo | hi) {  // (a store row's are zero)
+                    atomicMin(first, pos[u] + (lo ? (u32)__builtin_ctzll(lo) >> 3 : 8u + ((u32)__builtin_ctzll(hi) >> 3)));
+                    first[1 + crow0 + r] = 0u;
+                }
+            }
+    }
+}
+
+// The chunk's ragged end [valid, B), byte by byte, for this tile's R rows: the compare rows' stored
+// bytes first, then every slot's byte loaded once, kBatch slots at a time, feeding the copy (row
+// group 0) and all R rows; stores only where the output row still has bytes.
+template <int R>
+__device__ __forceinline__ void dchk_ragged(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                            const sec::DChkDesc &d, const sec::Tile &tl,
+                                            const u32 *__restrict__ tabs, const sec::DChkSlots sl)
+{
+    const int split = d.e > tl.r0 ? (int)min(d.e - tl.r0, (u32)R) : 0;
+    const int crow0 = (int)tl.r0 - (int)d.e;
+    const u32 ent0 = d.slot0 + d.k;  // the chunk's first check row entry
+    const u32 nrows = d.e + d.nr;
+    for (u32 i = ragged_lane0(d.valid, tl.t0); i < tl.ntail; i += blockDim.x) {
+        const u32 tp = d.valid + i;
+        u8 *dst = out + d.out_off + tp;
+        u32 acc[R > 0 ? R : 1];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            acc[r] = (r >= split && tp < sl.avail[ent0 + crow0 + r]) ? (u32)blocks[sl.off[ent0 + crow0 + r] + tp] : 0u;
+        for (u32 c0 = 0; c0 < d.k; c0 += kBatch) {
+            u32 x[kBatch];
+            load_slot_bytes(x, blocks, sl, d.slot0, c0, d.k, tp);
+#pragma unroll
+            for (u32 q = 0; q < kBatch; ++q)
+                if (c0 + q < d.k) {
+                    const u32 c = c0 + q;
+                    const u32 orow = sl.row[d.slot0 + c];
+                    if (tl.r0 == 0 && orow != 0xFFFFFFFFu && (u64)orow * d.B + tp < d.n)
+                        dst[(u64)orow * d.B] = (u8)x[q];
+                    gf_mac_bytes<R>(acc, tabs + d.tab, c * nrows + tl.r0, x[q]);
+                }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (r < split) {
+                const u32 orow = sl.miss[d.slot0 + tl.r0 + r];
+                if ((u64)orow * d.B + tp < d.n)
+                    dst[(u64)orow * d.B] = (u8)acc[r];
+            } else if (acc[r]) {
+                dchk_report(d, sl, (u32)(crow0 + r), tp);
+            }
+        }
+    }
+}
+
+// R = 0: a chunk with every primary held and no check row, copies only.  KBX > 0: slots per load
+// batch fixed at KBX, as sec_decode_kernel's
+template <int R, int U, bool W, int KBX = 0>
+__global__ __launch_bounds__(sec::max_lanes(R, U)) void sec_decode_check_kernel(const u8 *__restrict__ blocks,
+                                                               u8 *__restrict__ out,
+                                                               const sec::DChkDesc *__restrict__ descs,
+                                                               const sec::Tile *__restrict__ tiles,
+                                                               const u32 *__restrict__ tabs,
+                                                               const sec::DChkSlots sl)
+{
+    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::DChkDesc d = descs[tl.chunk];
+    const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
+    if (t < d.valid)
+        dchk_main<R, U, W, KBX>(blocks, out, d, tl, t, tabs, sl);
+    if (tl.ntail)
+        dchk_ragged<R>(blocks, out, d, tl, tabs, sl);
+}
+
+// One thread per (chunk, position) of the chunks too small for a tile (valid < 16): the copies,
+// every recovered row's byte and every check row's byte there.
+__global__ __launch_bounds__(256) void sec_decode_check_tail(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                             const sec::DChkDesc *__restrict__ descs,
+                                                             const sec::TailItem *__restrict__ items, u32 nitems,
+                                                             const u32 *__restrict__ tabs, const sec::DChkSlots sl)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nitems)
+        return;
+    const sec::TailItem it = items[i];
+    const sec::DChkDesc d = descs[it.chunk];
+    u8 *dst = out + d.out_off + it.t;
+    auto entry_byte = [&](u32 c) -> u32 {  // bytes past the entry's avail read as zero
+        return it.t < sl.avail[d.slot0 + c] ? (u32)blocks[sl.off[d.slot0 + c] + it.t] : 0u;
+    };
+    for (u32 c = 0; c < d.k; ++c) {
+        const u32 orow = sl.row[d.slot0 + c];
+        if (orow != 0xFFFFFFFFu && (u64)orow * d.B + it.t < d.n)
+            dst[(u64)orow * d.B] = (u8)entry_byte(c);
+    }
+    const u32 nrows = d.e + d.nr;
+    for (u32 r = 0; r < nrows; ++r) {
+        if (r < d.e && (u64)sl.miss[d.slot0 + r] * d.B + it.t >= d.n)
+            continue;
+        u32 acc = r < d.e ? 0u : entry_byte(d.k + r - d.e);
+        for (u32 c = 0; c < d.k; ++c)
+            acc ^= gf_mul_byte(tabs + d.tab + (c * nrows + r) * sec::kTabDwords, entry_byte(c));
+        if (r < d.e)
+            dst[(u64)sl.miss[d.slot0 + r] * d.B] = (u8)acc;
+        else if (acc)
+            dchk_report(d, sl, r - d.e, it.t);
+    }
+}
+
 // ---- SHA-1 of pieces (storb piece ids, /root/reference/storb/util/piece.py:54-68) ----
 // One lane per message: SHA-1 is a sequential chain of 64-byte compressions, so a
 // message cannot be split; the kernel is latency-bound on each lane's round chain
@@ -1625,6 +1885,33 @@ hipError_t dispatch_chk(int rows, const u8 *b, const sec::ChkDesc *d, const sec:
     }
 }
 
+template <int R, int U, bool W, int KBX>
+hipError_t launch_dchk(const u8 *blocks, u8 *out, const sec::DChkDesc *descs, const sec::Tile *tiles, u32 ntiles,
+                       const u32 *tabs, sec::DChkSlots sl, u32 lanes, hipStream_t s)
+{
+    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
+    return launch_shm(sec_decode_check_kernel<R, U, W, KBX>, dim3(ntiles), dim3(lanes),
+                      lds_tab_bytes<KB, R, true>(lanes), s, blocks, out, descs, tiles, tabs, sl);
+}
+
+template <int U, bool W, int KBX = 0>
+hipError_t dispatch_dchk(int rows, const u8 *b, u8 *o, const sec::DChkDesc *d, const sec::Tile *t, u32 nt,
+                         const u32 *tabs, sec::DChkSlots sl, u32 lanes, hipStream_t s)
+{
+    switch (rows) {
+    case 0: return launch_dchk<0, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 1: return launch_dchk<1, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 2: return launch_dchk<2, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 3: return launch_dchk<3, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 4: return launch_dchk<4, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 5: return launch_dchk<5, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 6: return launch_dchk<6, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 7: return launch_dchk<7, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    case 8: return launch_dchk<8, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace
 
 void sec_next_launch_events(void **start, void **stop)
@@ -1791,4 +2078,34 @@ int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uin
         return hipSuccess;
     return launch(sec_check_final, dim3((nentries + 255) / 256), dim3(256), (hipStream_t)stream, blocks, descs,
                   nentries, sl, results, row_bad, column);
+}
+
+int sec_launch_decode_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
+                            const sec::DChkDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
+                            sec::DChkSlots sl, void *stream, int kb)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    if (rows < 0 || U != 1 || lanes < 64 || lanes % 64 || lanes > sec::max_lanes(rows, U))
+        return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const u32 L = (u32)lanes;
+    if (kb) {  // small load batches: tiles of chunks with k <= kb only
+        if (wide || kb != 4)
+            return hipErrorInvalidValue;
+        return dispatch_dchk<1, false, 4>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
+    }
+    if (wide)
+        return dispatch_dchk<1, true>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
+    return dispatch_dchk<1, false>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
+}
+
+int sec_launch_decode_check_tail(const uint8_t *blocks, uint8_t *out, const sec::DChkDesc *descs,
+                                 const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::DChkSlots sl,
+                                 void *stream)
+{
+    if (nitems == 0)
+        return hipSuccess;
+    return launch(sec_decode_check_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out,
+                  descs, items, nitems, tabs, sl);
 }

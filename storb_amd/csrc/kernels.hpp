@@ -119,6 +119,32 @@ struct ChkResult {
     uint32_t pad;
 };
 
+// One decode + check chunk, device copy (48 B): e missing primaries recovered from k basis blocks,
+// the present primaries copied, and nr check rows predicted from the same basis and compared with
+// the stored rows.  Its n = k + nr entries in DChkSlots::off / avail are those of its ChkDesc (the
+// same arrays: sec_check_final writes the results), row / miss are indexed from slot0 as well.
+struct DChkDesc {
+    uint64_t out_off;  // reassembled chunk (recover-only: its e recovered blocks) in `out`
+    uint64_t n;        // bytes to write there
+    uint32_t B;
+    uint32_t k;
+    uint32_t e;        // missing primaries: rows 0 .. e-1 of the table, stored
+    uint32_t nr;       // check rows: rows e .. e+nr-1 of the table, compared
+    uint32_t tab;      // dword offset of tables, layout [slot][row][5]
+    uint32_t slot0;    // first of the n entries
+    uint32_t flag0;    // as ChkDesc::flag0
+    uint32_t valid;    // positions [0, valid) where every output row is writable and all n entries
+                       // readable: min(last output row's length unless recover-only, every avail)
+};
+
+struct DChkSlots {
+    const uint64_t *off;    // block address: blocks + off[entry]
+    const uint32_t *avail;  // bytes of the block that exist in memory; the rest read as zero
+    const uint32_t *row;    // basis slots: output row a present primary is copied to, or 0xFFFFFFFF
+    const uint32_t *miss;   // miss[slot0 + r]: output row of recovered row r
+    uint32_t *flags;        // see ChkDesc::flag0
+};
+
 // One chunk of a syndrome decode (kernels_bs.hip sec_syndrome_bs_kernel, sec_decode_bs_kernel; 56 B).  Block j of
 // the chunk (data j < k, parity row r at j = k + r) is at blocks + off[slot0 + j] with
 // avail[slot0 + j] readable bytes, when its bit in dmask / pmask is set.
@@ -266,6 +292,14 @@ int sec_launch_check(int rows, int U, int wide, int lanes, const uint8_t *blocks
                      int kb = 0);
 int sec_launch_check_tail(const uint8_t *blocks, const sec::ChkDesc *descs, const sec::TailItem *items,
                           uint32_t nitems, const uint32_t *tabs, sec::ChkSlots slots, void *stream);
+// Decode + check (sec_decode_check_kernel): tiles as the decode's over the chunk's e + nr rows
+// (rows 0..8 of the tile's group, kb as sec_launch_decode); the results by sec_launch_check_final
+int sec_launch_decode_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
+                            const sec::DChkDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
+                            sec::DChkSlots slots, void *stream, int kb = 0);
+int sec_launch_decode_check_tail(const uint8_t *blocks, uint8_t *out, const sec::DChkDesc *descs,
+                                 const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs,
+                                 sec::DChkSlots slots, void *stream);
 // One thread per entry of the launch's chunks: slots.flags into results[d.res], row_bad[d.cslot0 + ..]
 // and, for an inconsistent chunk, column[d.cslot0 + ..] (row_bad, column nullable)
 int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uint32_t nentries, sec::ChkSlots slots,

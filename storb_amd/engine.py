@@ -24,8 +24,8 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (CHK_DTYPE, CHK_RESULT_DTYPE, COPY_DTYPE, DEC_DTYPE, ENC_DTYPE, MSG_DTYPE, REP_DTYPE, SEC_F_ASYNC,
-                   SEC_F_GPU_PARITY_IDS, SEC_F_HOST, SEC_F_RECOVER, SEC_F_STAGED)
+from ._lib import (CHK_DTYPE, CHK_RESULT_DTYPE, COPY_DTYPE, DCHK_DTYPE, DEC_DTYPE, ENC_DTYPE, MSG_DTYPE, REP_DTYPE,
+                   SEC_F_ASYNC, SEC_F_GPU_PARITY_IDS, SEC_F_HOST, SEC_F_RECOVER, SEC_F_STAGED)
 
 
 class Error(Exception):
@@ -78,7 +78,8 @@ def device_count() -> int:
     return n.value if rc == 0 else 0
 
 
-_TIMING_KINDS = {"encode": 0, "decode": 1, "sha1": 2, "bignum": 3, "repair": 4, "check": 5}
+_TIMING_KINDS = {"encode": 0, "decode": 1, "sha1": 2, "bignum": 3, "repair": 4, "check": 5,
+                 "decode_check": 6}
 
 
 class Engine:
@@ -328,6 +329,96 @@ class Engine:
             else:
                 out.append((int(res[j]["first"]), [q for q in range(nb) if rb[s0 + q]], col[s0:s0 + nb].tobytes()))
         return out
+
+    def decode_check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks, out,
+                           results, *, block_avail: np.ndarray | None = None, row_bad=None, column=None,
+                           host: bool = False, asynchronous: bool = False, recover_only: bool = False) -> None:
+        """sec_decode_check_batch: decode_batch on each chunk's first k entries and check_batch on
+        all n of them (DCHK_DTYPE descriptors) in one pass over the blocks.  `out` receives what
+        decode_batch writes (recover_only: just the missing primaries), consistent or not;
+        results, row_bad and column what check_batch reports.  host: host buffers, always staged,
+        every entry gathered once."""
+        descs = np.ascontiguousarray(descs, dtype=DCHK_DTYPE)
+        sn = np.ascontiguousarray(sharenums, dtype=np.int32)
+        bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
+        av = None if block_avail is None else np.ascontiguousarray(block_avail, dtype=np.uint64)
+        if av is not None and av.size < bo.size:
+            raise ValueError("block_avail needs one entry per slot")
+        b, _kb = addr(blocks)
+        o, _ko = addr(out)
+        r, _kr = addr(results)
+        rb, _krb = addr(row_bad)
+        co, _kco = addr(column)
+        flags = ((SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0) |
+                 (SEC_F_RECOVER if recover_only else 0))
+        self._check(self.lib.sec_decode_check_batch(self._ctx, _ptr(descs), len(descs), _ptr(sn) or None,
+                                                    _ptr(bo) or None, None if av is None else _ptr(av), b or None,
+                                                    o or None, r or None, rb or None, co or None, flags))
+
+    def decode_check_host(self, items):
+        """Reassemble host chunks and check their spare blocks in one call.
+
+        items: [(k, m, blocks, sharenums, padlen)] with n >= k equal-length blocks per chunk: the
+        first k are decoded from and are the check's basis, the others are the check rows.
+        Returns ``(data, checks)``: data = every chunk's k*B - padlen bytes concatenated, as
+        ``decode_host`` returns them; checks = per chunk ``(first, bad, column)`` as
+        ``check_host`` returns them.  One recover-only host call stages every block once; only the
+        recovered rows and the results come back, and the present primaries are joined from the
+        caller's blocks on the library's copy threads.  The bytes are returned whatever the check
+        says."""
+        for it in items:
+            check_decode_check_item(*it)
+        n = len(items)
+        if not n:
+            return b"", []
+        descs = np.zeros(n, dtype=DCHK_DTYPE)
+        nslots = sum(len(it[2]) for it in items)
+        sn = np.zeros(max(nslots, 1), dtype=np.int32)
+        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
+        keep, rec = [], []
+        slot = total = 0
+        for j, (k, m, blocks, sharenums, padlen) in enumerate(items):
+            B = len(blocks[0])
+            for q, b in enumerate(blocks):
+                a, kp = addr(b)
+                keep.append(kp)
+                bo[slot + q] = a
+                sn[slot + q] = int(sharenums[q])
+            descs[j] = (total, B, padlen, slot, len(blocks), k, m, 0)
+            rec.append(total)
+            slot += len(blocks)
+            total += sum(1 for x in sharenums[:k] if int(x) >= k) * B
+        buf = self._out_buffer(max(total, 1))
+        res = np.zeros(n, dtype=CHK_RESULT_DTYPE)
+        rb = np.zeros(max(nslots, 1), dtype=np.uint8)
+        col = np.zeros(max(nslots, 1), dtype=np.uint8)
+        self.decode_check_batch(descs, sn, bo, 0, buf, res, row_bad=rb, column=col, host=True, recover_only=True)
+        mv = memoryview(buf)
+        views = []
+        for j, (k, m, blocks, sharenums, padlen) in enumerate(items):
+            B = len(blocks[0])
+            prim = {int(x): q for q, x in enumerate(sharenums[:k]) if int(x) < k}  # primary -> its block
+            o, left = rec[j], k * B - padlen
+            for row in range(k):
+                if left <= 0:
+                    break
+                if row in prim:
+                    v = memoryview(blocks[prim[row]]).cast("B")
+                else:  # the next recovered row (rows come in primary order)
+                    v = mv[o:o + B]
+                    o += B
+                views.append(v[:left] if left < B else v)
+                left -= B
+        data = self._joined(views)
+        checks = []
+        for j in range(n):
+            s0, nb = int(descs[j]["slot0"]), int(descs[j]["n"])
+            if int(res[j]["first"]) == _lib.CHK_CONSISTENT:
+                checks.append((None, [], None))
+            else:
+                checks.append((int(res[j]["first"]), [q for q in range(nb) if rb[s0 + q]],
+                               col[s0:s0 + nb].tobytes()))
+        return data, checks
 
     def encode_digest_batch(self, descs: np.ndarray, src, parity, digests, *, host: bool = False,
                             asynchronous: bool = False) -> None:
@@ -746,6 +837,16 @@ def check_check_item(k: int, m: int, blocks, sharenums) -> None:
         raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
     if len(set(sn)) != len(sn):
         raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
+
+
+def check_decode_check_item(k: int, m: int, blocks, sharenums, padlen: int) -> None:
+    """The decode + check preconditions for one chunk (the library's own checks, raised before any
+    GPU work): n equal-length blocks and n sharenums, 1 <= k <= m <= 256, k <= n <= m, sharenums
+    in [0, m) and distinct, 0 <= padlen <= k*B.  Raises Error."""
+    check_check_item(k, m, blocks, sharenums)
+    B = len(blocks[0]) if blocks else 0
+    if not (0 <= padlen <= k * B):
+        raise Error(_lib.strerror(_lib.SEC_EPADLEN))
 
 
 # -- matrices (host arithmetic; no device needed) ------------------------------

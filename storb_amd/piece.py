@@ -26,6 +26,9 @@ Deliberate differences (documented in DESIGN.md §Boundary):
 * ``check_chunks`` / ``check_pieces`` (no reference counterpart) tell whether the pieces held of
   a chunk agree with each other and, with two pieces beyond k, which one does not: the code's own
   check, read once on the GPU, where the reference can only hash every piece.
+* ``decode_chunks_checked`` / ``reconstruct_data_checked`` (no reference counterpart) reassemble
+  the chunks and run that check in the same pass over the pieces: a download verified by the code
+  word itself, where the validator hashes every fetched piece on one core (validator.py:1556-1604).
 * ``reconstruct_data_stream`` decodes window w+1 on a worker thread (its own HIP context)
   while the caller consumes window w's chunks; ``encode_chunks_stream`` does the same for the
   upload loop's produce/consume pattern (validator.py:1338-1446, 1630-1638).
@@ -60,8 +63,8 @@ from pydantic import BaseModel, ConfigDict, Field
 
 from .constants import MAX_PIECE_SIZE, MIN_PIECE_SIZE, PIECE_LENGTH_OFFSET, PIECE_LENGTH_SCALING
 from .easyfec import Decoder, Encoder, Error
-from .engine import (EngineGroup, check_decode_item, check_locate, choose_blocks, device_count, get_engine,
-                     spread_threads)
+from .engine import (EngineGroup, check_decode_check_item, check_decode_item, check_locate, choose_blocks, device_count,
+                     get_engine, spread_threads)
 
 logger = logging.getLogger(__name__)
 
@@ -70,6 +73,7 @@ __all__ = [
     "encode_chunk", "decode_chunk", "reconstruct_data", "reconstruct_data_stream", "encode_chunks",
     "decode_chunks", "chunk_shape", "piece_hashes", "encode_chunks_with_ids", "encode_chunks_stream", "Encoder",
     "Decoder", "Error", "use_devices", "repair_chunks", "repair_pieces", "ChunkCheck", "check_chunks", "check_pieces",
+    "decode_chunks_checked", "reconstruct_data_checked", "PieceCheckError",
 ]
 
 PREFETCH_PIECE_IDS = True  # encode_chunk hashes its pieces on a thread pool (see module doc)
@@ -785,6 +789,53 @@ def _check_item(ch: EncodedChunk, held: list[Piece]):
     return ch.k, ch.m, [p.data for p in use], [p.piece_idx for p in use]
 
 
+def _held_pieces(ch: EncodedChunk, what: str) -> list[Piece]:
+    """The distinct pieces held of a chunk in ascending piece_idx (the first of any repeat)."""
+    if not (1 <= ch.k <= ch.m <= 256):
+        raise Error(f"Precondition violation: 1 <= k <= m <= 256 required (k={ch.k}, m={ch.m})")
+    have: dict[int, Piece] = {}
+    for p in ch.pieces or []:
+        have.setdefault(p.piece_idx, p)
+    use = sorted(have.values(), key=lambda p: p.piece_idx)
+    if len(use) < ch.k:
+        raise ValueError(f"Not enough pieces to {what} chunk {ch.chunk_idx}")
+    return use
+
+
+def _check_rounds(chunks, held: list[list[Piece]], out: list[ChunkCheck], locate: bool, first=None) -> None:
+    """The check, locate, re-check rounds of ``check_chunks`` over `held` (per chunk its distinct
+    pieces, ascending; a located piece is taken out of its list), filling `out`.  first: the
+    ``(items, results)`` of round one when the caller has run it already (the fused decode +
+    check of ``decode_chunks_checked``); the later rounds are plain checks, one call each."""
+    todo = list(range(len(chunks)))  # chunks checked in the next call
+    first_round = True
+    while todo:
+        if first_round and first is not None:
+            items, res = first
+        else:
+            items = [_check_item(chunks[i], held[i]) for i in todo]
+            res = get_engine().check_host(items)
+        again = []
+        for i, it, (first_at, _bad, column) in zip(todo, items, res):
+            ck = out[i]
+            if first_round:
+                ck.consistent = first_at is None
+                ck.first_bad_offset = first_at
+            if first_at is None:
+                ck.located = not first_round
+                continue
+            if not locate:
+                continue
+            who = check_locate(it[0], it[1], it[3], column) if len(it[3]) - it[0] >= 2 else -2
+            if who < 0:  # no single piece explains the column: bad_piece_idx is what was named so far
+                continue
+            ck.bad_piece_idx.append(it[3][who])
+            held[i] = [p for p in held[i] if p.piece_idx != it[3][who]]
+            again.append(i)
+        todo = again
+        first_round = False
+
+
 def check_chunks(chunks: typing.Sequence[EncodedChunk], *, locate: bool = True) -> list[ChunkCheck]:
     """Whether each chunk's held pieces agree with each other, and which piece does not: GPU calls
     that read every held piece once and hash nothing.
@@ -803,46 +854,105 @@ def check_chunks(chunks: typing.Sequence[EncodedChunk], *, locate: bool = True) 
     out: list[ChunkCheck] = []
     held: list[list[Piece]] = []
     for ch in chunks:
-        if not (1 <= ch.k <= ch.m <= 256):
-            raise Error(f"Precondition violation: 1 <= k <= m <= 256 required (k={ch.k}, m={ch.m})")
-        have: dict[int, Piece] = {}
-        for p in ch.pieces or []:
-            have.setdefault(p.piece_idx, p)
-        use = sorted(have.values(), key=lambda p: p.piece_idx)
-        if len(use) < ch.k:
-            raise ValueError(f"Not enough pieces to check chunk {ch.chunk_idx}")
+        use = _held_pieces(ch, "check")
         held.append(use)
         out.append(ChunkCheck(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
-    todo = list(range(len(chunks)))  # chunks checked in the next call
-    first_round = True
-    while todo:
-        items = [_check_item(chunks[i], held[i]) for i in todo]
-        res = get_engine().check_host(items)
-        again = []
-        for i, it, (first, _bad, column) in zip(todo, items, res):
-            ck = out[i]
-            if first_round:
-                ck.consistent = first is None
-                ck.first_bad_offset = first
-            if first is None:
-                ck.located = not first_round
-                continue
-            if not locate:
-                continue
-            who = check_locate(it[0], it[1], it[3], column) if len(it[3]) - it[0] >= 2 else -2
-            if who < 0:  # no single piece explains the column: bad_piece_idx is what was named so far
-                continue
-            ck.bad_piece_idx.append(it[3][who])
-            held[i] = [p for p in held[i] if p.piece_idx != it[3][who]]
-            again.append(i)
-        todo = again
-        first_round = False
+    _check_rounds(chunks, held, out, locate)
     return out
 
 
 def check_pieces(chunk: EncodedChunk, *, locate: bool = True) -> ChunkCheck:
     """``check_chunks`` for one chunk."""
     return check_chunks([chunk], locate=locate)[0]
+
+
+class PieceCheckError(ValueError):
+    """``reconstruct_data_checked``: some chunk's held pieces disagree and the corrupt ones could
+    not be named, so its bytes cannot be trusted.  ``checks``: every chunk's ``ChunkCheck``."""
+
+    def __init__(self, message: str, checks: list[ChunkCheck]):
+        super().__init__(message)
+        self.checks = checks
+
+
+def decode_chunks_checked(encoded_chunks: typing.Sequence[EncodedChunk], *,
+                          locate: bool = True) -> tuple[bytes, list[ChunkCheck]]:
+    """``decode_chunks`` and ``check_chunks`` in one pass over the pieces: the concatenation of
+    every chunk's bytes, and per chunk what the code word says about the pieces held.
+
+    Every distinct piece held of a chunk is used, ordered as ``check_chunks`` orders them:
+    ``choose_blocks``' pick is decoded from and predicts the others, which are compared with what
+    is held; ONE fused GPU call reads each piece once (``Engine.decode_check_host``) and hashes
+    nothing.  Chunks reported inconsistent go on through ``check_chunks``' rounds (locate, re-check
+    without the named piece, in batches); those that end up ``located`` are decoded again from
+    their remaining pieces, all in one ``decode_host`` call, and spliced into the result.
+
+    The bytes of a chunk are trustworthy exactly when its ``ChunkCheck`` is ``consistent or
+    located``; otherwise they are what its first k pieces decode to, corrupt piece included.
+    What "trustworthy" means: corruption confined to at most n - k of a chunk's n held pieces is
+    always detected, and a chunk with exactly k pieces is not checked at all; more than n - k
+    pieces altered together can form another code word, which only the recorded piece ids
+    exclude.  ``devices=`` / ``EngineGroup`` splitting and a streaming variant are not provided:
+    one device, one call."""
+    chunks = list(encoded_chunks)
+    out: list[ChunkCheck] = []
+    held: list[list[Piece]] = []
+    items = []
+    for ch in chunks:
+        use = _held_pieces(ch, "reconstruct")
+        held.append(use)
+        out.append(ChunkCheck(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
+        items.append(_check_item(ch, use))
+    if not chunks:
+        return b"", []
+    full = [it + (ch.padlen,) for it, ch in zip(items, chunks)]
+    for it in full:  # every chunk's preconditions before any device work
+        check_decode_check_item(*it)
+    data, res = get_engine().decode_check_host(full)
+    _check_rounds(chunks, held, out, locate, first=(items, res))
+    redo = [i for i, ck in enumerate(out) if ck.located]
+    if not redo:
+        return data, out
+    again = []
+    for i in redo:  # from the pieces that passed the last re-check
+        k, m, blocks, sharenums = _check_item(chunks[i], held[i])
+        again.append((k, m, blocks[:k], sharenums[:k], chunks[i].padlen))
+    fixed = get_engine().decode_host(again)
+    lens = [it[0] * len(it[2][0]) - it[4] for it in full]
+    starts = [0]
+    for n in lens:
+        starts.append(starts[-1] + n)
+    parts, at, f = [], 0, 0
+    view = memoryview(data)
+    for i in redo:
+        parts.append(view[at:starts[i]])
+        parts.append(memoryview(fixed)[f:f + lens[i]])
+        f += lens[i]
+        at = starts[i + 1]
+    parts.append(view[at:])
+    return b"".join(parts), out
+
+
+def reconstruct_data_checked(pieces: list[Piece], chunks: list[EncodedChunk]) -> tuple[bytes, list[ChunkCheck]]:
+    """``reconstruct_data`` verified by the code word in the same pass (``decode_chunks_checked``
+    over every piece handed over, grouped as ``reconstruct_data`` groups them).  Raises
+    ``ValueError("Not enough pieces to reconstruct chunk N")`` as ``reconstruct_data`` does, before
+    any decode, and ``PieceCheckError`` (carrying ``.checks``) when some chunk is neither
+    consistent nor located; otherwise returns the bytes, all trustworthy in
+    ``decode_chunks_checked``'s sense, and the checks.  One device, no streaming variant."""
+    by_chunk: dict[int, list[Piece]] = {}
+    for p in pieces:
+        by_chunk.setdefault(p.chunk_idx, []).append(p)
+    for chunk in chunks:
+        relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
+        if len(relevant) < chunk.k:
+            raise ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
+        chunk.pieces = relevant
+    data, checks = decode_chunks_checked(chunks)
+    bad = [ck.chunk_idx for ck in checks if not (ck.consistent or ck.located)]
+    if bad:
+        raise PieceCheckError(f"Held pieces disagree and no corrupt piece could be named in chunk(s) {bad}", checks)
+    return data, checks
 
 
 def _windows(chunks, nbytes, size_of) -> Iterator[list]:
