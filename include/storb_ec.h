@@ -135,7 +135,8 @@ int sec_sync(sec_ctx *ctx);
 int sec_ctx_set_timing(sec_ctx *ctx, int enable);
 /* Waits for recorded pairs, returns the summed milliseconds and launch count of
  * kind 0 = encode, 1 = decode, 2 = SHA-1, 3 = bignum (APDP), 4 = repair (its kernels and,
- * with digests, their SHA-1), 5 = check, 6 = decode + check, and clears them. */
+ * with digests, their SHA-1), 5 = check, 6 = decode + check, 7 = repair + check (its main kernel and
+ * tail, sec_check_final and, with digests, their SHA-1), and clears them. */
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches);
 
 /* ---- context options --------------------------------------------------------
@@ -360,6 +361,56 @@ int sec_decode_check_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t n
                            const uint64_t *block_avail, const uint8_t *blocks, uint8_t *out,
                            sec_chk_result *results, uint8_t *row_bad, uint8_t *column,
                            unsigned flags);
+
+/* ---- repair + check: regenerate lost pieces and check the spare ones in one pass ---------------
+ * A repair runs because a miner is gone, and the caller usually still reaches more than k of the
+ * chunk's pieces.  This call regenerates the lost pieces from k of them and checks the spare ones
+ * against the same k from one read of the n blocks: n*B bytes read and ntargets*B written, where
+ * sec_check_batch followed by sec_repair_batch reads the k basis blocks twice.  The contract is the
+ * COMPOSITION of those two calls on the same arrays:
+ *   - the targets and `digests` (nullable) receive exactly what sec_repair_batch writes for entries
+ *     slot0 .. slot0+k-1 as sources: block target_nums[tgt0 + j] whole at out + target_offs[tgt0 + j],
+ *     all B bytes (for data block k-1 too, zero padding included), in the caller's target order, each
+ *     at its own address and any byte alignment; 20 digest bytes per target at digests + 20 (tgt0 + j),
+ *     from the SHA-1 kernel while the targets are device-resident.  The targets are written whether
+ *     or not the chunk turns out consistent.
+ *   - results, row_bad (nullable) and column (nullable) receive exactly what sec_check_batch
+ *     reports for entries slot0 .. slot0+n-1: the first k are the basis, the rest the check rows.
+ * The first k entries may be any k distinct blocks in any order.  block_avail (nullable) has the
+ * meaning both calls give it, for basis entries and check rows alike; nothing past an entry's avail
+ * is read.  A chunk with ntargets == 0 is a plain check, one with n == k a plain repair, reported
+ * consistent; with both it launches nothing.  `blocks` or `out` may be NULL: the offsets are then
+ * absolute addresses.  Nothing is ever written to the blocks; every call starts from clean state.
+ * More than 8 rows (targets + check rows) of a chunk take ceil((ntargets + n - k) / 8) row groups
+ * over its basis.
+ * Aliasing: sec_repair_batch's rule (no target range may overlap a block or another target of the
+ * call).
+ * Flags: none or SEC_F_ASYNC (device pointers); SEC_F_HOST (host pointers) is ALWAYS staged through
+ * pinned slabs as sec_check_batch's: the n*B bytes of a chunk are gathered ONCE, and the targets,
+ * digests and results are scattered back; sec_ctx_host_paths counts the call as staged.
+ * SEC_F_HOST with SEC_F_ASYNC is SEC_EINVAL; any other flag is SEC_EINVAL.
+ * Errors, all before any device work, in this order: SEC_EINVAL a NULL array, NULL results, n < 0
+ * or ntargets < 0; SEC_EKM; SEC_ENBLOCKS n < k or n > m; SEC_ESHARENUM an entry or a target outside
+ * [0, m); SEC_EDUPSHARE a repeat among the n entries, a repeated target, or a target that is also
+ * one of the n entries; SEC_ESIZE B >= 2^31.
+ * sec_timing_collect kind 7 times this call's kernels. */
+typedef struct sec_rchk_chunk {
+    uint64_t B;      /* block bytes                                                     */
+    uint64_t slot0;  /* first of the chunk's n entries in sharenums[] / block_offs[] /
+                        block_avail[]                                                   */
+    uint64_t tgt0;   /* first of its ntargets entries in target_nums[] / target_offs[]  */
+    int32_t ntargets;
+    int32_t n;       /* blocks held, k <= n <= m                                        */
+    int32_t k;
+    int32_t m;
+} sec_rchk_chunk; /* 40 bytes */
+
+int sec_repair_check_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks,
+                           const int32_t *sharenums, const uint64_t *block_offs,
+                           const uint64_t *block_avail, const uint8_t *blocks,
+                           const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out,
+                           uint8_t *digests, sec_chk_result *results, uint8_t *row_bad,
+                           uint8_t *column, unsigned flags);
 
 /* Which single entry explains an inconsistent column (host arithmetic, no device needed).
  * sharenums: the n block numbers, the first k the basis; column: the n bytes sec_check_batch

@@ -68,6 +68,11 @@ class sec_dchk_chunk(ctypes.Structure):
                 ("pad", ctypes.c_int32)]
 
 
+class sec_rchk_chunk(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_uint64), ("slot0", ctypes.c_uint64), ("tgt0", ctypes.c_uint64),
+                ("ntargets", ctypes.c_int32), ("n", ctypes.c_int32), ("k", ctypes.c_int32), ("m", ctypes.c_int32)]
+
+
 class sec_chk_result(ctypes.Structure):
     _fields_ = [("first", ctypes.c_uint64), ("nbad", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
@@ -83,6 +88,8 @@ CHK_DTYPE = np.dtype([("B", "<u8"), ("slot0", "<u8"), ("n", "<i4"), ("k", "<i4")
                      align=True)  # sec_chk_chunk
 DCHK_DTYPE = np.dtype([("out_off", "<u8"), ("B", "<u8"), ("padlen", "<u8"), ("slot0", "<u8"), ("n", "<i4"), ("k", "<i4"),
                        ("m", "<i4"), ("pad", "<i4")], align=True)  # sec_dchk_chunk
+RCHK_DTYPE = np.dtype([("B", "<u8"), ("slot0", "<u8"), ("tgt0", "<u8"), ("ntargets", "<i4"), ("n", "<i4"), ("k", "<i4"),
+                       ("m", "<i4")], align=True)  # sec_rchk_chunk
 CHK_RESULT_DTYPE = np.dtype([("first", "<u8"), ("nbad", "<u4"), ("pad", "<u4")], align=True)  # sec_chk_result
 CHK_CONSISTENT = 0xFFFFFFFFFFFFFFFF  # sec_chk_result.first of a consistent chunk
 MSG_DTYPE = np.dtype([("addr", "<u8"), ("len", "<u8"), ("avail", "<u8")], align=True)
@@ -99,6 +106,7 @@ assert DEC_DTYPE.itemsize == ctypes.sizeof(sec_dec_chunk) == 40
 assert REP_DTYPE.itemsize == ctypes.sizeof(sec_rep_chunk) == 40
 assert CHK_DTYPE.itemsize == ctypes.sizeof(sec_chk_chunk) == 32
 assert DCHK_DTYPE.itemsize == ctypes.sizeof(sec_dchk_chunk) == 48
+assert RCHK_DTYPE.itemsize == ctypes.sizeof(sec_rchk_chunk) == 40
 assert CHK_RESULT_DTYPE.itemsize == ctypes.sizeof(sec_chk_result) == 16
 
 # every symbol include/storb_ec.h declares: name -> (restype, argtypes)
@@ -130,6 +138,8 @@ _SIGS = {
     "sec_check_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint]),
     "sec_decode_check_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               ctypes.c_uint]),
+    "sec_repair_check_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, ctypes.c_uint]),
     "sec_check_locate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,
                                         ctypes.POINTER(ctypes.c_int32)]),
     "sec_sha1_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_uint]),

@@ -298,6 +298,7 @@ struct SubPlan {
     uint64_t chk_rows = 0, chk_col = 0;    // check, host mode: row_bad and column in the slab output
     size_t off_cdesc = 0;                  // decode + check: the chunks' ChkDesc (sec_check_final)
     uint64_t dchk_out = 0;                 // decode + check, host mode: the decoded bytes in the slab output
+    uint64_t rchk_out = 0;                 // repair + check, host mode: the targets in the slab output
     // repair digests: runs of consecutive digest slots, (first message, count, first slot)
     std::vector<std::array<uint64_t, 3>> sha_runs;
     // syndrome decodes (decode): phase 1 launches (bit-sliced syndromes) and phase 2 launches
@@ -679,15 +680,16 @@ struct sec_ctx {
     hipStream_t own = nullptr;
     hipStream_t ext = nullptr;
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[7];  // by timing kind
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[8];  // by timing kind
     std::vector<hipEvent_t> ev_pool;
     hipEvent_t stop_ev = nullptr;  // between timing_begin and timing_end of an attached launch
     PinBuf pin{nullptr, 0, false};  // metadata image staging (its own, not pooled: small, every call)
     hipEvent_t pin_ev = nullptr, meta_ev = nullptr;
-    TableCache enc_tabs, dec_tabs, rep_tabs, chk_tabs, dchk_tabs;
-    Plan enc_plan, dec_plan, sha_plan, bn_plan, rep_plan, chk_plan, dchk_plan;
+    TableCache enc_tabs, dec_tabs, rep_tabs, chk_tabs, dchk_tabs, rchk_tabs;
+    Plan enc_plan, dec_plan, sha_plan, bn_plan, rep_plan, chk_plan, dchk_plan, rchk_plan;
     DevBuf chk_flags;   // check: the flag words of the call in flight (ChkDesc::flag0)
     DevBuf dchk_flags;  // decode + check: likewise
+    DevBuf rchk_flags;  // repair + check: likewise
     DevBuf bn_scratch;  // host-mode staging of sec_bn_modexp / mulmod operands
     DevBuf bn_part;     // partial residues of segmented reductions (one region per slot)
     DevBuf syn;         // syndrome rows of device-mode syndrome decodes
@@ -2087,6 +2089,240 @@ int launch_decode_check_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, c
     return SEC_OK;
 }
 
+// ---- repair + check plan --------------------------------------------------------
+// Preconditions of a repair + check (sec_repair_check_batch): sec_check_batch's for the n held
+// blocks, then the targets: in [0, m), distinct, none of them held.
+int check_repair_check(int k, int m, const int32_t *sharenums, int n, const int32_t *targets, int nt)
+{
+    if (n < 0 || nt < 0 || !sharenums || (nt > 0 && !targets))
+        return SEC_EINVAL;
+    if (k < 1 || m < k || m > 256)
+        return SEC_EKM;
+    if (n < k || n > m)
+        return SEC_ENBLOCKS;
+    for (int i = 0; i < n; ++i)
+        if (sharenums[i] < 0 || sharenums[i] >= m)
+            return SEC_ESHARENUM;
+    for (int i = 0; i < nt; ++i)
+        if (targets[i] < 0 || targets[i] >= m)
+            return SEC_ESHARENUM;
+    bool seen[256] = {false};
+    for (int i = 0; i < n + nt; ++i) {
+        const int b = i < n ? sharenums[i] : targets[i - n];
+        if (seen[b])
+            return SEC_EDUPSHARE;
+        seen[b] = true;
+    }
+    return SEC_OK;
+}
+
+// The check plan with the repair's rows in front (a sibling of build_repair_plan and
+// build_decode_check_plan): per chunk one table of the repair matrix over its basis, layout
+// [slot][row][5], rows = its targets in the caller's order, then its check rows in entry order
+// (cached by basis, targets and check rows); its n entries as a check's (the basis in normalised
+// order, then the check rows); one address per target; tiles as a repair's (add_work) over all
+// nt + nr rows and valid = the least avail of all n; flag words as a check's, in ctx->rchk_flags;
+// one SHA-1 message per target when digests are asked for.  Both an RChkDesc (the tile kernels) and
+// a ChkDesc (sec_check_final) per chunk.  Host mode stages all n entries densely once and returns
+// results, row_bad, column, the targets and their digests through the slab output.
+int build_repair_check_plan(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                            const uint64_t *block_offs, const uint64_t *block_avail, const int32_t *target_nums,
+                            const uint64_t *target_offs, const SlotLayout &L, bool host, bool digest)
+{
+    Plan &plan = ctx->rchk_plan;
+    TableCache &tc = ctx->rchk_tabs;
+    std::vector<PendingExpand> pending;
+    std::vector<uint32_t> tab_of;
+    auto want = [&](int64_t i, std::string &key) -> size_t {
+        const sec_rchk_chunk &c = chunks[i];
+        const int rows = c.ntargets + c.n - c.k;
+        if (!rows)
+            return 0;
+        key = slots_key(c.k, c.m, &L.idx[L.first[i]]) + "|";
+        for (int r = 0; r < c.ntargets; ++r)
+            key += std::to_string(target_nums[c.tgt0 + r]) + ",";
+        key += "|";
+        for (int r = c.k; r < c.n; ++r)
+            key += std::to_string(sharenums[c.slot0 + r]) + ",";
+        return (size_t)c.k * rows;
+    };
+    auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
+        const sec_rchk_chunk &c = chunks[i];
+        const int k = c.k;
+        const int *idx = &L.idx[L.first[i]];
+        std::vector<int> rows_of;
+        if (c.ntargets)
+            rows_of.assign(target_nums + c.tgt0, target_nums + c.tgt0 + c.ntargets);
+        rows_of.insert(rows_of.end(), sharenums + c.slot0 + k, sharenums + c.slot0 + c.n);
+        const int rows = (int)rows_of.size();
+        std::vector<uint8_t> rm;
+        if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k), rows_of, rm))
+            return (int)SEC_ESINGULAR;
+        cf.resize((size_t)k * rows);
+        for (int s = 0; s < k; ++s)
+            for (int r = 0; r < rows; ++r)
+                cf[(size_t)s * rows + r] = rm[(size_t)r * k + s];
+        return (int)SEC_OK;
+    };
+    RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
+
+    // with digests few large slabs, as the repair's (one SHA-1 chain per piece)
+    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return (uint64_t)chunks[i].n * chunks[i].B; },
+                                    (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
+    Image img;
+    plan.subs.clear();
+    plan.nflags = 0;
+    for (auto [c0, c1] : ranges) {
+        SubPlan sp;
+        sp.c0 = c0;
+        sp.c1 = c1;
+        std::vector<sec::RChkDesc> descs((size_t)(c1 - c0));
+        std::vector<sec::ChkDesc> cdescs((size_t)(c1 - c0));
+        std::vector<uint64_t> soff, toff;
+        std::vector<uint32_t> savail, cpos, echunk;
+        std::vector<sec::MsgDesc> msgs;
+        Bins bins;
+        std::vector<sec::TailItem> tail;
+        // host mode's slab output: the results, row_bad and column (one byte per entry each), then
+        // every chunk's targets, then their digests
+        uint64_t nent = 0;
+        for (int64_t i = c0; i < c1; ++i)
+            nent += (uint64_t)chunks[i].n;
+        sp.chk_rows = (uint64_t)(c1 - c0) * sizeof(sec::ChkResult);
+        sp.chk_col = sp.chk_rows + nent;
+        sp.rchk_out = align_up(sp.chk_col + nent, 256);
+        sp.out_bytes = sp.rchk_out;
+        for (int64_t i = c0; i < c1; ++i) {
+            const sec_rchk_chunk &c = chunks[i];
+            const uint64_t base = L.first[i];
+            const uint32_t slot0 = (uint32_t)soff.size();
+            uint64_t min_avail = c.B;
+            for (int e = 0; e < c.n; ++e) {
+                const int from = e < c.k ? L.perm[base + e] : e;
+                soff.push_back(host ? sp.in_bytes + (uint64_t)e * c.B : block_offs[c.slot0 + from]);
+                const uint64_t av = host ? c.B : slot_avail(c, block_avail, from);  // staged entries are zero-filled
+                savail.push_back((uint32_t)av);
+                cpos.push_back((uint32_t)from);
+                echunk.push_back((uint32_t)(i - c0));
+                min_avail = std::min(min_avail, av);
+            }
+            const uint32_t nt = (uint32_t)c.ntargets, nr = (uint32_t)(c.n - c.k);
+            sec::RChkDesc &d = descs[i - c0];
+            d.B = (uint32_t)c.B;
+            d.k = (uint32_t)c.k;
+            d.nt = nt;
+            d.nr = nr;
+            d.tab = tab_of[i];
+            d.slot0 = slot0;
+            d.tgt0 = (uint32_t)toff.size();
+            d.flag0 = (uint32_t)plan.nflags;
+            d.valid = (uint32_t)min_avail;
+            d.pad = 0;
+            sec::ChkDesc &cd = cdescs[i - c0];
+            cd.B = d.B;
+            cd.k = d.k;
+            cd.nr = nr;
+            cd.tab = d.tab;
+            cd.slot0 = slot0;
+            cd.flag0 = d.flag0;
+            cd.valid = d.valid;
+            cd.res = (uint32_t)(host ? i - c0 : i);
+            cd.cslot0 = (uint32_t)(host ? slot0 : c.slot0);
+            cd.pad = 0;
+            plan.nflags += 1 + nr;
+            for (uint32_t r = 0; r < nt; ++r) {
+                const uint64_t to = host ? sp.out_bytes + (uint64_t)r * c.B : target_offs[c.tgt0 + r];
+                if (digest) {
+                    // device mode: the caller's digest slot tgt0 + r; consecutive slots share a launch
+                    const uint64_t slot = host ? msgs.size() : c.tgt0 + (uint64_t)r;
+                    if (sp.sha_runs.empty() || sp.sha_runs.back()[2] + sp.sha_runs.back()[1] != slot)
+                        sp.sha_runs.push_back({(uint64_t)msgs.size(), 0, slot});
+                    ++sp.sha_runs.back()[1];
+                    msgs.push_back(sec::MsgDesc{to, c.B, c.B, 0, 0});
+                }
+                toff.push_back(to);
+            }
+            sp.in_bytes += (uint64_t)c.n * c.B;
+            sp.out_bytes += (uint64_t)nt * c.B;
+            if (nt + nr > 0)
+                add_work(bins, tail, (uint32_t)(i - c0), c.B, (int64_t)min_avail, (int)(nt + nr), c.k, true, false,
+                         dec_small_kb(c.k));
+        }
+        std::vector<sec::Tile> tiles;
+        flatten(bins, sp.groups, tiles, true);
+        sp.ntail = (uint32_t)tail.size();
+        sp.nmsgs = (uint32_t)msgs.size();
+        sp.sha_split = sha1_split(ctx->opt, msgs);
+        sp.dig_off = align_up(sp.out_bytes, 4);  // host mode: digests follow the slab's targets (dword stores)
+        if (host)
+            sp.out_bytes = sp.dig_off + (uint64_t)msgs.size() * 20;
+        sp.off_desc = img.put(descs.data(), descs.size() * sizeof(sec::RChkDesc));
+        sp.off_cdesc = img.put(cdescs.data(), cdescs.size() * sizeof(sec::ChkDesc));
+        sp.off_tiles = img.put(tiles.data(), tiles.size() * sizeof(sec::Tile));
+        sp.off_tail = img.put(tail.data(), tail.size() * sizeof(sec::TailItem));
+        sp.off_savail = img.put(savail.data(), savail.size() * 4);
+        sp.off_cpos = img.put(cpos.data(), cpos.size() * 4);
+        sp.off_echunk = img.put(echunk.data(), echunk.size() * 4);
+        sp.off_toff = img.put(toff.data(), toff.size() * 8);
+        sp.off_msgs = img.put(msgs.data(), msgs.size() * sizeof(sec::MsgDesc));
+        sp.nentries = (uint32_t)echunk.size();
+        soff.resize(soff.size() + sec::kBatchVecs, 0);  // the kernel loads a batch's offsets unconditionally
+        sp.off_soff = img.put(soff.data(), soff.size() * 8);
+        plan.subs.push_back(std::move(sp));
+    }
+    if (plan.nflags >= UINT32_MAX)
+        return SEC_EINVAL;
+    RC(upload_plan(ctx, plan, img, tc, pending));
+    plan.gen = tc.gen;
+    return SEC_OK;
+}
+
+// The repair + check kernels of one launch unit, its results and, with digests, the targets' SHA-1
+// while they are device-resident (timing kind 7; a unit with no row launches the results alone,
+// untimed, as a check's)
+int launch_repair_check_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const uint8_t *blocks, uint8_t *out,
+                            uint8_t *digests, sec::ChkResult *results, uint8_t *row_bad, uint8_t *column,
+                            hipStream_t s)
+{
+    const sec::RChkDesc *dd = plan.meta.as<sec::RChkDesc>(sp.off_desc);
+    const sec::ChkDesc *cd = plan.meta.as<sec::ChkDesc>(sp.off_cdesc);
+    const sec::Tile *dt = plan.meta.as<sec::Tile>(sp.off_tiles);
+    const uint32_t *tabs = ctx->rchk_tabs.buf.as<uint32_t>();
+    uint32_t *flags = ctx->rchk_flags.as<uint32_t>();
+    const sec::RChkSlots sl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
+                            plan.meta.as<uint64_t>(sp.off_toff), flags};
+    const sec::ChkSlots csl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
+                            plan.meta.as<uint32_t>(sp.off_cpos), plan.meta.as<uint32_t>(sp.off_echunk), flags};
+    const bool work = !sp.groups.empty() || sp.ntail || !sp.sha_runs.empty();
+    hipEvent_t t0 = nullptr;
+    if (work)
+        RC(timing_begin(ctx, &t0, s));
+    for (const Group &g : sp.groups) {
+        int e = sec_launch_repair_check(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl,
+                                        s, g.mfma);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_repair_check_kernel");
+    }
+    if (sp.ntail) {
+        int e = sec_launch_repair_check_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs,
+                                             sl, s);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_repair_check_tail");
+    }
+    int e = sec_launch_check_final(blocks, cd, sp.nentries, csl, results, row_bad, column, s);
+    if (e)
+        return hip_fail((hipError_t)e, "sec_check_final");
+    for (const auto &run : sp.sha_runs) {
+        e = sec_launch_sha1(out, out, plan.meta.as<sec::MsgDesc>(sp.off_msgs) + run[0], (uint32_t)run[1],
+                            digests + 20 * run[2], s, sp.sha_split);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_sha1_kernel");
+    }
+    if (work)
+        RC(timing_end(ctx, t0, 7, s));
+    return SEC_OK;
+}
+
 // ---- pinned caller memory: the zero-copy host path ----------------------------
 // A SEC_F_HOST encode / decode whose caller buffers all lie in page-locked host memory the
 // HIP runtime maps at the same address on the device (hipHostMalloc / sec_host_alloc,
@@ -2458,6 +2694,7 @@ void sec_ctx_destroy(sec_ctx *ctx)
     ctx->rep_tabs.buf.release();
     ctx->chk_tabs.buf.release();
     ctx->dchk_tabs.buf.release();
+    ctx->rchk_tabs.buf.release();
     ctx->enc_plan.meta.release();
     ctx->dec_plan.meta.release();
     ctx->sha_plan.meta.release();
@@ -2467,6 +2704,8 @@ void sec_ctx_destroy(sec_ctx *ctx)
     ctx->chk_flags.release();
     ctx->dchk_plan.meta.release();
     ctx->dchk_flags.release();
+    ctx->rchk_plan.meta.release();
+    ctx->rchk_flags.release();
     ctx->bn_scratch.release();
     ctx->bn_part.release();
     ctx->syn.release();
@@ -2517,7 +2756,7 @@ int sec_ctx_set_option(sec_ctx *ctx, const char *name, int64_t value)
     RC(drain_all(ctx));  // nothing in flight may still use a plan or pool built the old way
     ctx->opt.v[i] = value;
     for (Plan *p : {&ctx->enc_plan, &ctx->dec_plan, &ctx->sha_plan, &ctx->bn_plan, &ctx->rep_plan, &ctx->chk_plan,
-                    &ctx->dchk_plan})
+                    &ctx->dchk_plan, &ctx->rchk_plan})
         p->valid = false;
     if (i == O_COPY_THREADS) {
         ctx->tasks.reset();
@@ -2542,7 +2781,7 @@ const char *sec_option_name(int index)
 
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches)
 {
-    if (!ctx || kind < 0 || kind > 6 || !total_ms || !launches)
+    if (!ctx || kind < 0 || kind > 7 || !total_ms || !launches)
         return SEC_EINVAL;
     RC(set_dev(ctx));
     double tot = 0;
@@ -4113,6 +4352,149 @@ int sec_decode_check_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t n
     };
     auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
         return launch_decode_check_sub(ctx, plan, sp, din, dout, (sec::ChkResult *)dout,
+                                       row_bad ? dout + sp.chk_rows : nullptr, column ? dout + sp.chk_col : nullptr, s);
+    };
+    RC(run_pipeline(ctx, plan, gather, scatter, launch));
+    if (column)
+        for (int64_t i = 0; i < nchunks; ++i)
+            if (results[i].first != UINT64_MAX)
+                memcpy(column + chunks[i].slot0, col.data() + chunks[i].slot0, (size_t)chunks[i].n);
+    return SEC_OK;
+}
+
+// ---- repair + check: regenerate lost pieces and check the spare ones in one pass -------------
+int sec_repair_check_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                           const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
+                           const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out, uint8_t *digests,
+                           sec_chk_result *results, uint8_t *row_bad, uint8_t *column, unsigned flags)
+{
+    static_assert(sizeof(sec_rchk_chunk) == 40 && sizeof(sec::RChkDesc) == 40, "ABI layout");
+    if (!ctx || nchunks < 0 || (nchunks > 0 && (!chunks || !sharenums || !block_offs || !results)) ||
+        (flags & ~(SEC_F_HOST | SEC_F_ASYNC)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
+        return SEC_EINVAL;
+    if (nchunks == 0)
+        return SEC_OK;
+    if (nchunks >= (int64_t)UINT32_MAX)
+        return SEC_EINVAL;
+    const bool host = flags & SEC_F_HOST;
+    const bool digest = digests != nullptr;
+    RC(set_dev(ctx));
+
+    // preconditions of every chunk before any device work; SEC_EINVAL's first
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const sec_rchk_chunk &c = chunks[i];
+        if (c.n < 0 || c.ntargets < 0 || (c.ntargets > 0 && (!target_nums || !target_offs)))
+            return SEC_EINVAL;
+    }
+    uint64_t total_slots = 0, total_tgts = 0;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const sec_rchk_chunk &c = chunks[i];
+        RC(check_repair_check(c.k, c.m, sharenums + c.slot0, c.n, c.ntargets ? target_nums + c.tgt0 : nullptr,
+                              c.ntargets));
+        if (c.B >= (1ull << 31))
+            return SEC_ESIZE;
+        total_slots = std::max<uint64_t>(total_slots, c.slot0 + (uint64_t)c.n);
+        if (c.ntargets)
+            total_tgts = std::max<uint64_t>(total_tgts, c.tgt0 + (uint64_t)c.ntargets);
+    }
+    if (total_slots >= UINT32_MAX || total_tgts >= UINT32_MAX)
+        return SEC_EINVAL;
+    // (blocks and out may be NULL: block_offs / target_offs are then absolute addresses)
+
+    // Plan key, as sec_repair_batch's with the check's entries: host mode keys on shapes, sharenums
+    // and targets only (its entries are staged densely, zero-filled past their avail, its targets
+    // dense in the slab); device mode on every descriptor, sharenum, target, address and avail.
+    // The results' addresses are launch arguments, not part of the plan.
+    Plan &plan = ctx->rchk_plan;
+    PlanKey key;
+    if (host) {
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const sec_rchk_chunk &c = chunks[i];
+            key.put(c.B);
+            key.put(c.ntargets);
+            key.put(c.n);
+            key.put(c.k);
+            key.put(c.m);
+            key.put(sharenums + c.slot0, (size_t)c.n * 4);
+            if (c.ntargets)
+                key.put(target_nums + c.tgt0, (size_t)c.ntargets * 4);
+        }
+    } else {
+        key.put(chunks, sizeof(sec_rchk_chunk) * (size_t)nchunks);
+        key.put(sharenums, total_slots * 4);
+        key.put(block_offs, total_slots * 8);
+        if (block_avail)
+            key.put(block_avail, total_slots * 8);
+        if (total_tgts) {
+            key.put(target_nums, total_tgts * 4);
+            key.put(target_offs, total_tgts * 8);
+        }
+    }
+    key.put((host ? SEC_F_HOST : 0u) | (!host && block_avail ? 0x10000u : 0u) | (digest ? 0x20000u : 0u));
+    const bool reuse = plan_reusable(plan, ctx->rchk_tabs, key);
+    SlotLayout L;
+    if (!reuse || host)
+        L = slot_layout(chunks, nchunks, sharenums);
+    if (!reuse) {
+        plan.valid = false;
+        RC(build_repair_check_plan(ctx, chunks, nchunks, sharenums, block_offs, block_avail, target_nums, target_offs,
+                                   L, host, digest));
+        plan.key.swap(key.bytes);
+        plan.valid = true;
+    }
+    // every call starts from clean flag words, whatever the last call on this plan found
+    RC(ctx->rchk_flags.ensure((size_t)plan.nflags * 4));
+    CK(hipMemsetAsync(ctx->rchk_flags.p, 0xFF, (size_t)plan.nflags * 4, ctx->stream()));
+
+    if (!host) {
+        RC(launch_repair_check_sub(ctx, plan, plan.subs[0], blocks, out, digests, (sec::ChkResult *)results, row_bad,
+                                   column, ctx->stream()));
+        if (!(flags & SEC_F_ASYNC))
+            CK(hipStreamSynchronize(ctx->stream()));
+        return SEC_OK;
+    }
+    // Host mode is always staged, as sec_check_batch's: all n entries of a chunk are gathered into
+    // pinned slabs ONCE and feed both the repair and the check; the targets, their digests and the
+    // results come back.  column passes through a buffer of its own so that a consistent chunk's
+    // bytes stay untouched.
+    ++ctx->staged_calls;
+    std::vector<uint8_t> col(column ? (size_t)total_slots : 0);
+    auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        uint64_t o = 0;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const sec_rchk_chunk &c = chunks[i];
+            for (int e = 0; e < c.n; ++e) {
+                const int from = e < c.k ? L.perm[L.first[i] + e] : e;
+                const uint64_t av = slot_avail(c, block_avail, from);
+                jobs.push_back(sec::CopyJob{stage + o, (const void *)((uintptr_t)blocks + block_offs[c.slot0 + from]), av});
+                if (av < c.B)  // the entry's bytes past its avail are zero
+                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
+                o += c.B;
+            }
+        }
+    };
+    auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        jobs.push_back(sec::CopyJob{results + sp.c0, stage, (uint64_t)(sp.c1 - sp.c0) * sizeof(sec_chk_result)});
+        uint64_t o = 0, b = sp.rchk_out, g = sp.dig_off;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const sec_rchk_chunk &c = chunks[i];
+            if (row_bad)
+                jobs.push_back(sec::CopyJob{row_bad + c.slot0, stage + sp.chk_rows + o, (uint64_t)c.n});
+            if (column)
+                jobs.push_back(sec::CopyJob{col.data() + c.slot0, stage + sp.chk_col + o, (uint64_t)c.n});
+            o += (uint64_t)c.n;
+            for (int r = 0; r < c.ntargets; ++r) {
+                jobs.push_back(sec::CopyJob{(void *)((uintptr_t)out + target_offs[c.tgt0 + r]), stage + b, c.B});
+                b += c.B;
+                if (digest) {
+                    jobs.push_back(sec::CopyJob{digests + 20 * (c.tgt0 + (uint64_t)r), stage + g, 20});
+                    g += 20;
+                }
+            }
+        }
+    };
+    auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
+        return launch_repair_check_sub(ctx, plan, sp, din, dout, dout + sp.dig_off, (sec::ChkResult *)dout,
                                        row_bad ? dout + sp.chk_rows : nullptr, column ? dout + sp.chk_col : nullptr, s);
     };
     RC(run_pipeline(ctx, plan, gather, scatter, launch));

@@ -145,6 +145,30 @@ struct DChkSlots {
     uint32_t *flags;        // see ChkDesc::flag0
 };
 
+// One repair + check chunk, device copy (40 B): nt lost blocks regenerated from k basis blocks, each
+// a whole B-byte piece at an address of its own, and nr check rows predicted from the same basis and
+// compared with the stored rows.  Its n = k + nr entries in RChkSlots::off / avail are those of its
+// ChkDesc (the same arrays: sec_check_final writes the results).
+struct RChkDesc {
+    uint32_t B;
+    uint32_t k;
+    uint32_t nt;     // target rows: rows 0 .. nt-1 of the table, stored
+    uint32_t nr;     // check rows: rows nt .. nt+nr-1 of the table, compared
+    uint32_t tab;    // dword offset of tables, layout [slot][row][5]
+    uint32_t slot0;  // first of the n entries
+    uint32_t tgt0;   // first entry in RChkSlots::tgt_off
+    uint32_t flag0;  // as ChkDesc::flag0
+    uint32_t valid;  // positions [0, valid) where all n entries are readable: min(B, every avail)
+    uint32_t pad;
+};
+
+struct RChkSlots {
+    const uint64_t *off;      // block address: blocks + off[entry]
+    const uint32_t *avail;    // bytes of the block that exist in memory; the rest read as zero
+    const uint64_t *tgt_off;  // target address: out + tgt_off[target], any byte alignment
+    uint32_t *flags;          // see ChkDesc::flag0
+};
+
 // One chunk of a syndrome decode (kernels_bs.hip sec_syndrome_bs_kernel, sec_decode_bs_kernel; 56 B).  Block j of
 // the chunk (data j < k, parity row r at j = k + r) is at blocks + off[slot0 + j] with
 // avail[slot0 + j] readable bytes, when its bit in dmask / pmask is set.
@@ -300,6 +324,14 @@ int sec_launch_decode_check(int rows, int U, int wide, int lanes, const uint8_t 
 int sec_launch_decode_check_tail(const uint8_t *blocks, uint8_t *out, const sec::DChkDesc *descs,
                                  const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs,
                                  sec::DChkSlots slots, void *stream);
+// Repair + check (sec_repair_check_kernel): tiles as the repair's over the chunk's nt + nr rows
+// (rows 1..8 of the tile's group, kb as sec_launch_decode); the results by sec_launch_check_final
+int sec_launch_repair_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
+                            const sec::RChkDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
+                            sec::RChkSlots slots, void *stream, int kb = 0);
+int sec_launch_repair_check_tail(const uint8_t *blocks, uint8_t *out, const sec::RChkDesc *descs,
+                                 const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs,
+                                 sec::RChkSlots slots, void *stream);
 // One thread per entry of the launch's chunks: slots.flags into results[d.res], row_bad[d.cslot0 + ..]
 // and, for an inconsistent chunk, column[d.cslot0 + ..] (row_bad, column nullable)
 int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uint32_t nentries, sec::ChkSlots slots,

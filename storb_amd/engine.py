@@ -24,8 +24,8 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (CHK_DTYPE, CHK_RESULT_DTYPE, COPY_DTYPE, DCHK_DTYPE, DEC_DTYPE, ENC_DTYPE, MSG_DTYPE, REP_DTYPE,
-                   SEC_F_ASYNC, SEC_F_GPU_PARITY_IDS, SEC_F_HOST, SEC_F_RECOVER, SEC_F_STAGED)
+from ._lib import (CHK_DTYPE, CHK_RESULT_DTYPE, COPY_DTYPE, DCHK_DTYPE, DEC_DTYPE, ENC_DTYPE, MSG_DTYPE, RCHK_DTYPE,
+                   REP_DTYPE, SEC_F_ASYNC, SEC_F_GPU_PARITY_IDS, SEC_F_HOST, SEC_F_RECOVER, SEC_F_STAGED)
 
 
 class Error(Exception):
@@ -79,7 +79,7 @@ def device_count() -> int:
 
 
 _TIMING_KINDS = {"encode": 0, "decode": 1, "sha1": 2, "bignum": 3, "repair": 4, "check": 5,
-                 "decode_check": 6}
+                 "decode_check": 6, "repair_check": 7}
 
 
 class Engine:
@@ -128,7 +128,8 @@ class Engine:
 
     def collect_timing(self, kind: str) -> tuple[float, int]:
         """(summed kernel ms, launch count) recorded since the last collect;
-        kind 'encode' | 'decode' | 'sha1' | 'bignum' | 'repair' | 'check'."""
+        kind 'encode' | 'decode' | 'sha1' | 'bignum' | 'repair' | 'check' | 'decode_check' |
+        'repair_check'."""
         ms = ctypes.c_double(0)
         n = ctypes.c_int64(0)
         self._check(self.lib.sec_timing_collect(self._ctx, _TIMING_KINDS[kind], ctypes.byref(ms),
@@ -419,6 +420,101 @@ class Engine:
                 checks.append((int(res[j]["first"]), [q for q in range(nb) if rb[s0 + q]],
                                col[s0:s0 + nb].tobytes()))
         return data, checks
+
+    def repair_check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
+                           target_nums: np.ndarray, target_offs: np.ndarray, out, results, *,
+                           block_avail: np.ndarray | None = None, digests=None, row_bad=None, column=None,
+                           host: bool = False, asynchronous: bool = False) -> None:
+        """sec_repair_check_batch: repair_batch from each chunk's first k entries and check_batch
+        on all n of them (RCHK_DTYPE descriptors) in one pass over the blocks.  The targets (and
+        digests) receive what repair_batch writes, consistent or not; results, row_bad and column
+        what check_batch reports.  host: host buffers, always staged, every entry gathered once."""
+        descs = np.ascontiguousarray(descs, dtype=RCHK_DTYPE)
+        sn = np.ascontiguousarray(sharenums, dtype=np.int32)
+        bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
+        tn = np.ascontiguousarray(target_nums, dtype=np.int32)
+        to = np.ascontiguousarray(target_offs, dtype=np.uint64)
+        av = None if block_avail is None else np.ascontiguousarray(block_avail, dtype=np.uint64)
+        if av is not None and av.size < bo.size:
+            raise ValueError("block_avail needs one entry per slot")
+        if tn.size != to.size:
+            raise ValueError("one target address per target")
+        b, _kb = addr(blocks)
+        o, _ko = addr(out)
+        g, _kg = addr(digests)
+        r, _kr = addr(results)
+        rb, _krb = addr(row_bad)
+        co, _kco = addr(column)
+        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
+        self._check(self.lib.sec_repair_check_batch(self._ctx, _ptr(descs), len(descs), _ptr(sn) or None,
+                                                    _ptr(bo) or None, None if av is None else _ptr(av), b or None,
+                                                    _ptr(tn) or None, _ptr(to) or None, o or None, g or None,
+                                                    r or None, rb or None, co or None, flags))
+
+    def repair_check_host(self, items, digests: bool = False):
+        """Lost blocks of host chunks regenerated and their spare blocks checked, in one call.
+
+        items: [(k, m, blocks, sharenums, targets)] with n >= k equal-length blocks per chunk: the
+        first k are repaired from and are the check's basis, the others are the check rows.
+        Returns what ``repair_host`` returns (per chunk the target blocks as bytes in the order of
+        `targets`; with ``digests=True`` also, per chunk, each one's SHA-1 digest) followed by
+        checks = per chunk ``(first, bad, column)`` as ``check_host`` returns them.  One host
+        call stages every block once.  The targets are returned whatever the check says."""
+        from ._hostbytes import _finalize, _new_bytes
+
+        for it in items:
+            check_repair_check_item(*it)
+        n = len(items)
+        if not n:
+            return ([], [], []) if digests else ([], [])
+        descs = np.zeros(n, dtype=RCHK_DTYPE)
+        nslots = sum(len(it[2]) for it in items)
+        ntg = sum(len(it[4]) for it in items)
+        sn = np.zeros(max(nslots, 1), dtype=np.int32)
+        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
+        tn = np.zeros(max(ntg, 1), dtype=np.int32)
+        to = np.zeros(max(ntg, 1), dtype=np.uint64)
+        keep, objs = [], []
+        slot = tgt = 0
+        for j, (k, m, blocks, sharenums, targets) in enumerate(items):
+            B = len(blocks[0])
+            for q, b in enumerate(blocks):
+                a, kp = addr(b)
+                keep.append(kp)
+                bo[slot + q] = a
+                sn[slot + q] = int(sharenums[q])
+            row = []
+            for q, t in enumerate(targets):
+                b, v = _new_bytes(B)
+                row.append(b)
+                tn[tgt + q] = int(t)
+                to[tgt + q] = v.ctypes.data if B else 0
+                keep.append(v)
+            objs.append(row)
+            descs[j] = (B, slot, tgt, len(targets), len(blocks), k, m)
+            slot += len(blocks)
+            tgt += len(targets)
+        dig = np.zeros(max(20 * ntg, 1), dtype=np.uint8) if digests else None
+        res = np.zeros(n, dtype=CHK_RESULT_DTYPE)
+        rb = np.zeros(max(nslots, 1), dtype=np.uint8)
+        col = np.zeros(max(nslots, 1), dtype=np.uint8)
+        self.repair_check_batch(descs, sn, bo, 0, tn, to, 0, res, digests=dig, row_bad=rb, column=col, host=True)
+        out = [[_finalize(b) for b in row] for row in objs]
+        checks = []
+        for j in range(n):
+            s0, nb = int(descs[j]["slot0"]), int(descs[j]["n"])
+            if int(res[j]["first"]) == _lib.CHK_CONSISTENT:
+                checks.append((None, [], None))
+            else:
+                checks.append((int(res[j]["first"]), [q for q in range(nb) if rb[s0 + q]],
+                               col[s0:s0 + nb].tobytes()))
+        if not digests:
+            return out, checks
+        dv, digs, f = memoryview(dig), [], 0
+        for row in out:
+            digs.append([bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(len(row))])
+            f += len(row)
+        return out, digs, checks
 
     def encode_digest_batch(self, descs: np.ndarray, src, parity, digests, *, host: bool = False,
                             asynchronous: bool = False) -> None:
@@ -847,6 +943,27 @@ def check_decode_check_item(k: int, m: int, blocks, sharenums, padlen: int) -> N
     B = len(blocks[0]) if blocks else 0
     if not (0 <= padlen <= k * B):
         raise Error(_lib.strerror(_lib.SEC_EPADLEN))
+
+
+def check_repair_check_item(k: int, m: int, blocks, sharenums, targets) -> None:
+    """The repair + check preconditions for one chunk (the library's own checks, raised before any
+    GPU work): n equal-length blocks and n sharenums, 1 <= k <= m <= 256, k <= n <= m, sharenums
+    and targets in [0, m), all distinct, no target among the blocks held.  Raises Error."""
+    if len(blocks) != len(sharenums):
+        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
+    B = len(blocks[0]) if blocks else 0
+    for b in blocks:
+        if len(b) != B:
+            raise Error(_lib.strerror(_lib.SEC_EBLOCKLEN))
+    if not (1 <= k <= m <= 256):
+        raise Error(_lib.strerror(_lib.SEC_EKM))
+    if not (k <= len(blocks) <= m):
+        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
+    sn, tg = [int(x) for x in sharenums], [int(x) for x in targets]
+    if any(x < 0 or x >= m for x in sn + tg):
+        raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
+    if len(set(sn + tg)) != len(sn) + len(tg):
+        raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
 
 
 # -- matrices (host arithmetic; no device needed) ------------------------------

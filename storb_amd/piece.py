@@ -29,6 +29,9 @@ Deliberate differences (documented in DESIGN.md §Boundary):
 * ``decode_chunks_checked`` / ``reconstruct_data_checked`` (no reference counterpart) reassemble
   the chunks and run that check in the same pass over the pieces: a download verified by the code
   word itself, where the validator hashes every fetched piece on one core (validator.py:1556-1604).
+* ``repair_chunks_checked`` / ``repair_pieces_checked`` (no reference counterpart) regenerate lost
+  pieces and run that check on every surviving piece in the same pass: a corrupt survivor is
+  found, and named, before it is turned into new pieces.
 * ``reconstruct_data_stream`` decodes window w+1 on a worker thread (its own HIP context)
   while the caller consumes window w's chunks; ``encode_chunks_stream`` does the same for the
   upload loop's produce/consume pattern (validator.py:1338-1446, 1630-1638).
@@ -63,8 +66,8 @@ from pydantic import BaseModel, ConfigDict, Field
 
 from .constants import MAX_PIECE_SIZE, MIN_PIECE_SIZE, PIECE_LENGTH_OFFSET, PIECE_LENGTH_SCALING
 from .easyfec import Decoder, Encoder, Error
-from .engine import (EngineGroup, check_decode_check_item, check_decode_item, check_locate, choose_blocks, device_count,
-                     get_engine, spread_threads)
+from .engine import (EngineGroup, check_decode_check_item, check_decode_item, check_locate, check_repair_check_item,
+                     choose_blocks, device_count, get_engine, spread_threads)
 
 logger = logging.getLogger(__name__)
 
@@ -73,7 +76,8 @@ __all__ = [
     "encode_chunk", "decode_chunk", "reconstruct_data", "reconstruct_data_stream", "encode_chunks",
     "decode_chunks", "chunk_shape", "piece_hashes", "encode_chunks_with_ids", "encode_chunks_stream", "Encoder",
     "Decoder", "Error", "use_devices", "repair_chunks", "repair_pieces", "ChunkCheck", "check_chunks", "check_pieces",
-    "decode_chunks_checked", "reconstruct_data_checked", "PieceCheckError",
+    "decode_chunks_checked", "reconstruct_data_checked", "PieceCheckError", "repair_chunks_checked",
+    "repair_pieces_checked",
 ]
 
 PREFETCH_PIECE_IDS = True  # encode_chunk hashes its pieces on a thread pool (see module doc)
@@ -931,6 +935,87 @@ def decode_chunks_checked(encoded_chunks: typing.Sequence[EncodedChunk], *,
         at = starts[i + 1]
     parts.append(view[at:])
     return b"".join(parts), out
+
+
+def repair_chunks_checked(chunks: typing.Sequence[EncodedChunk], targets=None, *, piece_ids: bool = False,
+                          locate: bool = True) -> tuple[list[list[Piece]], list[ChunkCheck]]:
+    """``repair_chunks`` and ``check_chunks`` in one pass over the surviving pieces: per chunk the
+    regenerated pieces, and what the code word says about the pieces they were made from.
+
+    Every distinct piece held of a chunk is used, ordered as ``check_chunks`` orders them:
+    ``choose_blocks``' pick is repaired from and predicts the others, which are compared with what
+    is held; ONE fused GPU call reads each piece once (``Engine.repair_check_host``).  targets: as
+    ``repair_chunks``' (default: every absent ``piece_idx``); ``piece_ids`` as there.  Chunks
+    reported inconsistent go on through ``check_chunks``' rounds (locate, re-check without the
+    named piece, in batches); those that end up ``located`` are repaired again from the pieces
+    that passed, all in one ``repair_host`` call, which regenerates the requested targets followed
+    by the pieces named in ``bad_piece_idx``, in the order named: the caller then holds a full
+    healthy set.
+
+    The pieces of a chunk are trustworthy exactly when its ``ChunkCheck`` is ``consistent or
+    located``; otherwise they are what its first k pieces give, corrupt piece included.  What
+    "trustworthy" means: corruption confined to at most n - k of a chunk's n held pieces is always
+    detected, and a chunk with exactly k pieces is not checked at all; more than n - k pieces
+    altered together can form another code word, which only the recorded piece ids exclude.
+    ``devices=`` / ``EngineGroup`` splitting is not provided: one device, one call.
+    ``repair_chunks`` is unchanged."""
+    chunks = list(chunks)
+    if targets is not None and len(targets) != len(chunks):
+        raise ValueError("repair_chunks_checked: one target list (or None) per chunk")
+    out: list[ChunkCheck] = []
+    held: list[list[Piece]] = []
+    items, tgs = [], []
+    for i, ch in enumerate(chunks):
+        use = _held_pieces(ch, "repair")
+        held.append(use)
+        out.append(ChunkCheck(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
+        items.append(_check_item(ch, use))
+        tg = targets[i] if targets is not None and targets[i] is not None else None
+        if tg is None:
+            have = {p.piece_idx for p in use}
+            tg = [t for t in range(ch.m) if t not in have]
+        tgs.append([int(t) for t in tg])
+    if not chunks:
+        return [], []
+    full = [it + (tg,) for it, tg in zip(items, tgs)]
+    for it in full:  # every chunk's preconditions before any device work
+        check_repair_check_item(*it)
+    res = get_engine().repair_check_host(full, digests=piece_ids)
+    blocks, digs, checks = res if piece_ids else (res[0], None, res[1])
+    _check_rounds(chunks, held, out, locate, first=(items, checks))
+    redo = [i for i, ck in enumerate(out) if ck.located]
+    if redo:
+        again = []
+        for i in redo:  # from the pieces that passed the last re-check
+            k, m, blks, sharenums = _check_item(chunks[i], held[i])
+            tgs[i] = tgs[i] + [b for b in out[i].bad_piece_idx if b not in tgs[i]]
+            again.append((k, m, blks[:k], sharenums[:k], tgs[i]))
+        fixed = get_engine().repair_host(again, digests=piece_ids)
+        fblocks, fdigs = fixed if piece_ids else (fixed, None)
+        for j, i in enumerate(redo):
+            blocks[i] = fblocks[j]
+            if piece_ids:
+                digs[i] = fdigs[j]
+    pieces = []
+    for i, ch in enumerate(chunks):
+        row = []
+        for j, t in enumerate(tgs[i]):
+            kind = PieceType.Data if t < ch.k else PieceType.Parity
+            if piece_ids:
+                row.append(ProcessedPieceInfo(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind,
+                                              data=blocks[i][j], piece_id=digs[i][j].hex()))
+            else:
+                row.append(Piece(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind, data=blocks[i][j]))
+        pieces.append(row)
+    return pieces, out
+
+
+def repair_pieces_checked(chunk: EncodedChunk, targets=None, *, piece_ids: bool = False,
+                          locate: bool = True) -> tuple[list[Piece], ChunkCheck]:
+    """``repair_chunks_checked`` for one chunk."""
+    pieces, checks = repair_chunks_checked([chunk], None if targets is None else [targets], piece_ids=piece_ids,
+                                           locate=locate)
+    return pieces[0], checks[0]
 
 
 def reconstruct_data_checked(pieces: list[Piece], chunks: list[EncodedChunk]) -> tuple[bytes, list[ChunkCheck]]:
