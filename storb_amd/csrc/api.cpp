@@ -26,6 +26,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -292,14 +293,15 @@ struct SubPlan {
     uint32_t nsegs = 0, max_seg = 0;       // segment count; most segments of one message
     uint64_t dig_first = 0;                // first digest slot of this unit
     uint64_t dig_off = 0;                  // host mode: digests' offset in the slab output
-    size_t off_toff = 0;                   // repair: the targets' addresses (RepSlots::tgt_off)
-    size_t off_cpos = 0, off_echunk = 0;   // check: the entries' caller positions and chunks (ChkSlots)
-    uint32_t nentries = 0;                 // check: entries of the unit's chunks
-    uint64_t chk_rows = 0, chk_col = 0;    // check, host mode: row_bad and column in the slab output
-    size_t off_cdesc = 0;                  // decode + check: the chunks' ChkDesc (sec_check_final)
-    uint64_t dchk_out = 0;                 // decode + check, host mode: the decoded bytes in the slab output
-    uint64_t rchk_out = 0;                 // repair + check, host mode: the targets in the slab output
-    // repair digests: runs of consecutive digest slots, (first message, count, first slot)
+    // row operations (build_row_plan)
+    size_t off_toff = 0;                   // the targets' addresses (RepSlots / RChkSlots::tgt_off)
+    size_t off_cpos = 0, off_echunk = 0;   // the entries' caller positions and chunks (ChkSlots)
+    uint32_t nentries = 0;                 // entries of the unit's chunks (operations with compared rows)
+    size_t off_cdesc = 0;                  // the chunks' ChkDesc (sec_check_final)
+    // host mode's slab output: the results at 0, then row_bad and column, then the stored rows
+    // (targets or decoded bytes), then the digests (dig_off)
+    uint64_t chk_rows = 0, chk_col = 0, pay_off = 0;
+    // digests of targets: runs of consecutive digest slots, (first message, count, first slot)
     std::vector<std::array<uint64_t, 3>> sha_runs;
     // syndrome decodes (decode): phase 1 launches (bit-sliced syndromes) and phase 2 launches
     // (the Cauchy solve), one each per shape
@@ -328,6 +330,14 @@ struct TableCache {
     size_t used = 0;  // dwords
     uint64_t gen = 1;
     std::map<std::string, uint32_t> index;
+};
+
+// What a row operation (repair, check, decode + check, repair + check) keeps between calls: none
+// of it is shared with another operation
+struct RowOpState {
+    Plan plan;
+    TableCache tabs;
+    DevBuf flags;  // the flag words of the call in flight (ChkDesc::flag0)
 };
 
 struct PendingExpand {
@@ -685,11 +695,9 @@ struct sec_ctx {
     hipEvent_t stop_ev = nullptr;  // between timing_begin and timing_end of an attached launch
     PinBuf pin{nullptr, 0, false};  // metadata image staging (its own, not pooled: small, every call)
     hipEvent_t pin_ev = nullptr, meta_ev = nullptr;
-    TableCache enc_tabs, dec_tabs, rep_tabs, chk_tabs, dchk_tabs, rchk_tabs;
-    Plan enc_plan, dec_plan, sha_plan, bn_plan, rep_plan, chk_plan, dchk_plan, rchk_plan;
-    DevBuf chk_flags;   // check: the flag words of the call in flight (ChkDesc::flag0)
-    DevBuf dchk_flags;  // decode + check: likewise
-    DevBuf rchk_flags;  // repair + check: likewise
+    TableCache enc_tabs, dec_tabs;
+    Plan enc_plan, dec_plan, sha_plan, bn_plan;
+    RowOpState row_ops[4];  // repair, check, decode + check, repair + check (by their Op::kId)
     DevBuf bn_scratch;  // host-mode staging of sec_bn_modexp / mulmod operands
     DevBuf bn_part;     // partial residues of segmented reductions (one region per slot)
     DevBuf syn;         // syndrome rows of device-mode syndrome decodes
@@ -835,7 +843,7 @@ void drop_pending(TableCache &tc, const std::vector<PendingExpand> &pending)
     tc.used = first;
 }
 
-// The tables of a batch's chunks (the three plan builders): tab_of[i] = dword offset of chunk i's
+// The tables of a batch's chunks (every plan builder): tab_of[i] = dword offset of chunk i's
 // tables in the cache, `pending` = the tables that are new, for upload_plan to expand.
 //   want(i, key): 0 when chunk i needs no table, else its coefficient count, with the table's
 //                 cache key (matrix identity) in `key`
@@ -993,26 +1001,36 @@ int check_sharenums(int k, int m, const int32_t *s)
     return SEC_OK;
 }
 
-// Preconditions of a repair (sec_repair_matrix, sec_repair_batch): k distinct sources and nt
-// distinct targets in [0, m), no target among the sources (repair never copies a block the
-// caller already holds).
-int check_repair(int k, int m, const int32_t *sources, const int32_t *targets, int nt)
+// Preconditions of "n held blocks plus nt targets" of a (k, m) code: every number in [0, m) and no
+// two alike (a target is never a block the caller already holds).
+//   in_turn (repair, sec_repair_matrix, sec_check_locate: n is k): each number is judged in its
+//     turn, range then duplicate, as zfec judges sharenums;
+//   else (the check family): k <= n <= m, and every range error comes before any duplicate.
+int check_blocks(int k, int m, const int32_t *held, int n, const int32_t *targets, int nt, bool in_turn)
 {
-    if (nt < 0 || !sources || (nt > 0 && !targets))
+    if (nt < 0 || !held || (nt > 0 && !targets) || (!in_turn && n < 0))
         return SEC_EINVAL;
     if (k < 1 || m < k || m > 256)
         return SEC_EKM;
-    RC(check_sharenums(k, m, sources));
+    if (!in_turn && (n < k || n > m))
+        return SEC_ENBLOCKS;
+    const int32_t *nums[2] = {held, targets};
+    const int count[2] = {n, nt};
+    if (!in_turn)
+        for (int a = 0; a < 2; ++a)
+            for (int i = 0; i < count[a]; ++i)
+                if (nums[a][i] < 0 || nums[a][i] >= m)
+                    return SEC_ESHARENUM;
     bool seen[256] = {false};
-    for (int i = 0; i < k; ++i)
-        seen[sources[i]] = true;
-    for (int i = 0; i < nt; ++i) {
-        if (targets[i] < 0 || targets[i] >= m)
-            return SEC_ESHARENUM;
-        if (seen[targets[i]])
-            return SEC_EDUPSHARE;
-        seen[targets[i]] = true;
-    }
+    for (int a = 0; a < 2; ++a)
+        for (int i = 0; i < count[a]; ++i) {
+            const int b = nums[a][i];
+            if (in_turn && (b < 0 || b >= m))
+                return SEC_ESHARENUM;
+            if (seen[b])
+                return SEC_EDUPSHARE;
+            seen[b] = true;
+        }
     return SEC_OK;
 }
 
@@ -1535,14 +1553,13 @@ int launch_decode_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
                            plan.meta.as<uint32_t>(sp.off_mrow), plan.meta.as<uint32_t>(sp.off_savail)};
     for (const Group &g : sp.groups) {
         // decode groups: the bin kind is the small-batch variant's batch (or 0)
-        int e = sec_launch_decode(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
-                                  g.mfma);
+        int e = sec_launch_rows(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
+                                g.mfma);
         if (e)
             return hip_fail((hipError_t)e, "sec_decode_kernel");
     }
     if (sp.ntail) {
-        int e = sec_launch_decode_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs,
-                                       sl, s);
+        int e = sec_launch_rows_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
         if (e)
             return hip_fail((hipError_t)e, "sec_decode_tail");
     }
@@ -1585,84 +1602,347 @@ int launch_decode_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
     return SEC_OK;
 }
 
-// ---- repair plan --------------------------------------------------------------
-// A sibling of the decode plan's direct branch: no syndrome choice and no copies.  Per chunk the
-// repair matrix's tables (layout [slot][target][5], cached by sources and targets), the k slots
-// in normalised order, one address per target, tiles as a copy-free decode's (add_work), and one
-// SHA-1 message per target when digests are asked for.
-int build_repair_plan(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks, const uint64_t *block_offs,
-                      const uint64_t *block_avail, const int32_t *target_nums, const uint64_t *target_offs,
-                      const SlotLayout &L, bool host, bool digest)
+// ---- row operations: repair, check, decode + check, repair + check -----------------------------
+// The four operations share one plan builder, one launch unit and one entry skeleton (row_op).
+// Each computes rows of the repair matrix over a basis of k held blocks (the first k, in normalised
+// order) and either stores a row or compares it with a held block:
+//                    held entries   stored rows                         compared rows    digests
+//   repair           k              targets, at caller addresses        none             optional
+//   check            n              none                                entries k..n-1   no
+//   decode + check   n              missing primaries, ascending,       entries k..n-1   no
+//                                   into the reassembled chunk
+//   repair + check   n              targets, at caller addresses        entries k..n-1   optional
+// What differs is held in a traits struct per operation (RepairOp .. RepairCheckOp): the ABI chunk
+// and its RowChunk view, the device descriptor and slots the tile kernels take, the order of its
+// precondition errors (screen_first over the whole batch, then screen chunk by chunk), and its timing
+// kind.
+
+// A chunk of any of the four, in common terms (fields an operation lacks are 0)
+struct RowChunk {
+    uint64_t B, slot0, tgt0, out_off, padlen;
+    int k, m;
+    int n;   // held entries (repair: k)
+    int nt;  // targets
+};
+
+// The arguments of the four entry points (those an operation lacks are NULL)
+struct RowArgs {
+    const int32_t *sharenums;
+    const uint64_t *block_offs, *block_avail;
+    const uint8_t *blocks;
+    const int32_t *target_nums;
+    const uint64_t *target_offs;
+    uint8_t *out, *digests;
+    sec_chk_result *results;
+    uint8_t *row_bad, *column;
+    unsigned flags;
+};
+
+// What a descriptor is made from
+struct RowInfo {
+    uint32_t B, k, ns, nr, tab, slot0, tgt0, flag0, valid;  // ns stored rows, nr compared rows
+    uint64_t out_off, nout;                                 // decode + check: the chunk's output
+};
+
+sec::ChkDesc chk_desc(const RowInfo &r, uint32_t res, uint32_t cslot0)
 {
-    Plan &plan = ctx->rep_plan;
-    TableCache &tc = ctx->rep_tabs;
+    return {r.B, r.k, r.nr, r.tab, r.slot0, r.flag0, r.valid, res, cslot0, 0};
+}
+
+// Preconditions of a check (sec_check_batch), and of the held blocks of the others
+int check_held(const RowChunk &c, const RowArgs &a, const int32_t *targets = nullptr)
+{
+    return check_blocks(c.k, c.m, a.sharenums + c.slot0, c.n, targets, c.nt, false);
+}
+
+struct RepairOp {
+    using Chunk = sec_rep_chunk;
+    using Desc = sec::RepDesc;
+    using Slots = sec::RepSlots;
+    static constexpr int kId = 0, kTiming = 4;
+    static constexpr bool kChecks = false, kStores = true, kTargets = true, kDecodes = false;
+    static constexpr const char *kTile = "sec_repair_kernel", *kTail = "sec_repair_tail";
+    static RowChunk view(const Chunk &c) { return {c.B, c.slot0, c.tgt0, 0, 0, c.k, c.m, c.k, c.ntargets}; }
+    static Desc desc(const RowInfo &r, uint32_t, uint32_t) { return {r.B, r.k, r.ns, r.tab, r.slot0, r.tgt0, r.valid, 0}; }
+    static Slots slots(const DevBuf &m, const SubPlan &sp, uint32_t *)
+    {
+        return {m.as<uint64_t>(sp.off_soff), m.as<uint32_t>(sp.off_savail), m.as<uint64_t>(sp.off_toff)};
+    }
+    static int screen_first(const Chunk *, int64_t, const RowArgs &) { return SEC_OK; }
+    // sec_repair_matrix's preconditions
+    static int screen(const Chunk &c, const RowArgs &a)
+    {
+        if (c.ntargets < 0 || (c.ntargets > 0 && (!a.target_nums || !a.target_offs)))
+            return SEC_EINVAL;
+        if (c.k < 1 || c.m < c.k || c.m > 256)
+            return SEC_EKM;
+        RC(check_blocks(c.k, c.m, a.sharenums + c.slot0, c.k, c.ntargets ? a.target_nums + c.tgt0 : nullptr,
+                        c.ntargets, true));
+        return c.B >= (1ull << 31) ? SEC_ESIZE : SEC_OK;
+    }
+};
+
+struct CheckOp {
+    using Chunk = sec_chk_chunk;
+    using Desc = sec::ChkDesc;
+    using Slots = sec::ChkSlots;
+    static constexpr int kId = 1, kTiming = 5;
+    static constexpr bool kChecks = true, kStores = false, kTargets = false, kDecodes = false;
+    static constexpr const char *kTile = "sec_check_kernel", *kTail = "sec_check_tail";
+    static RowChunk view(const Chunk &c) { return {c.B, c.slot0, 0, 0, 0, c.k, c.m, c.n, 0}; }
+    static Desc desc(const RowInfo &r, uint32_t res, uint32_t cslot0) { return chk_desc(r, res, cslot0); }
+    static Slots slots(const DevBuf &m, const SubPlan &sp, uint32_t *flags)
+    {
+        return {m.as<uint64_t>(sp.off_soff), m.as<uint32_t>(sp.off_savail), m.as<uint32_t>(sp.off_cpos),
+                m.as<uint32_t>(sp.off_echunk), flags};
+    }
+    static int screen_first(const Chunk *, int64_t, const RowArgs &) { return SEC_OK; }
+    static int screen(const Chunk &c, const RowArgs &a)
+    {
+        RC(check_held(view(c), a));
+        return c.B >= (1ull << 31) ? SEC_ESIZE : SEC_OK;
+    }
+};
+
+struct DecodeCheckOp {
+    using Chunk = sec_dchk_chunk;
+    using Desc = sec::DChkDesc;
+    using Slots = sec::DChkSlots;
+    static constexpr int kId = 2, kTiming = 6;
+    static constexpr bool kChecks = true, kStores = true, kTargets = false, kDecodes = true;
+    static constexpr const char *kTile = "sec_decode_check_kernel", *kTail = "sec_decode_check_tail";
+    static RowChunk view(const Chunk &c) { return {c.B, c.slot0, 0, c.out_off, c.padlen, c.k, c.m, c.n, 0}; }
+    static Desc desc(const RowInfo &r, uint32_t, uint32_t)
+    {
+        return {r.out_off, r.nout, r.B, r.k, r.ns, r.nr, r.tab, r.slot0, r.flag0, r.valid};
+    }
+    static Slots slots(const DevBuf &m, const SubPlan &sp, uint32_t *flags)
+    {
+        return {m.as<uint64_t>(sp.off_soff), m.as<uint32_t>(sp.off_savail), m.as<uint32_t>(sp.off_srow),
+                m.as<uint32_t>(sp.off_mrow), flags};
+    }
+    // SEC_EINVAL's first: n < 0, and a NULL `out` where a chunk has bytes to write (judged only
+    // where the chunk's k sharenums can be read)
+    static int screen_first(const Chunk *chunks, int64_t nchunks, const RowArgs &a)
+    {
+        const bool recover = a.flags & SEC_F_RECOVER;
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const Chunk &c = chunks[i];
+            if (c.n < 0)
+                return SEC_EINVAL;
+            if (a.out || c.k < 1 || c.k > 256 || c.n < c.k || c.B == 0)
+                continue;
+            if (!recover && (uint64_t)c.k * c.B > c.padlen)
+                return SEC_EINVAL;
+            for (int j = 0; recover && j < c.k; ++j)
+                if (a.sharenums[c.slot0 + j] < 0 || a.sharenums[c.slot0 + j] >= c.k)
+                    return SEC_EINVAL;  // a basis entry that is no primary: a primary is recovered
+        }
+        return SEC_OK;
+    }
+    static int screen(const Chunk &c, const RowArgs &a)
+    {
+        RC(check_held(view(c), a));
+        if (c.padlen > (uint64_t)c.k * c.B)
+            return SEC_EPADLEN;
+        return c.B >= (1ull << 31) ? SEC_ESIZE : SEC_OK;
+    }
+};
+
+struct RepairCheckOp {
+    using Chunk = sec_rchk_chunk;
+    using Desc = sec::RChkDesc;
+    using Slots = sec::RChkSlots;
+    static constexpr int kId = 3, kTiming = 7;
+    static constexpr bool kChecks = true, kStores = true, kTargets = true, kDecodes = false;
+    static constexpr const char *kTile = "sec_repair_check_kernel", *kTail = "sec_repair_check_tail";
+    static RowChunk view(const Chunk &c) { return {c.B, c.slot0, c.tgt0, 0, 0, c.k, c.m, c.n, c.ntargets}; }
+    static Desc desc(const RowInfo &r, uint32_t, uint32_t)
+    {
+        return {r.B, r.k, r.ns, r.nr, r.tab, r.slot0, r.tgt0, r.flag0, r.valid, 0};
+    }
+    static Slots slots(const DevBuf &m, const SubPlan &sp, uint32_t *flags)
+    {
+        return {m.as<uint64_t>(sp.off_soff), m.as<uint32_t>(sp.off_savail), m.as<uint64_t>(sp.off_toff), flags};
+    }
+    // SEC_EINVAL's of every chunk first
+    static int screen_first(const Chunk *chunks, int64_t nchunks, const RowArgs &a)
+    {
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const Chunk &c = chunks[i];
+            if (c.n < 0 || c.ntargets < 0 || (c.ntargets > 0 && (!a.target_nums || !a.target_offs)))
+                return SEC_EINVAL;
+        }
+        return SEC_OK;
+    }
+    // then the held blocks' and the targets': in [0, m), distinct, no target held
+    static int screen(const Chunk &c, const RowArgs &a)
+    {
+        RC(check_held(view(c), a, c.ntargets ? a.target_nums + c.tgt0 : nullptr));
+        return c.B >= (1ull << 31) ? SEC_ESIZE : SEC_OK;
+    }
+};
+
+// The cache key of the table of the blocks `rows` over the k blocks idx[0..k) (a table's contents
+// depend on nothing else)
+std::string rows_key(int k, int m, const int *idx, const std::vector<int> &rows)
+{
+    std::string key = slots_key(k, m, idx) + "|";
+    for (int r : rows)
+        key += std::to_string(r) + ",";
+    return key;
+}
+
+// That table's coefficients: the repair matrix, transposed to [slot][row]
+int rows_coef(int k, int m, const int *idx, const std::vector<int> &rows, std::vector<uint8_t> &cf)
+{
+    std::vector<uint8_t> rm;
+    if (!sec::repair_matrix(k, m, std::vector<int>(idx, idx + k), rows, rm))
+        return SEC_ESINGULAR;
+    const size_t nr = rows.size();
+    cf.resize((size_t)k * nr);
+    for (int s = 0; s < k; ++s)
+        for (size_t r = 0; r < nr; ++r)
+            cf[(size_t)s * nr + r] = rm[r * k + s];
+    return SEC_OK;
+}
+
+// The caller position of entry e of a chunk: the basis in normalised order, then the caller's
+int entry_from(const SlotLayout &L, int64_t i, int k, int e) { return e < k ? L.perm[L.first[i] + e] : e; }
+
+// Per chunk: the table of its stored rows, then its compared rows, over its basis (layout
+// [slot][row][5]); its held entries (the basis in normalised order, then the compared rows in the
+// caller's); tiles as a copy-free decode's (add_work) over all its rows and [0, valid), valid = the
+// least avail of its entries (decode + check: and no more than the last output row's length,
+// unless recover-only); with compared rows, its flag words (one for the first differing position,
+// one per compared row: ChkDesc::flag0) and a ChkDesc for sec_check_final; with targets, one address
+// per target and, when digests are asked for, one SHA-1 message.  Host mode stages all held entries
+// densely and returns through the slab output the results, row_bad and column (one byte per entry
+// each), then from a 256-aligned offset the stored rows, then the digests.
+template <class Op>
+int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, const RowArgs &a,
+                   const SlotLayout &L, bool host)
+{
+    using Desc = typename Op::Desc;
+    constexpr bool separate_cdesc = Op::kChecks && !std::is_same<Desc, sec::ChkDesc>::value;
+    Plan &plan = ctx->row_ops[Op::kId].plan;
+    TableCache &tc = ctx->row_ops[Op::kId].tabs;
+    const bool recover = a.flags & SEC_F_RECOVER, digest = a.digests != nullptr;
     std::vector<PendingExpand> pending;
-    std::vector<uint32_t> tab_of;
+    std::vector<uint32_t> tab_of, ns_of((size_t)nchunks, 0);
+    std::vector<int> rows;
+    auto rows_of = [&](int64_t i) {  // -> rows; ns_of[i] = how many of them are stored
+        const RowChunk c = Op::view(chunks[i]);
+        const int *idx = &L.idx[L.first[i]];
+        rows.clear();
+        if (Op::kDecodes) {
+            for (int s = 0; s < c.k; ++s)  // normalised slot s holds primary s, or stands in for it
+                if (idx[s] >= c.k)
+                    rows.push_back(s);
+        } else if (c.nt) {
+            rows.assign(a.target_nums + c.tgt0, a.target_nums + c.tgt0 + c.nt);
+        }
+        ns_of[i] = (uint32_t)rows.size();
+        rows.insert(rows.end(), a.sharenums + c.slot0 + c.k, a.sharenums + c.slot0 + c.n);
+        return idx;
+    };
     auto want = [&](int64_t i, std::string &key) -> size_t {
-        const sec_rep_chunk &c = chunks[i];
-        if (c.ntargets == 0)
+        const int *idx = rows_of(i);
+        if (rows.empty())
             return 0;
-        key = slots_key(c.k, c.m, &L.idx[L.first[i]]) + "|";
-        for (int r = 0; r < c.ntargets; ++r)
-            key += std::to_string(target_nums[c.tgt0 + r]) + ",";
-        return (size_t)c.k * c.ntargets;
+        key = rows_key(chunks[i].k, chunks[i].m, idx, rows);
+        return (size_t)chunks[i].k * rows.size();
     };
     auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
-        const sec_rep_chunk &c = chunks[i];
-        const int k = c.k, nt = c.ntargets;
-        const int *idx = &L.idx[L.first[i]];
-        std::vector<uint8_t> rm;
-        if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k),
-                                std::vector<int>(target_nums + c.tgt0, target_nums + c.tgt0 + nt), rm))
-            return (int)SEC_ESINGULAR;
-        cf.resize((size_t)k * nt);
-        for (int s = 0; s < k; ++s)
-            for (int r = 0; r < nt; ++r)
-                cf[(size_t)s * nt + r] = rm[(size_t)r * k + s];
-        return (int)SEC_OK;
+        const int *idx = rows_of(i);
+        return rows_coef(chunks[i].k, chunks[i].m, idx, rows, cf);
     };
     RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
 
     // with digests few large slabs, as the encode's digest mode (one SHA-1 chain per piece)
-    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return (uint64_t)chunks[i].k * chunks[i].B; },
-                                    (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
+    const auto ranges = slab_ranges(
+        host, nchunks, [&](int64_t i) { return (uint64_t)Op::view(chunks[i]).n * chunks[i].B; },
+        (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
     Image img;
     plan.subs.clear();
+    plan.nflags = 0;
     for (auto [c0, c1] : ranges) {
         SubPlan sp;
         sp.c0 = c0;
         sp.c1 = c1;
-        std::vector<sec::RepDesc> descs((size_t)(c1 - c0));
+        std::vector<Desc> descs((size_t)(c1 - c0));
+        std::vector<sec::ChkDesc> cdescs(separate_cdesc ? (size_t)(c1 - c0) : 0);
         std::vector<uint64_t> soff, toff;
-        std::vector<uint32_t> savail;
+        std::vector<uint32_t> savail, cpos, echunk, srow, mrow;
         std::vector<sec::MsgDesc> msgs;
         Bins bins;
         std::vector<sec::TailItem> tail;
+        uint64_t nent = 0;
+        if (Op::kChecks) {
+            for (int64_t i = c0; i < c1; ++i)
+                nent += (uint64_t)Op::view(chunks[i]).n;
+            sp.chk_rows = (uint64_t)(c1 - c0) * sizeof(sec::ChkResult);
+            sp.chk_col = sp.chk_rows + nent;
+            sp.pay_off = align_up(sp.chk_col + nent, 256);
+        }
+        sp.out_bytes = Op::kStores ? sp.pay_off : sp.chk_col + nent;
         for (int64_t i = c0; i < c1; ++i) {
-            const sec_rep_chunk &c = chunks[i];
-            const uint64_t base = L.first[i];
-            sec::RepDesc &d = descs[i - c0];
-            d.B = (uint32_t)c.B;
-            d.k = (uint32_t)c.k;
-            d.nt = (uint32_t)c.ntargets;
-            d.tab = tab_of[i];
-            d.slot0 = (uint32_t)soff.size();
-            d.tgt0 = (uint32_t)toff.size();
-            d.pad = 0;
+            const RowChunk c = Op::view(chunks[i]);
+            const int *idx = &L.idx[L.first[i]];
+            RowInfo r{};
+            r.B = (uint32_t)c.B;
+            r.k = (uint32_t)c.k;
+            r.ns = ns_of[i];
+            r.nr = (uint32_t)(c.n - c.k);
+            r.tab = tab_of[i];
+            r.slot0 = (uint32_t)soff.size();
+            r.tgt0 = (uint32_t)toff.size();
+            r.flag0 = (uint32_t)plan.nflags;
             uint64_t min_avail = c.B;
-            for (int s = 0; s < c.k; ++s) {
-                const int from = L.perm[base + s];
-                soff.push_back(host ? sp.in_bytes + (uint64_t)s * c.B : block_offs[c.slot0 + from]);
-                const uint64_t av = host ? c.B : slot_avail(c, block_avail, from);  // staged slots are zero-filled
+            for (int e = 0; e < c.n; ++e) {
+                const int from = entry_from(L, i, c.k, e);
+                soff.push_back(host ? sp.in_bytes + (uint64_t)e * c.B : a.block_offs[c.slot0 + from]);
+                const uint64_t av = host ? c.B : slot_avail(c, a.block_avail, from);  // staged entries are zero-filled
                 savail.push_back((uint32_t)av);
                 min_avail = std::min(min_avail, av);
+                if (Op::kChecks) {
+                    cpos.push_back((uint32_t)from);
+                    echunk.push_back((uint32_t)(i - c0));
+                }
             }
-            d.valid = (uint32_t)min_avail;
-            for (int r = 0; r < c.ntargets; ++r) {
-                const uint64_t to = host ? sp.out_bytes + (uint64_t)r * c.B : target_offs[c.tgt0 + r];
+            int64_t valid = (int64_t)min_avail;
+            uint64_t nstore = (uint64_t)c.nt * c.B;
+            if (Op::kDecodes) {
+                // the present primaries' output rows and the recovered rows' (recover-only: no
+                // copies, and recovered row r goes to output row r)
+                const size_t m0 = mrow.size();
+                mrow.resize(m0 + (size_t)c.n, 0);
+                srow.resize(m0 + (size_t)c.n, 0xFFFFFFFFu);
+                for (int e = 0, q = 0; e < c.k; ++e) {
+                    if (idx[e] >= c.k) {
+                        mrow[m0 + q] = (uint32_t)(recover ? q : e);
+                        ++q;
+                    } else if (!recover) {
+                        srow[m0 + e] = (uint32_t)idx[e];
+                    }
+                }
+                nstore = r.nout = recover ? (uint64_t)r.ns * c.B : (uint64_t)c.k * c.B - c.padlen;
+                r.out_off = host ? sp.out_bytes : c.out_off;
+                valid = std::max<int64_t>(
+                    0, std::min<int64_t>(recover ? (int64_t)c.B : (int64_t)r.nout - (int64_t)(c.k - 1) * (int64_t)c.B,
+                                         valid));
+            }
+            r.valid = (uint32_t)valid;
+            descs[i - c0] = Op::desc(r, (uint32_t)(host ? i - c0 : i), (uint32_t)(host ? r.slot0 : c.slot0));
+            if (separate_cdesc)
+                cdescs[i - c0] = chk_desc(r, (uint32_t)(host ? i - c0 : i), (uint32_t)(host ? r.slot0 : c.slot0));
+            if (Op::kChecks)
+                plan.nflags += 1 + r.nr;
+            for (int t = 0; t < c.nt; ++t) {
+                const uint64_t to = host ? sp.out_bytes + (uint64_t)t * c.B : a.target_offs[c.tgt0 + t];
                 if (digest) {
-                    // device mode: the caller's digest slot tgt0 + r; consecutive slots share a launch
-                    const uint64_t slot = host ? msgs.size() : c.tgt0 + (uint64_t)r;
+                    // device mode: the caller's digest slot tgt0 + t; consecutive slots share a launch
+                    const uint64_t slot = host ? msgs.size() : c.tgt0 + (uint64_t)t;
                     if (sp.sha_runs.empty() || sp.sha_runs.back()[2] + sp.sha_runs.back()[1] != slot)
                         sp.sha_runs.push_back({(uint64_t)msgs.size(), 0, slot});
                     ++sp.sha_runs.back()[1];
@@ -1670,656 +1950,98 @@ int build_repair_plan(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks
                 }
                 toff.push_back(to);
             }
-            sp.in_bytes += (uint64_t)c.k * c.B;
-            sp.out_bytes += (uint64_t)c.ntargets * c.B;
-            if (c.ntargets > 0)
-                add_work(bins, tail, (uint32_t)(i - c0), c.B, (int64_t)min_avail, c.ntargets, c.k, true, false,
+            sp.in_bytes += (uint64_t)c.n * c.B;
+            sp.out_bytes += nstore;
+            // (a chunk with no row and nothing to copy has no work)
+            if (r.ns + r.nr > 0 || (Op::kDecodes && !recover && r.nout > 0))
+                add_work(bins, tail, (uint32_t)(i - c0), c.B, valid, (int)(r.ns + r.nr), c.k, true, false,
                          dec_small_kb(c.k));
         }
         std::vector<sec::Tile> tiles;
         flatten(bins, sp.groups, tiles, true);
         sp.ntail = (uint32_t)tail.size();
-        sp.nmsgs = (uint32_t)msgs.size();
-        sp.sha_split = sha1_split(ctx->opt, msgs);
-        sp.dig_off = align_up(sp.out_bytes, 4);  // host mode: digests follow the slab's targets (dword stores)
-        if (host)
-            sp.out_bytes = sp.dig_off + (uint64_t)msgs.size() * 20;
-        sp.off_desc = img.put(descs.data(), descs.size() * sizeof(sec::RepDesc));
+        sp.nentries = (uint32_t)echunk.size();
+        sp.off_desc = img.put(descs.data(), descs.size() * sizeof(Desc));
+        sp.off_cdesc = separate_cdesc ? img.put(cdescs.data(), cdescs.size() * sizeof(sec::ChkDesc)) : sp.off_desc;
         sp.off_tiles = img.put(tiles.data(), tiles.size() * sizeof(sec::Tile));
         sp.off_tail = img.put(tail.data(), tail.size() * sizeof(sec::TailItem));
+        sp.off_savail = img.put(savail.data(), savail.size() * 4);
+        if (Op::kChecks) {
+            sp.off_cpos = img.put(cpos.data(), cpos.size() * 4);
+            sp.off_echunk = img.put(echunk.data(), echunk.size() * 4);
+        }
+        if (Op::kDecodes) {
+            sp.off_srow = img.put(srow.data(), srow.size() * 4);
+            sp.off_mrow = img.put(mrow.data(), mrow.size() * 4);
+        }
+        if (Op::kTargets) {
+            sp.nmsgs = (uint32_t)msgs.size();
+            sp.sha_split = sha1_split(ctx->opt, msgs);
+            sp.dig_off = align_up(sp.out_bytes, 4);  // host mode: digests follow the slab's targets (dword stores)
+            if (host)
+                sp.out_bytes = sp.dig_off + (uint64_t)msgs.size() * 20;
+            sp.off_toff = img.put(toff.data(), toff.size() * 8);
+            sp.off_msgs = img.put(msgs.data(), msgs.size() * sizeof(sec::MsgDesc));
+        }
         soff.resize(soff.size() + sec::kBatchVecs, 0);  // the kernel loads a batch's offsets unconditionally
         sp.off_soff = img.put(soff.data(), soff.size() * 8);
-        sp.off_savail = img.put(savail.data(), savail.size() * 4);
-        sp.off_toff = img.put(toff.data(), toff.size() * 8);
-        sp.off_msgs = img.put(msgs.data(), msgs.size() * sizeof(sec::MsgDesc));
         plan.subs.push_back(std::move(sp));
     }
+    if (plan.nflags >= UINT32_MAX)
+        return SEC_EINVAL;
     RC(upload_plan(ctx, plan, img, tc, pending));
     plan.gen = tc.gen;
     return SEC_OK;
 }
 
-int launch_repair_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const uint8_t *blocks, uint8_t *out,
-                      uint8_t *digests, hipStream_t s)
+// One launch unit: the tile and tail kernels, then (operations with compared rows) the results
+// and (with digests) the targets' SHA-1 while they are device-resident (storb's piece ids).
+// Timing: a repair records kind 4 around its whole device-mode unit and nothing in host mode; the
+// others record their kind here, only around a unit with work (SHA-1 runs count), so a unit that
+// launches sec_check_final alone is untimed.
+template <class Op>
+int launch_row_sub(sec_ctx *ctx, const SubPlan &sp, bool host, const uint8_t *blocks, uint8_t *out, uint8_t *digests,
+                   sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, hipStream_t s)
 {
-    const sec::RepDesc *dd = plan.meta.as<sec::RepDesc>(sp.off_desc);
+    const RowOpState &st = ctx->row_ops[Op::kId];
+    const Plan &plan = st.plan;
+    const typename Op::Desc *dd = plan.meta.as<typename Op::Desc>(sp.off_desc);
     const sec::Tile *dt = plan.meta.as<sec::Tile>(sp.off_tiles);
-    const uint32_t *tabs = ctx->rep_tabs.buf.as<uint32_t>();
-    const sec::RepSlots sl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
-                           plan.meta.as<uint64_t>(sp.off_toff)};
+    const uint32_t *tabs = st.tabs.buf.as<uint32_t>();
+    uint32_t *flags = st.flags.as<uint32_t>();
+    const typename Op::Slots sl = Op::slots(plan.meta, sp, flags);
+    const bool work = !sp.groups.empty() || sp.ntail || !sp.sha_runs.empty();
+    const bool timed = Op::kChecks ? work : !host;
+    hipEvent_t t0 = nullptr;
+    if (timed)
+        RC(timing_begin(ctx, &t0, s));
     for (const Group &g : sp.groups) {
-        int e = sec_launch_repair(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
-                                  g.mfma);
+        int e = sec_launch_rows(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
+                                g.mfma);
         if (e)
-            return hip_fail((hipError_t)e, "sec_repair_kernel");
+            return hip_fail((hipError_t)e, Op::kTile);
     }
     if (sp.ntail) {
-        int e = sec_launch_repair_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
+        int e = sec_launch_rows_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
         if (e)
-            return hip_fail((hipError_t)e, "sec_repair_tail");
+            return hip_fail((hipError_t)e, Op::kTail);
     }
-    // the repaired pieces' SHA-1 (storb's piece ids) while they are device-resident
+    if (Op::kChecks) {
+        const sec::ChkSlots csl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
+                                plan.meta.as<uint32_t>(sp.off_cpos), plan.meta.as<uint32_t>(sp.off_echunk), flags};
+        int e = sec_launch_check_final(blocks, plan.meta.as<sec::ChkDesc>(sp.off_cdesc), sp.nentries, csl, results,
+                                       row_bad, column, s);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_check_final");
+    }
     for (const auto &run : sp.sha_runs) {
         int e = sec_launch_sha1(out, out, plan.meta.as<sec::MsgDesc>(sp.off_msgs) + run[0], (uint32_t)run[1],
                                 digests + 20 * run[2], s, sp.sha_split);
         if (e)
             return hip_fail((hipError_t)e, "sec_sha1_kernel");
     }
-    return SEC_OK;
-}
-
-// ---- check plan ---------------------------------------------------------------
-// Preconditions of a check (sec_check_batch): n held blocks, k <= n <= m, all in [0, m) and
-// distinct.  The basis is the first k.
-int check_check(int k, int m, const int32_t *sharenums, int n)
-{
-    if (n < 0 || !sharenums)
-        return SEC_EINVAL;
-    if (k < 1 || m < k || m > 256)
-        return SEC_EKM;
-    if (n < k || n > m)
-        return SEC_ENBLOCKS;
-    for (int i = 0; i < n; ++i)
-        if (sharenums[i] < 0 || sharenums[i] >= m)
-            return SEC_ESHARENUM;
-    bool seen[256] = {false};
-    for (int i = 0; i < n; ++i) {
-        if (seen[sharenums[i]])
-            return SEC_EDUPSHARE;
-        seen[sharenums[i]] = true;
-    }
-    return SEC_OK;
-}
-
-// The repair plan with check rows in place of targets: per chunk the tables of the repair matrix
-// of its check rows over its basis (layout [slot][row][5], cached by basis and check rows), its
-// n entries (the basis in normalised order, then the check rows in the caller's), tiles as a
-// repair's (add_work) over valid = the least avail of all n, and its flag words in ctx->chk_flags:
-// one for the first differing position, one per check row (ChkDesc::flag0).  Host mode stages
-// all n entries densely and returns results, row_bad and column through the slab output.
-int build_check_plan(sec_ctx *ctx, const sec_chk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
-                     const uint64_t *block_offs, const uint64_t *block_avail, const SlotLayout &L, bool host)
-{
-    Plan &plan = ctx->chk_plan;
-    TableCache &tc = ctx->chk_tabs;
-    std::vector<PendingExpand> pending;
-    std::vector<uint32_t> tab_of;
-    auto want = [&](int64_t i, std::string &key) -> size_t {
-        const sec_chk_chunk &c = chunks[i];
-        if (c.n == c.k)
-            return 0;
-        key = slots_key(c.k, c.m, &L.idx[L.first[i]]) + "|";
-        for (int r = c.k; r < c.n; ++r)
-            key += std::to_string(sharenums[c.slot0 + r]) + ",";
-        return (size_t)c.k * (c.n - c.k);
-    };
-    auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
-        const sec_chk_chunk &c = chunks[i];
-        const int k = c.k, nr = c.n - c.k;
-        const int *idx = &L.idx[L.first[i]];
-        std::vector<uint8_t> rm;
-        if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k),
-                                std::vector<int>(sharenums + c.slot0 + k, sharenums + c.slot0 + c.n), rm))
-            return (int)SEC_ESINGULAR;
-        cf.resize((size_t)k * nr);
-        for (int s = 0; s < k; ++s)
-            for (int r = 0; r < nr; ++r)
-                cf[(size_t)s * nr + r] = rm[(size_t)r * k + s];
-        return (int)SEC_OK;
-    };
-    RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
-
-    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return (uint64_t)chunks[i].n * chunks[i].B; },
-                                    (size_t)ctx->opt[O_SLAB_BYTES]);
-    Image img;
-    plan.subs.clear();
-    plan.nflags = 0;
-    for (auto [c0, c1] : ranges) {
-        SubPlan sp;
-        sp.c0 = c0;
-        sp.c1 = c1;
-        std::vector<sec::ChkDesc> descs((size_t)(c1 - c0));
-        std::vector<uint64_t> soff;
-        std::vector<uint32_t> savail, cpos, echunk;
-        Bins bins;
-        std::vector<sec::TailItem> tail;
-        for (int64_t i = c0; i < c1; ++i) {
-            const sec_chk_chunk &c = chunks[i];
-            const uint64_t base = L.first[i];
-            sec::ChkDesc &d = descs[i - c0];
-            d.B = (uint32_t)c.B;
-            d.k = (uint32_t)c.k;
-            d.nr = (uint32_t)(c.n - c.k);
-            d.tab = tab_of[i];
-            d.slot0 = (uint32_t)soff.size();
-            d.flag0 = (uint32_t)plan.nflags;
-            d.res = (uint32_t)(host ? i - c0 : i);
-            d.cslot0 = (uint32_t)(host ? soff.size() : c.slot0);
-            d.pad = 0;
-            plan.nflags += 1 + d.nr;
-            uint64_t min_avail = c.B;
-            for (int e = 0; e < c.n; ++e) {
-                const int from = e < c.k ? L.perm[base + e] : e;
-                soff.push_back(host ? sp.in_bytes + (uint64_t)e * c.B : block_offs[c.slot0 + from]);
-                const uint64_t av = host ? c.B : slot_avail(c, block_avail, from);  // staged entries are zero-filled
-                savail.push_back((uint32_t)av);
-                cpos.push_back((uint32_t)from);
-                echunk.push_back((uint32_t)(i - c0));
-                min_avail = std::min(min_avail, av);
-            }
-            d.valid = (uint32_t)min_avail;
-            sp.in_bytes += (uint64_t)c.n * c.B;
-            if (d.nr > 0)
-                add_work(bins, tail, (uint32_t)(i - c0), c.B, (int64_t)min_avail, (int)d.nr, c.k, true, false,
-                         dec_small_kb(c.k));
-        }
-        std::vector<sec::Tile> tiles;
-        flatten(bins, sp.groups, tiles, true);
-        sp.ntail = (uint32_t)tail.size();
-        // host mode's slab output: the results, then row_bad and column, one byte per entry each
-        sp.chk_rows = (uint64_t)(c1 - c0) * sizeof(sec::ChkResult);
-        sp.chk_col = sp.chk_rows + soff.size();
-        sp.out_bytes = sp.chk_col + soff.size();
-        sp.off_desc = img.put(descs.data(), descs.size() * sizeof(sec::ChkDesc));
-        sp.off_tiles = img.put(tiles.data(), tiles.size() * sizeof(sec::Tile));
-        sp.off_tail = img.put(tail.data(), tail.size() * sizeof(sec::TailItem));
-        sp.off_savail = img.put(savail.data(), savail.size() * 4);
-        sp.off_cpos = img.put(cpos.data(), cpos.size() * 4);
-        sp.off_echunk = img.put(echunk.data(), echunk.size() * 4);
-        sp.nentries = (uint32_t)echunk.size();
-        soff.resize(soff.size() + sec::kBatchVecs, 0);  // the kernel loads a batch's offsets unconditionally
-        sp.off_soff = img.put(soff.data(), soff.size() * 8);
-        plan.subs.push_back(std::move(sp));
-    }
-    if (plan.nflags >= UINT32_MAX)
-        return SEC_EINVAL;
-    RC(upload_plan(ctx, plan, img, tc, pending));
-    plan.gen = tc.gen;
-    return SEC_OK;
-}
-
-// The check kernels of one launch unit, then its results (timed as kind 5 by the caller's stream
-// events only when there is a check row: a unit of n == k chunks launches the results alone)
-int launch_check_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const uint8_t *blocks,
-                     sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, hipStream_t s)
-{
-    const sec::ChkDesc *dd = plan.meta.as<sec::ChkDesc>(sp.off_desc);
-    const sec::Tile *dt = plan.meta.as<sec::Tile>(sp.off_tiles);
-    const uint32_t *tabs = ctx->chk_tabs.buf.as<uint32_t>();
-    const sec::ChkSlots sl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
-                           plan.meta.as<uint32_t>(sp.off_cpos), plan.meta.as<uint32_t>(sp.off_echunk),
-                           ctx->chk_flags.as<uint32_t>()};
-    const bool work = !sp.groups.empty() || sp.ntail;
-    hipEvent_t t0 = nullptr;
-    if (work)
-        RC(timing_begin(ctx, &t0, s));
-    for (const Group &g : sp.groups) {
-        int e = sec_launch_check(g.rows, g.U, g.wide, g.lanes, blocks, dd, dt + g.first, g.count, tabs, sl, s, g.mfma);
-        if (e)
-            return hip_fail((hipError_t)e, "sec_check_kernel");
-    }
-    if (sp.ntail) {
-        int e = sec_launch_check_tail(blocks, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
-        if (e)
-            return hip_fail((hipError_t)e, "sec_check_tail");
-    }
-    int e = sec_launch_check_final(blocks, dd, sp.nentries, sl, results, row_bad, column, s);
-    if (e)
-        return hip_fail((hipError_t)e, "sec_check_final");
-    if (work)
-        RC(timing_end(ctx, t0, 5, s));
-    return SEC_OK;
-}
-
-// ---- decode + check plan --------------------------------------------------------
-// The check plan with the decode's rows in front (a sibling of build_check_plan): per chunk one
-// table of the repair matrix over its basis, layout [slot][row][5], rows = its e missing primaries
-// in ascending order, then its check rows in the caller's order (cached by basis and check rows:
-// the basis fixes the missing primaries); its n entries as a check's (the basis in normalised
-// order, then the check rows), with the decode's per-slot output rows beside them; tiles as a
-// decode's (add_work) over all e + nr rows and valid = min(the last output row's length unless
-// recover-only, the least avail of all n); flag words as a check's, in ctx->dchk_flags.  Both a
-// DChkDesc (the tile kernels) and a ChkDesc (sec_check_final) per chunk.  Host mode stages all n
-// entries densely once and returns results, row_bad, column and the decoded bytes through the slab
-// output.
-int build_decode_check_plan(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
-                            const uint64_t *block_offs, const uint64_t *block_avail, const SlotLayout &L, bool host,
-                            bool recover)
-{
-    Plan &plan = ctx->dchk_plan;
-    TableCache &tc = ctx->dchk_tabs;
-    std::vector<PendingExpand> pending;
-    std::vector<uint32_t> tab_of, e_of((size_t)nchunks, 0);
-    auto want = [&](int64_t i, std::string &key) -> size_t {
-        const sec_dchk_chunk &c = chunks[i];
-        const int *idx = &L.idx[L.first[i]];
-        int e = 0;
-        for (int s = 0; s < c.k; ++s)
-            e += idx[s] >= c.k;
-        e_of[i] = (uint32_t)e;
-        const int rows = e + c.n - c.k;
-        if (!rows)
-            return 0;
-        key = slots_key(c.k, c.m, idx) + "|";
-        for (int r = c.k; r < c.n; ++r)
-            key += std::to_string(sharenums[c.slot0 + r]) + ",";
-        return (size_t)c.k * rows;
-    };
-    auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
-        const sec_dchk_chunk &c = chunks[i];
-        const int k = c.k;
-        const int *idx = &L.idx[L.first[i]];
-        std::vector<int> targets;
-        for (int s = 0; s < k; ++s)  // normalised slot s holds primary s, or stands in for it
-            if (idx[s] >= k)
-                targets.push_back(s);
-        targets.insert(targets.end(), sharenums + c.slot0 + k, sharenums + c.slot0 + c.n);
-        const int rows = (int)targets.size();
-        std::vector<uint8_t> rm;
-        if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k), targets, rm))
-            return (int)SEC_ESINGULAR;
-        cf.resize((size_t)k * rows);
-        for (int s = 0; s < k; ++s)
-            for (int r = 0; r < rows; ++r)
-                cf[(size_t)s * rows + r] = rm[(size_t)r * k + s];
-        return (int)SEC_OK;
-    };
-    RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
-
-    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return (uint64_t)chunks[i].n * chunks[i].B; },
-                                    (size_t)ctx->opt[O_SLAB_BYTES]);
-    Image img;
-    plan.subs.clear();
-    plan.nflags = 0;
-    for (auto [c0, c1] : ranges) {
-        SubPlan sp;
-        sp.c0 = c0;
-        sp.c1 = c1;
-        std::vector<sec::DChkDesc> descs((size_t)(c1 - c0));
-        std::vector<sec::ChkDesc> cdescs((size_t)(c1 - c0));
-        std::vector<uint64_t> soff;
-        std::vector<uint32_t> savail, cpos, echunk, srow, mrow;
-        Bins bins;
-        std::vector<sec::TailItem> tail;
-        // host mode's slab output: the results, row_bad and column (one byte per entry each), then
-        // the decoded bytes of every chunk
-        uint64_t nent = 0;
-        for (int64_t i = c0; i < c1; ++i)
-            nent += (uint64_t)chunks[i].n;
-        sp.chk_rows = (uint64_t)(c1 - c0) * sizeof(sec::ChkResult);
-        sp.chk_col = sp.chk_rows + nent;
-        sp.dchk_out = align_up(sp.chk_col + nent, 256);
-        sp.out_bytes = sp.dchk_out;
-        for (int64_t i = c0; i < c1; ++i) {
-            const sec_dchk_chunk &c = chunks[i];
-            const uint64_t base = L.first[i];
-            const int *idx = &L.idx[base];
-            const uint32_t slot0 = (uint32_t)soff.size();
-            std::vector<uint32_t> mr;
-            uint64_t min_avail = c.B;
-            for (int e = 0; e < c.n; ++e) {
-                const int from = e < c.k ? L.perm[base + e] : e;
-                soff.push_back(host ? sp.in_bytes + (uint64_t)e * c.B : block_offs[c.slot0 + from]);
-                const uint64_t av = host ? c.B : slot_avail(c, block_avail, from);  // staged entries are zero-filled
-                savail.push_back((uint32_t)av);
-                cpos.push_back((uint32_t)from);
-                echunk.push_back((uint32_t)(i - c0));
-                min_avail = std::min(min_avail, av);
-                // recover-only: no copies, and recovered row r goes to output row r
-                srow.push_back(e < c.k && !recover && idx[e] < c.k ? (uint32_t)idx[e] : 0xFFFFFFFFu);
-                if (e < c.k && idx[e] >= c.k)
-                    mr.push_back(recover ? (uint32_t)mr.size() : (uint32_t)e);
-            }
-            mr.resize((size_t)c.n, 0);
-            mrow.insert(mrow.end(), mr.begin(), mr.end());
-            const uint32_t e = e_of[i], nr = (uint32_t)(c.n - c.k);
-            const uint64_t nout = recover ? (uint64_t)e * c.B : (uint64_t)c.k * c.B - c.padlen;
-            const int64_t valid = std::max<int64_t>(
-                0, std::min<int64_t>(recover ? (int64_t)c.B : (int64_t)nout - (int64_t)(c.k - 1) * (int64_t)c.B,
-                                     (int64_t)min_avail));
-            sec::DChkDesc &d = descs[i - c0];
-            d.out_off = host ? sp.out_bytes : c.out_off;
-            d.n = nout;
-            d.B = (uint32_t)c.B;
-            d.k = (uint32_t)c.k;
-            d.e = e;
-            d.nr = nr;
-            d.tab = tab_of[i];
-            d.slot0 = slot0;
-            d.flag0 = (uint32_t)plan.nflags;
-            d.valid = (uint32_t)valid;
-            sec::ChkDesc &cd = cdescs[i - c0];
-            cd.B = d.B;
-            cd.k = d.k;
-            cd.nr = nr;
-            cd.tab = d.tab;
-            cd.slot0 = slot0;
-            cd.flag0 = d.flag0;
-            cd.valid = d.valid;
-            cd.res = (uint32_t)(host ? i - c0 : i);
-            cd.cslot0 = (uint32_t)(host ? slot0 : c.slot0);
-            cd.pad = 0;
-            plan.nflags += 1 + nr;
-            sp.in_bytes += (uint64_t)c.n * c.B;
-            sp.out_bytes += nout;
-            // (a chunk with no row and nothing to copy has no work: n == k, no primary lost, and
-            // recover-only or every byte cut by padlen)
-            if (e + nr > 0 || (!recover && nout > 0))
-                add_work(bins, tail, (uint32_t)(i - c0), c.B, valid, (int)(e + nr), c.k, true, false,
-                         dec_small_kb(c.k));
-        }
-        std::vector<sec::Tile> tiles;
-        flatten(bins, sp.groups, tiles, true);
-        sp.ntail = (uint32_t)tail.size();
-        sp.off_desc = img.put(descs.data(), descs.size() * sizeof(sec::DChkDesc));
-        sp.off_cdesc = img.put(cdescs.data(), cdescs.size() * sizeof(sec::ChkDesc));
-        sp.off_tiles = img.put(tiles.data(), tiles.size() * sizeof(sec::Tile));
-        sp.off_tail = img.put(tail.data(), tail.size() * sizeof(sec::TailItem));
-        sp.off_savail = img.put(savail.data(), savail.size() * 4);
-        sp.off_cpos = img.put(cpos.data(), cpos.size() * 4);
-        sp.off_echunk = img.put(echunk.data(), echunk.size() * 4);
-        sp.off_srow = img.put(srow.data(), srow.size() * 4);
-        sp.off_mrow = img.put(mrow.data(), mrow.size() * 4);
-        sp.nentries = (uint32_t)echunk.size();
-        soff.resize(soff.size() + sec::kBatchVecs, 0);  // the kernel loads a batch's offsets unconditionally
-        sp.off_soff = img.put(soff.data(), soff.size() * 8);
-        plan.subs.push_back(std::move(sp));
-    }
-    if (plan.nflags >= UINT32_MAX)
-        return SEC_EINVAL;
-    RC(upload_plan(ctx, plan, img, tc, pending));
-    plan.gen = tc.gen;
-    return SEC_OK;
-}
-
-// The decode + check kernels of one launch unit, then its results (timing kind 6)
-int launch_decode_check_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const uint8_t *blocks, uint8_t *out,
-                            sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, hipStream_t s)
-{
-    const sec::DChkDesc *dd = plan.meta.as<sec::DChkDesc>(sp.off_desc);
-    const sec::ChkDesc *cd = plan.meta.as<sec::ChkDesc>(sp.off_cdesc);
-    const sec::Tile *dt = plan.meta.as<sec::Tile>(sp.off_tiles);
-    const uint32_t *tabs = ctx->dchk_tabs.buf.as<uint32_t>();
-    uint32_t *flags = ctx->dchk_flags.as<uint32_t>();
-    const sec::DChkSlots sl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
-                            plan.meta.as<uint32_t>(sp.off_srow), plan.meta.as<uint32_t>(sp.off_mrow), flags};
-    const sec::ChkSlots csl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
-                            plan.meta.as<uint32_t>(sp.off_cpos), plan.meta.as<uint32_t>(sp.off_echunk), flags};
-    const bool work = !sp.groups.empty() || sp.ntail;
-    hipEvent_t t0 = nullptr;
-    if (work)
-        RC(timing_begin(ctx, &t0, s));
-    for (const Group &g : sp.groups) {
-        int e = sec_launch_decode_check(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl,
-                                        s, g.mfma);
-        if (e)
-            return hip_fail((hipError_t)e, "sec_decode_check_kernel");
-    }
-    if (sp.ntail) {
-        int e = sec_launch_decode_check_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs,
-                                             sl, s);
-        if (e)
-            return hip_fail((hipError_t)e, "sec_decode_check_tail");
-    }
-    int e = sec_launch_check_final(blocks, cd, sp.nentries, csl, results, row_bad, column, s);
-    if (e)
-        return hip_fail((hipError_t)e, "sec_check_final");
-    if (work)
-        RC(timing_end(ctx, t0, 6, s));
-    return SEC_OK;
-}
-
-// ---- repair + check plan --------------------------------------------------------
-// Preconditions of a repair + check (sec_repair_check_batch): sec_check_batch's for the n held
-// blocks, then the targets: in [0, m), distinct, none of them held.
-int check_repair_check(int k, int m, const int32_t *sharenums, int n, const int32_t *targets, int nt)
-{
-    if (n < 0 || nt < 0 || !sharenums || (nt > 0 && !targets))
-        return SEC_EINVAL;
-    if (k < 1 || m < k || m > 256)
-        return SEC_EKM;
-    if (n < k || n > m)
-        return SEC_ENBLOCKS;
-    for (int i = 0; i < n; ++i)
-        if (sharenums[i] < 0 || sharenums[i] >= m)
-            return SEC_ESHARENUM;
-    for (int i = 0; i < nt; ++i)
-        if (targets[i] < 0 || targets[i] >= m)
-            return SEC_ESHARENUM;
-    bool seen[256] = {false};
-    for (int i = 0; i < n + nt; ++i) {
-        const int b = i < n ? sharenums[i] : targets[i - n];
-        if (seen[b])
-            return SEC_EDUPSHARE;
-        seen[b] = true;
-    }
-    return SEC_OK;
-}
-
-// The check plan with the repair's rows in front (a sibling of build_repair_plan and
-// build_decode_check_plan): per chunk one table of the repair matrix over its basis, layout
-// [slot][row][5], rows = its targets in the caller's order, then its check rows in entry order
-// (cached by basis, targets and check rows); its n entries as a check's (the basis in normalised
-// order, then the check rows); one address per target; tiles as a repair's (add_work) over all
-// nt + nr rows and valid = the least avail of all n; flag words as a check's, in ctx->rchk_flags;
-// one SHA-1 message per target when digests are asked for.  Both an RChkDesc (the tile kernels) and
-// a ChkDesc (sec_check_final) per chunk.  Host mode stages all n entries densely once and returns
-// results, row_bad, column, the targets and their digests through the slab output.
-int build_repair_check_plan(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
-                            const uint64_t *block_offs, const uint64_t *block_avail, const int32_t *target_nums,
-                            const uint64_t *target_offs, const SlotLayout &L, bool host, bool digest)
-{
-    Plan &plan = ctx->rchk_plan;
-    TableCache &tc = ctx->rchk_tabs;
-    std::vector<PendingExpand> pending;
-    std::vector<uint32_t> tab_of;
-    auto want = [&](int64_t i, std::string &key) -> size_t {
-        const sec_rchk_chunk &c = chunks[i];
-        const int rows = c.ntargets + c.n - c.k;
-        if (!rows)
-            return 0;
-        key = slots_key(c.k, c.m, &L.idx[L.first[i]]) + "|";
-        for (int r = 0; r < c.ntargets; ++r)
-            key += std::to_string(target_nums[c.tgt0 + r]) + ",";
-        key += "|";
-        for (int r = c.k; r < c.n; ++r)
-            key += std::to_string(sharenums[c.slot0 + r]) + ",";
-        return (size_t)c.k * rows;
-    };
-    auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
-        const sec_rchk_chunk &c = chunks[i];
-        const int k = c.k;
-        const int *idx = &L.idx[L.first[i]];
-        std::vector<int> rows_of;
-        if (c.ntargets)
-            rows_of.assign(target_nums + c.tgt0, target_nums + c.tgt0 + c.ntargets);
-        rows_of.insert(rows_of.end(), sharenums + c.slot0 + k, sharenums + c.slot0 + c.n);
-        const int rows = (int)rows_of.size();
-        std::vector<uint8_t> rm;
-        if (!sec::repair_matrix(k, c.m, std::vector<int>(idx, idx + k), rows_of, rm))
-            return (int)SEC_ESINGULAR;
-        cf.resize((size_t)k * rows);
-        for (int s = 0; s < k; ++s)
-            for (int r = 0; r < rows; ++r)
-                cf[(size_t)s * rows + r] = rm[(size_t)r * k + s];
-        return (int)SEC_OK;
-    };
-    RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
-
-    // with digests few large slabs, as the repair's (one SHA-1 chain per piece)
-    const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return (uint64_t)chunks[i].n * chunks[i].B; },
-                                    (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
-    Image img;
-    plan.subs.clear();
-    plan.nflags = 0;
-    for (auto [c0, c1] : ranges) {
-        SubPlan sp;
-        sp.c0 = c0;
-        sp.c1 = c1;
-        std::vector<sec::RChkDesc> descs((size_t)(c1 - c0));
-        std::vector<sec::ChkDesc> cdescs((size_t)(c1 - c0));
-        std::vector<uint64_t> soff, toff;
-        std::vector<uint32_t> savail, cpos, echunk;
-        std::vector<sec::MsgDesc> msgs;
-        Bins bins;
-        std::vector<sec::TailItem> tail;
-        // host mode's slab output: the results, row_bad and column (one byte per entry each), then
-        // every chunk's targets, then their digests
-        uint64_t nent = 0;
-        for (int64_t i = c0; i < c1; ++i)
-            nent += (uint64_t)chunks[i].n;
-        sp.chk_rows = (uint64_t)(c1 - c0) * sizeof(sec::ChkResult);
-        sp.chk_col = sp.chk_rows + nent;
-        sp.rchk_out = align_up(sp.chk_col + nent, 256);
-        sp.out_bytes = sp.rchk_out;
-        for (int64_t i = c0; i < c1; ++i) {
-            const sec_rchk_chunk &c = chunks[i];
-            const uint64_t base = L.first[i];
-            const uint32_t slot0 = (uint32_t)soff.size();
-            uint64_t min_avail = c.B;
-            for (int e = 0; e < c.n; ++e) {
-                const int from = e < c.k ? L.perm[base + e] : e;
-                soff.push_back(host ? sp.in_bytes + (uint64_t)e * c.B : block_offs[c.slot0 + from]);
-                const uint64_t av = host ? c.B : slot_avail(c, block_avail, from);  // staged entries are zero-filled
-                savail.push_back((uint32_t)av);
-                cpos.push_back((uint32_t)from);
-                echunk.push_back((uint32_t)(i - c0));
-                min_avail = std::min(min_avail, av);
-            }
-            const uint32_t nt = (uint32_t)c.ntargets, nr = (uint32_t)(c.n - c.k);
-            sec::RChkDesc &d = descs[i - c0];
-            d.B = (uint32_t)c.B;
-            d.k = (uint32_t)c.k;
-            d.nt = nt;
-            d.nr = nr;
-            d.tab = tab_of[i];
-            d.slot0 = slot0;
-            d.tgt0 = (uint32_t)toff.size();
-            d.flag0 = (uint32_t)plan.nflags;
-            d.valid = (uint32_t)min_avail;
-            d.pad = 0;
-            sec::ChkDesc &cd = cdescs[i - c0];
-            cd.B = d.B;
-            cd.k = d.k;
-            cd.nr = nr;
-            cd.tab = d.tab;
-            cd.slot0 = slot0;
-            cd.flag0 = d.flag0;
-            cd.valid = d.valid;
-            cd.res = (uint32_t)(host ? i - c0 : i);
-            cd.cslot0 = (uint32_t)(host ? slot0 : c.slot0);
-            cd.pad = 0;
-            plan.nflags += 1 + nr;
-            for (uint32_t r = 0; r < nt; ++r) {
-                const uint64_t to = host ? sp.out_bytes + (uint64_t)r * c.B : target_offs[c.tgt0 + r];
-                if (digest) {
-                    // device mode: the caller's digest slot tgt0 + r; consecutive slots share a launch
-                    const uint64_t slot = host ? msgs.size() : c.tgt0 + (uint64_t)r;
-                    if (sp.sha_runs.empty() || sp.sha_runs.back()[2] + sp.sha_runs.back()[1] != slot)
-                        sp.sha_runs.push_back({(uint64_t)msgs.size(), 0, slot});
-                    ++sp.sha_runs.back()[1];
-                    msgs.push_back(sec::MsgDesc{to, c.B, c.B, 0, 0});
-                }
-                toff.push_back(to);
-            }
-            sp.in_bytes += (uint64_t)c.n * c.B;
-            sp.out_bytes += (uint64_t)nt * c.B;
-            if (nt + nr > 0)
-                add_work(bins, tail, (uint32_t)(i - c0), c.B, (int64_t)min_avail, (int)(nt + nr), c.k, true, false,
-                         dec_small_kb(c.k));
-        }
-        std::vector<sec::Tile> tiles;
-        flatten(bins, sp.groups, tiles, true);
-        sp.ntail = (uint32_t)tail.size();
-        sp.nmsgs = (uint32_t)msgs.size();
-        sp.sha_split = sha1_split(ctx->opt, msgs);
-        sp.dig_off = align_up(sp.out_bytes, 4);  // host mode: digests follow the slab's targets (dword stores)
-        if (host)
-            sp.out_bytes = sp.dig_off + (uint64_t)msgs.size() * 20;
-        sp.off_desc = img.put(descs.data(), descs.size() * sizeof(sec::RChkDesc));
-        sp.off_cdesc = img.put(cdescs.data(), cdescs.size() * sizeof(sec::ChkDesc));
-        sp.off_tiles = img.put(tiles.data(), tiles.size() * sizeof(sec::Tile));
-        sp.off_tail = img.put(tail.data(), tail.size() * sizeof(sec::TailItem));
-        sp.off_savail = img.put(savail.data(), savail.size() * 4);
-        sp.off_cpos = img.put(cpos.data(), cpos.size() * 4);
-        sp.off_echunk = img.put(echunk.data(), echunk.size() * 4);
-        sp.off_toff = img.put(toff.data(), toff.size() * 8);
-        sp.off_msgs = img.put(msgs.data(), msgs.size() * sizeof(sec::MsgDesc));
-        sp.nentries = (uint32_t)echunk.size();
-        soff.resize(soff.size() + sec::kBatchVecs, 0);  // the kernel loads a batch's offsets unconditionally
-        sp.off_soff = img.put(soff.data(), soff.size() * 8);
-        plan.subs.push_back(std::move(sp));
-    }
-    if (plan.nflags >= UINT32_MAX)
-        return SEC_EINVAL;
-    RC(upload_plan(ctx, plan, img, tc, pending));
-    plan.gen = tc.gen;
-    return SEC_OK;
-}
-
-// The repair + check kernels of one launch unit, its results and, with digests, the targets' SHA-1
-// while they are device-resident (timing kind 7; a unit with no row launches the results alone,
-// untimed, as a check's)
-int launch_repair_check_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const uint8_t *blocks, uint8_t *out,
-                            uint8_t *digests, sec::ChkResult *results, uint8_t *row_bad, uint8_t *column,
-                            hipStream_t s)
-{
-    const sec::RChkDesc *dd = plan.meta.as<sec::RChkDesc>(sp.off_desc);
-    const sec::ChkDesc *cd = plan.meta.as<sec::ChkDesc>(sp.off_cdesc);
-    const sec::Tile *dt = plan.meta.as<sec::Tile>(sp.off_tiles);
-    const uint32_t *tabs = ctx->rchk_tabs.buf.as<uint32_t>();
-    uint32_t *flags = ctx->rchk_flags.as<uint32_t>();
-    const sec::RChkSlots sl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
-                            plan.meta.as<uint64_t>(sp.off_toff), flags};
-    const sec::ChkSlots csl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
-                            plan.meta.as<uint32_t>(sp.off_cpos), plan.meta.as<uint32_t>(sp.off_echunk), flags};
-    const bool work = !sp.groups.empty() || sp.ntail || !sp.sha_runs.empty();
-    hipEvent_t t0 = nullptr;
-    if (work)
-        RC(timing_begin(ctx, &t0, s));
-    for (const Group &g : sp.groups) {
-        int e = sec_launch_repair_check(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl,
-                                        s, g.mfma);
-        if (e)
-            return hip_fail((hipError_t)e, "sec_repair_check_kernel");
-    }
-    if (sp.ntail) {
-        int e = sec_launch_repair_check_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs,
-                                             sl, s);
-        if (e)
-            return hip_fail((hipError_t)e, "sec_repair_check_tail");
-    }
-    int e = sec_launch_check_final(blocks, cd, sp.nentries, csl, results, row_bad, column, s);
-    if (e)
-        return hip_fail((hipError_t)e, "sec_check_final");
-    for (const auto &run : sp.sha_runs) {
-        e = sec_launch_sha1(out, out, plan.meta.as<sec::MsgDesc>(sp.off_msgs) + run[0], (uint32_t)run[1],
-                            digests + 20 * run[2], s, sp.sha_split);
-        if (e)
-            return hip_fail((hipError_t)e, "sec_sha1_kernel");
-    }
-    if (work)
-        RC(timing_end(ctx, t0, 7, s));
+    if (timed)
+        RC(timing_end(ctx, t0, Op::kTiming, s));
     return SEC_OK;
 }
 
@@ -2424,6 +2146,166 @@ int run_pipeline(sec_ctx *ctx, Plan &plan, Gather gather, Scatter scatter, Launc
         sl.in.release();
         sl.out.release();
     }
+    return SEC_OK;
+}
+
+// ---- row operations: the entry skeleton ------------------------------------------------
+// Everything behind the four entry points but what they differ in (their Op).  Plan key: host
+// mode keys on shapes, sharenums and targets only (its entries are staged densely, zero-filled past
+// their avail, its stored rows dense in the slab); device mode on every descriptor, sharenum,
+// target, address and avail.  The outputs' addresses are launch arguments, not part of the plan.
+// (blocks and out may be NULL: block_offs / target_offs / out_off are then absolute addresses)
+template <class Op>
+int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, const RowArgs &a)
+{
+    using Chunk = typename Op::Chunk;
+    const unsigned allowed = SEC_F_HOST | SEC_F_ASYNC | (Op::kDecodes ? SEC_F_RECOVER : 0u);
+    if (!ctx || nchunks < 0 ||
+        (nchunks > 0 && (!chunks || !a.sharenums || !a.block_offs || (Op::kChecks && !a.results))) ||
+        (a.flags & ~allowed) || ((a.flags & SEC_F_HOST) && (a.flags & SEC_F_ASYNC)))
+        return SEC_EINVAL;
+    if (nchunks == 0)
+        return SEC_OK;
+    if (nchunks >= (int64_t)UINT32_MAX)
+        return SEC_EINVAL;
+    const bool host = a.flags & SEC_F_HOST;
+    const bool digest = a.digests != nullptr;
+    RC(set_dev(ctx));
+
+    // preconditions of every chunk before any device work, in the operation's own order
+    RC(Op::screen_first(chunks, nchunks, a));
+    uint64_t total_slots = 0, total_tgts = 0, total_out = 0;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        RC(Op::screen(chunks[i], a));
+        const RowChunk c = Op::view(chunks[i]);
+        total_slots = std::max<uint64_t>(total_slots, c.slot0 + (uint64_t)c.n);
+        if (c.nt)
+            total_tgts = std::max<uint64_t>(total_tgts, c.tgt0 + (uint64_t)c.nt);
+        total_out += (uint64_t)c.nt * c.B;
+    }
+    // with no results to report, a call with no target, or no output byte and no digest, is done
+    if (!Op::kChecks && (total_tgts == 0 || (total_out == 0 && !digest)))
+        return SEC_OK;
+    if (total_slots >= UINT32_MAX || total_tgts >= UINT32_MAX)
+        return SEC_EINVAL;
+
+    RowOpState &st = ctx->row_ops[Op::kId];
+    Plan &plan = st.plan;
+    PlanKey key;
+    if (host) {
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const RowChunk c = Op::view(chunks[i]);
+            key.put(c.B);
+            key.put(c.padlen);
+            key.put(c.n);
+            key.put(c.nt);
+            key.put(c.k);
+            key.put(c.m);
+            key.put(a.sharenums + c.slot0, (size_t)c.n * 4);
+            if (c.nt)
+                key.put(a.target_nums + c.tgt0, (size_t)c.nt * 4);
+        }
+    } else {
+        key.put(chunks, sizeof(Chunk) * (size_t)nchunks);
+        key.put(a.sharenums, total_slots * 4);
+        key.put(a.block_offs, total_slots * 8);
+        if (a.block_avail)
+            key.put(a.block_avail, total_slots * 8);
+        if (total_tgts) {
+            key.put(a.target_nums, total_tgts * 4);
+            key.put(a.target_offs, total_tgts * 8);
+        }
+    }
+    key.put((a.flags & (SEC_F_HOST | SEC_F_RECOVER)) | (!host && a.block_avail ? 0x10000u : 0u) |
+            (digest ? 0x20000u : 0u));
+    const bool reuse = plan_reusable(plan, st.tabs, key);
+    SlotLayout L;
+    if (!reuse || host)
+        L = slot_layout(chunks, nchunks, a.sharenums);
+    if (!reuse) {
+        plan.valid = false;
+        RC(build_row_plan<Op>(ctx, chunks, nchunks, a, L, host));
+        plan.key.swap(key.bytes);
+        plan.valid = true;
+    }
+    if (Op::kChecks) {
+        // every call starts from clean flag words (0xFFFFFFFF: no position yet, row agrees), whatever
+        // the last call on this plan found
+        RC(st.flags.ensure((size_t)plan.nflags * 4));
+        CK(hipMemsetAsync(st.flags.p, 0xFF, (size_t)plan.nflags * 4, ctx->stream()));
+    }
+
+    if (!host) {
+        RC(launch_row_sub<Op>(ctx, plan.subs[0], false, a.blocks, a.out, a.digests, (sec::ChkResult *)a.results,
+                              a.row_bad, a.column, ctx->stream()));
+        if (!(a.flags & SEC_F_ASYNC))
+            CK(hipStreamSynchronize(ctx->stream()));
+        return SEC_OK;
+    }
+    // Host mode is always staged: all held entries of a chunk are gathered into pinned slabs ONCE
+    // (zero-filled from their avail to B) and feed every row; the stored rows, their digests and
+    // the results are scattered back.  A caller's buffer is never page-locked (no HostLock) nor
+    // used in place.  column passes through a buffer of its own so that a consistent chunk's
+    // bytes stay untouched.
+    ++ctx->staged_calls;
+    std::vector<uint8_t> col(a.column ? (size_t)total_slots : 0);
+    auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        uint64_t o = 0;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const RowChunk c = Op::view(chunks[i]);
+            for (int e = 0; e < c.n; ++e) {
+                const int from = entry_from(L, i, c.k, e);
+                const uint64_t av = slot_avail(c, a.block_avail, from);
+                jobs.push_back(
+                    sec::CopyJob{stage + o, (const void *)((uintptr_t)a.blocks + a.block_offs[c.slot0 + from]), av});
+                if (av < c.B)  // the entry's bytes past its avail are zero
+                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
+                o += c.B;
+            }
+        }
+    };
+    auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+        if (Op::kChecks)
+            jobs.push_back(
+                sec::CopyJob{a.results + sp.c0, stage, (uint64_t)(sp.c1 - sp.c0) * sizeof(sec_chk_result)});
+        uint64_t o = 0, b = sp.pay_off, g = sp.dig_off;
+        for (int64_t i = sp.c0; i < sp.c1; ++i) {
+            const RowChunk c = Op::view(chunks[i]);
+            if (Op::kChecks && a.row_bad)
+                jobs.push_back(sec::CopyJob{a.row_bad + c.slot0, stage + sp.chk_rows + o, (uint64_t)c.n});
+            if (Op::kChecks && a.column)
+                jobs.push_back(sec::CopyJob{col.data() + c.slot0, stage + sp.chk_col + o, (uint64_t)c.n});
+            o += (uint64_t)c.n;
+            for (int t = 0; t < c.nt; ++t) {
+                jobs.push_back(sec::CopyJob{(void *)((uintptr_t)a.out + a.target_offs[c.tgt0 + t]), stage + b, c.B});
+                b += c.B;
+                if (digest) {
+                    jobs.push_back(sec::CopyJob{a.digests + 20 * (c.tgt0 + (uint64_t)t), stage + g, 20});
+                    g += 20;
+                }
+            }
+            if (Op::kDecodes) {  // the reassembled chunk, or (recover-only) its recovered blocks
+                uint64_t nb = (uint64_t)c.k * c.B - c.padlen;
+                if (a.flags & SEC_F_RECOVER) {
+                    nb = 0;
+                    for (int j = 0; j < c.k; ++j)
+                        nb += a.sharenums[c.slot0 + j] >= c.k ? c.B : 0;
+                }
+                if (nb)
+                    jobs.push_back(sec::CopyJob{(void *)((uintptr_t)a.out + c.out_off), stage + b, nb});
+                b += nb;
+            }
+        }
+    };
+    auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
+        return launch_row_sub<Op>(ctx, sp, true, din, dout, dout + sp.dig_off, (sec::ChkResult *)dout,
+                                  a.row_bad ? dout + sp.chk_rows : nullptr, a.column ? dout + sp.chk_col : nullptr, s);
+    };
+    RC(run_pipeline(ctx, plan, gather, scatter, launch));
+    if (Op::kChecks && a.column)
+        for (int64_t i = 0; i < nchunks; ++i)
+            if (a.results[i].first != UINT64_MAX)
+                memcpy(a.column + chunks[i].slot0, col.data() + chunks[i].slot0, (size_t)Op::view(chunks[i]).n);
     return SEC_OK;
 }
 
@@ -2691,21 +2573,15 @@ void sec_ctx_destroy(sec_ctx *ctx)
     ctx->pin.release();
     ctx->enc_tabs.buf.release();
     ctx->dec_tabs.buf.release();
-    ctx->rep_tabs.buf.release();
-    ctx->chk_tabs.buf.release();
-    ctx->dchk_tabs.buf.release();
-    ctx->rchk_tabs.buf.release();
     ctx->enc_plan.meta.release();
     ctx->dec_plan.meta.release();
     ctx->sha_plan.meta.release();
     ctx->bn_plan.meta.release();
-    ctx->rep_plan.meta.release();
-    ctx->chk_plan.meta.release();
-    ctx->chk_flags.release();
-    ctx->dchk_plan.meta.release();
-    ctx->dchk_flags.release();
-    ctx->rchk_plan.meta.release();
-    ctx->rchk_flags.release();
+    for (RowOpState &st : ctx->row_ops) {
+        st.tabs.buf.release();
+        st.plan.meta.release();
+        st.flags.release();
+    }
     ctx->bn_scratch.release();
     ctx->bn_part.release();
     ctx->syn.release();
@@ -2755,9 +2631,10 @@ int sec_ctx_set_option(sec_ctx *ctx, const char *name, int64_t value)
     RC(set_dev(ctx));
     RC(drain_all(ctx));  // nothing in flight may still use a plan or pool built the old way
     ctx->opt.v[i] = value;
-    for (Plan *p : {&ctx->enc_plan, &ctx->dec_plan, &ctx->sha_plan, &ctx->bn_plan, &ctx->rep_plan, &ctx->chk_plan,
-                    &ctx->dchk_plan, &ctx->rchk_plan})
+    for (Plan *p : {&ctx->enc_plan, &ctx->dec_plan, &ctx->sha_plan, &ctx->bn_plan})
         p->valid = false;
+    for (RowOpState &st : ctx->row_ops)
+        st.plan.valid = false;
     if (i == O_COPY_THREADS) {
         ctx->tasks.reset();
         ctx->hash_tasks.reset();
@@ -2904,7 +2781,7 @@ int sec_decode_matrix(int k, int m, const int32_t *sharenums, uint8_t *out, int3
 
 int sec_repair_matrix(int k, int m, const int32_t *sharenums, const int32_t *targets, int ntargets, uint8_t *out)
 {
-    RC(check_repair(k, m, sharenums, targets, ntargets));
+    RC(check_blocks(k, m, sharenums, k, targets, ntargets, true));
     if (ntargets == 0)
         return SEC_OK;
     if (!out)
@@ -3990,524 +3867,51 @@ int decode_core(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks, cons
 }
 }  // namespace
 
-// ---- repair: lost pieces from any k survivors -------------------------------------------
+// ---- repair, check, decode + check, repair + check (row_op) ---------------------------------
 int sec_repair_batch(sec_ctx *ctx, const sec_rep_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
                      const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
                      const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out, uint8_t *digests,
                      unsigned flags)
 {
-    if (!ctx || nchunks < 0 || (nchunks > 0 && (!chunks || !sharenums || !block_offs)) ||
-        (flags & ~(SEC_F_HOST | SEC_F_ASYNC)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
-        return SEC_EINVAL;
-    if (nchunks == 0)
-        return SEC_OK;
-    if (nchunks >= (int64_t)UINT32_MAX)
-        return SEC_EINVAL;
-    const bool host = flags & SEC_F_HOST;
-    const bool digest = digests != nullptr;
-    RC(set_dev(ctx));
-
-    // preconditions of every chunk before any device work (sec_repair_matrix's)
-    uint64_t total_slots = 0, total_tgts = 0, total_out = 0;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const sec_rep_chunk &c = chunks[i];
-        if (c.ntargets < 0 || (c.ntargets > 0 && (!target_nums || !target_offs)))
-            return SEC_EINVAL;
-        if (c.k < 1 || c.m < c.k || c.m > 256)
-            return SEC_EKM;
-        RC(check_repair(c.k, c.m, sharenums + c.slot0, c.ntargets ? target_nums + c.tgt0 : nullptr, c.ntargets));
-        if (c.B >= (1ull << 31))
-            return SEC_ESIZE;
-        total_slots = std::max<uint64_t>(total_slots, c.slot0 + (uint64_t)c.k);
-        if (c.ntargets)
-            total_tgts = std::max<uint64_t>(total_tgts, c.tgt0 + (uint64_t)c.ntargets);
-        total_out += (uint64_t)c.ntargets * c.B;
-    }
-    if (total_tgts == 0 || (total_out == 0 && !digest))
-        return SEC_OK;
-    if (total_slots >= UINT32_MAX || total_tgts >= UINT32_MAX)
-        return SEC_EINVAL;
-    // (blocks and out may be NULL: block_offs / target_offs are then absolute addresses)
-
-    // Plan key: host mode keys on shapes, sharenums and targets only (its slots are staged densely,
-    // zero-filled past their avail, its targets dense in the slab); device mode on every descriptor,
-    // sharenum, target, address and avail.
-    Plan &plan = ctx->rep_plan;
-    PlanKey key;
-    if (host) {
-        for (int64_t i = 0; i < nchunks; ++i) {
-            const sec_rep_chunk &c = chunks[i];
-            key.put(c.B);
-            key.put(c.ntargets);
-            key.put(c.k);
-            key.put(c.m);
-            key.put(sharenums + c.slot0, (size_t)c.k * 4);
-            if (c.ntargets)
-                key.put(target_nums + c.tgt0, (size_t)c.ntargets * 4);
-        }
-    } else {
-        key.put(chunks, sizeof(sec_rep_chunk) * (size_t)nchunks);
-        key.put(sharenums, total_slots * 4);
-        key.put(block_offs, total_slots * 8);
-        if (block_avail)
-            key.put(block_avail, total_slots * 8);
-        key.put(target_nums, total_tgts * 4);
-        key.put(target_offs, total_tgts * 8);
-    }
-    key.put((host ? SEC_F_HOST : 0u) | (!host && block_avail ? 0x10000u : 0u) | (digest ? 0x20000u : 0u));
-    const bool reuse = plan_reusable(plan, ctx->rep_tabs, key);
-    SlotLayout L;
-    if (!reuse || host)
-        L = slot_layout(chunks, nchunks, sharenums);
-    if (!reuse) {
-        plan.valid = false;
-        RC(build_repair_plan(ctx, chunks, nchunks, block_offs, block_avail, target_nums, target_offs, L, host, digest));
-        plan.key.swap(key.bytes);
-        plan.valid = true;
-    }
-
-    if (!host) {
-        hipEvent_t t0 = nullptr;
-        RC(timing_begin(ctx, &t0, ctx->stream()));
-        RC(launch_repair_sub(ctx, plan, plan.subs[0], blocks, out, digests, ctx->stream()));
-        RC(timing_end(ctx, t0, 4, ctx->stream()));
-        if (!(flags & SEC_F_ASYNC))
-            CK(hipStreamSynchronize(ctx->stream()));
-        return SEC_OK;
-    }
-    // Host mode is always staged: the sources are gathered into pinned slabs, the targets (and
-    // digests) scattered back; a caller's buffer is never page-locked (no HostLock) nor used in
-    // place.
-    ++ctx->staged_calls;
-    auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        gather_slots(chunks, sp.c0, sp.c1, L, block_offs, block_avail, blocks, stage, jobs);
-    };
-    auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        uint64_t o = 0, g = sp.dig_off;
-        for (int64_t i = sp.c0; i < sp.c1; ++i) {
-            const sec_rep_chunk &c = chunks[i];
-            for (int r = 0; r < c.ntargets; ++r) {
-                jobs.push_back(sec::CopyJob{(void *)((uintptr_t)out + target_offs[c.tgt0 + r]), stage + o, c.B});
-                o += c.B;
-                if (digest) {
-                    jobs.push_back(sec::CopyJob{digests + 20 * (c.tgt0 + (uint64_t)r), stage + g, 20});
-                    g += 20;
-                }
-            }
-        }
-    };
-    auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
-        return launch_repair_sub(ctx, plan, sp, din, dout, dout + sp.dig_off, s);
-    };
-    return run_pipeline(ctx, plan, gather, scatter, launch);
+    return row_op<RepairOp>(ctx, chunks, nchunks,
+                            RowArgs{sharenums, block_offs, block_avail, blocks, target_nums, target_offs, out, digests,
+                                    nullptr, nullptr, nullptr, flags});
 }
 
-// ---- check: the held pieces of a chunk against each other ---------------------------------
 int sec_check_batch(sec_ctx *ctx, const sec_chk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
                     const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
                     sec_chk_result *results, uint8_t *row_bad, uint8_t *column, unsigned flags)
 {
     static_assert(sizeof(sec_chk_result) == sizeof(sec::ChkResult) && sizeof(sec_chk_chunk) == 32, "ABI layout");
-    if (!ctx || nchunks < 0 || (nchunks > 0 && (!chunks || !sharenums || !block_offs || !results)) ||
-        (flags & ~(SEC_F_HOST | SEC_F_ASYNC)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
-        return SEC_EINVAL;
-    if (nchunks == 0)
-        return SEC_OK;
-    if (nchunks >= (int64_t)UINT32_MAX)
-        return SEC_EINVAL;
-    const bool host = flags & SEC_F_HOST;
-    RC(set_dev(ctx));
-
-    // preconditions of every chunk before any device work
-    uint64_t total_slots = 0;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const sec_chk_chunk &c = chunks[i];
-        RC(check_check(c.k, c.m, sharenums + c.slot0, c.n));
-        if (c.B >= (1ull << 31))
-            return SEC_ESIZE;
-        total_slots = std::max<uint64_t>(total_slots, c.slot0 + (uint64_t)c.n);
-    }
-    if (total_slots >= UINT32_MAX)
-        return SEC_EINVAL;
-    // (blocks may be NULL: block_offs are then absolute addresses)
-
-    // Plan key: host mode keys on shapes and sharenums only (its entries are staged densely,
-    // zero-filled past their avail); device mode on every descriptor, sharenum, address and avail.
-    // The outputs' addresses are launch arguments, not part of the plan.
-    Plan &plan = ctx->chk_plan;
-    PlanKey key;
-    if (host) {
-        for (int64_t i = 0; i < nchunks; ++i) {
-            const sec_chk_chunk &c = chunks[i];
-            key.put(c.B);
-            key.put(c.n);
-            key.put(c.k);
-            key.put(c.m);
-            key.put(sharenums + c.slot0, (size_t)c.n * 4);
-        }
-    } else {
-        key.put(chunks, sizeof(sec_chk_chunk) * (size_t)nchunks);
-        key.put(sharenums, total_slots * 4);
-        key.put(block_offs, total_slots * 8);
-        if (block_avail)
-            key.put(block_avail, total_slots * 8);
-    }
-    key.put((host ? SEC_F_HOST : 0u) | (!host && block_avail ? 0x10000u : 0u));
-    const bool reuse = plan_reusable(plan, ctx->chk_tabs, key);
-    SlotLayout L;
-    if (!reuse || host)
-        L = slot_layout(chunks, nchunks, sharenums);
-    if (!reuse) {
-        plan.valid = false;
-        RC(build_check_plan(ctx, chunks, nchunks, sharenums, block_offs, block_avail, L, host));
-        plan.key.swap(key.bytes);
-        plan.valid = true;
-    }
-    // every call starts from clean flag words (0xFFFFFFFF: no position yet, row agrees), whatever
-    // the last call on this plan found
-    RC(ctx->chk_flags.ensure((size_t)plan.nflags * 4));
-    CK(hipMemsetAsync(ctx->chk_flags.p, 0xFF, (size_t)plan.nflags * 4, ctx->stream()));
-
-    if (!host) {
-        RC(launch_check_sub(ctx, plan, plan.subs[0], blocks, (sec::ChkResult *)results, row_bad, column,
-                            ctx->stream()));
-        if (!(flags & SEC_F_ASYNC))
-            CK(hipStreamSynchronize(ctx->stream()));
-        return SEC_OK;
-    }
-    // Host mode is always staged, as repair's: all n entries are gathered into pinned slabs, only
-    // the results come back.  column passes through a buffer of its own so that a consistent
-    // chunk's bytes stay untouched.
-    ++ctx->staged_calls;
-    std::vector<uint8_t> col(column ? (size_t)total_slots : 0);
-    auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        uint64_t o = 0;
-        for (int64_t i = sp.c0; i < sp.c1; ++i) {
-            const sec_chk_chunk &c = chunks[i];
-            for (int e = 0; e < c.n; ++e) {
-                const int from = e < c.k ? L.perm[L.first[i] + e] : e;
-                const uint64_t av = slot_avail(c, block_avail, from);
-                jobs.push_back(sec::CopyJob{stage + o, (const void *)((uintptr_t)blocks + block_offs[c.slot0 + from]), av});
-                if (av < c.B)  // the entry's bytes past its avail are zero
-                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
-                o += c.B;
-            }
-        }
-    };
-    auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        jobs.push_back(sec::CopyJob{results + sp.c0, stage, (uint64_t)(sp.c1 - sp.c0) * sizeof(sec_chk_result)});
-        uint64_t o = 0;
-        for (int64_t i = sp.c0; i < sp.c1; ++i) {
-            const sec_chk_chunk &c = chunks[i];
-            if (row_bad)
-                jobs.push_back(sec::CopyJob{row_bad + c.slot0, stage + sp.chk_rows + o, (uint64_t)c.n});
-            if (column)
-                jobs.push_back(sec::CopyJob{col.data() + c.slot0, stage + sp.chk_col + o, (uint64_t)c.n});
-            o += (uint64_t)c.n;
-        }
-    };
-    auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
-        return launch_check_sub(ctx, plan, sp, din, (sec::ChkResult *)dout, row_bad ? dout + sp.chk_rows : nullptr,
-                                column ? dout + sp.chk_col : nullptr, s);
-    };
-    RC(run_pipeline(ctx, plan, gather, scatter, launch));
-    if (column)
-        for (int64_t i = 0; i < nchunks; ++i)
-            if (results[i].first != UINT64_MAX)
-                memcpy(column + chunks[i].slot0, col.data() + chunks[i].slot0, (size_t)chunks[i].n);
-    return SEC_OK;
+    return row_op<CheckOp>(ctx, chunks, nchunks,
+                           RowArgs{sharenums, block_offs, block_avail, blocks, nullptr, nullptr, nullptr, nullptr,
+                                   results, row_bad, column, flags});
 }
 
-// ---- decode + check: reassemble and check the spare pieces in one pass ---------------------
 int sec_decode_check_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
                            const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
                            uint8_t *out, sec_chk_result *results, uint8_t *row_bad, uint8_t *column, unsigned flags)
 {
     static_assert(sizeof(sec_dchk_chunk) == 48 && sizeof(sec::DChkDesc) == 48, "ABI layout");
-    if (!ctx || nchunks < 0 || (nchunks > 0 && (!chunks || !sharenums || !block_offs || !results)) ||
-        (flags & ~(SEC_F_HOST | SEC_F_ASYNC | SEC_F_RECOVER)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
-        return SEC_EINVAL;
-    if (nchunks == 0)
-        return SEC_OK;
-    if (nchunks >= (int64_t)UINT32_MAX)
-        return SEC_EINVAL;
-    const bool host = flags & SEC_F_HOST;
-    const bool recover = flags & SEC_F_RECOVER;
-    RC(set_dev(ctx));
-
-    // preconditions of every chunk before any device work; SEC_EINVAL's first: n < 0, and a NULL
-    // `out` where a chunk has bytes to write (judged only where the chunk's k sharenums can be read)
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const sec_dchk_chunk &c = chunks[i];
-        if (c.n < 0)
-            return SEC_EINVAL;
-        if (out || c.k < 1 || c.k > 256 || c.n < c.k || c.B == 0)
-            continue;
-        if (!recover && (uint64_t)c.k * c.B > c.padlen)
-            return SEC_EINVAL;
-        for (int j = 0; recover && j < c.k; ++j)
-            if (sharenums[c.slot0 + j] < 0 || sharenums[c.slot0 + j] >= c.k)
-                return SEC_EINVAL;  // a basis entry that is no primary: a primary is recovered
-    }
-    uint64_t total_slots = 0;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const sec_dchk_chunk &c = chunks[i];
-        RC(check_check(c.k, c.m, sharenums + c.slot0, c.n));
-        if (c.padlen > (uint64_t)c.k * c.B)
-            return SEC_EPADLEN;
-        if (c.B >= (1ull << 31))
-            return SEC_ESIZE;
-        total_slots = std::max<uint64_t>(total_slots, c.slot0 + (uint64_t)c.n);
-    }
-    if (total_slots >= UINT32_MAX)
-        return SEC_EINVAL;
-    // (blocks may be NULL: block_offs are then absolute addresses)
-
-    // Plan key, as sec_check_batch's with the decode's fields: host mode keys on shapes, padlen and
-    // sharenums only; device mode on every descriptor, sharenum, address and avail.
-    Plan &plan = ctx->dchk_plan;
-    PlanKey key;
-    if (host) {
-        for (int64_t i = 0; i < nchunks; ++i) {
-            const sec_dchk_chunk &c = chunks[i];
-            key.put(c.B);
-            key.put(c.padlen);
-            key.put(c.n);
-            key.put(c.k);
-            key.put(c.m);
-            key.put(sharenums + c.slot0, (size_t)c.n * 4);
-        }
-    } else {
-        key.put(chunks, sizeof(sec_dchk_chunk) * (size_t)nchunks);
-        key.put(sharenums, total_slots * 4);
-        key.put(block_offs, total_slots * 8);
-        if (block_avail)
-            key.put(block_avail, total_slots * 8);
-    }
-    key.put((flags & (SEC_F_HOST | SEC_F_RECOVER)) | (!host && block_avail ? 0x10000u : 0u));
-    const bool reuse = plan_reusable(plan, ctx->dchk_tabs, key);
-    SlotLayout L;
-    if (!reuse || host)
-        L = slot_layout(chunks, nchunks, sharenums);
-    if (!reuse) {
-        plan.valid = false;
-        RC(build_decode_check_plan(ctx, chunks, nchunks, sharenums, block_offs, block_avail, L, host, recover));
-        plan.key.swap(key.bytes);
-        plan.valid = true;
-    }
-    // every call starts from clean flag words, whatever the last call on this plan found
-    RC(ctx->dchk_flags.ensure((size_t)plan.nflags * 4));
-    CK(hipMemsetAsync(ctx->dchk_flags.p, 0xFF, (size_t)plan.nflags * 4, ctx->stream()));
-
-    if (!host) {
-        RC(launch_decode_check_sub(ctx, plan, plan.subs[0], blocks, out, (sec::ChkResult *)results, row_bad, column,
-                                   ctx->stream()));
-        if (!(flags & SEC_F_ASYNC))
-            CK(hipStreamSynchronize(ctx->stream()));
-        return SEC_OK;
-    }
-    // Host mode is always staged, as sec_check_batch's: all n entries of a chunk are gathered into
-    // pinned slabs ONCE and feed both the decode and the check; the decoded bytes (recover-only:
-    // the recovered rows) and the results come back.  column passes through a buffer of its own so
-    // that a consistent chunk's bytes stay untouched.
-    ++ctx->staged_calls;
-    std::vector<uint8_t> col(column ? (size_t)total_slots : 0);
-    auto nout = [&](const sec_dchk_chunk &c) -> uint64_t {
-        if (!recover)
-            return (uint64_t)c.k * c.B - c.padlen;
-        uint64_t e = 0;
-        for (int j = 0; j < c.k; ++j)
-            e += sharenums[c.slot0 + j] >= c.k;
-        return e * c.B;
-    };
-    auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        uint64_t o = 0;
-        for (int64_t i = sp.c0; i < sp.c1; ++i) {
-            const sec_dchk_chunk &c = chunks[i];
-            for (int e = 0; e < c.n; ++e) {
-                const int from = e < c.k ? L.perm[L.first[i] + e] : e;
-                const uint64_t av = slot_avail(c, block_avail, from);
-                jobs.push_back(sec::CopyJob{stage + o, (const void *)((uintptr_t)blocks + block_offs[c.slot0 + from]), av});
-                if (av < c.B)  // the entry's bytes past its avail are zero
-                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
-                o += c.B;
-            }
-        }
-    };
-    auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        jobs.push_back(sec::CopyJob{results + sp.c0, stage, (uint64_t)(sp.c1 - sp.c0) * sizeof(sec_chk_result)});
-        uint64_t o = 0, b = sp.dchk_out;
-        for (int64_t i = sp.c0; i < sp.c1; ++i) {
-            const sec_dchk_chunk &c = chunks[i];
-            if (row_bad)
-                jobs.push_back(sec::CopyJob{row_bad + c.slot0, stage + sp.chk_rows + o, (uint64_t)c.n});
-            if (column)
-                jobs.push_back(sec::CopyJob{col.data() + c.slot0, stage + sp.chk_col + o, (uint64_t)c.n});
-            o += (uint64_t)c.n;
-            const uint64_t nb = nout(c);
-            if (nb)
-                jobs.push_back(sec::CopyJob{(void *)((uintptr_t)out + c.out_off), stage + b, nb});
-            b += nb;
-        }
-    };
-    auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
-        return launch_decode_check_sub(ctx, plan, sp, din, dout, (sec::ChkResult *)dout,
-                                       row_bad ? dout + sp.chk_rows : nullptr, column ? dout + sp.chk_col : nullptr, s);
-    };
-    RC(run_pipeline(ctx, plan, gather, scatter, launch));
-    if (column)
-        for (int64_t i = 0; i < nchunks; ++i)
-            if (results[i].first != UINT64_MAX)
-                memcpy(column + chunks[i].slot0, col.data() + chunks[i].slot0, (size_t)chunks[i].n);
-    return SEC_OK;
+    return row_op<DecodeCheckOp>(ctx, chunks, nchunks,
+                                 RowArgs{sharenums, block_offs, block_avail, blocks, nullptr, nullptr, out, nullptr,
+                                         results, row_bad, column, flags});
 }
 
-// ---- repair + check: regenerate lost pieces and check the spare ones in one pass -------------
 int sec_repair_check_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
                            const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
                            const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out, uint8_t *digests,
                            sec_chk_result *results, uint8_t *row_bad, uint8_t *column, unsigned flags)
 {
     static_assert(sizeof(sec_rchk_chunk) == 40 && sizeof(sec::RChkDesc) == 40, "ABI layout");
-    if (!ctx || nchunks < 0 || (nchunks > 0 && (!chunks || !sharenums || !block_offs || !results)) ||
-        (flags & ~(SEC_F_HOST | SEC_F_ASYNC)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
-        return SEC_EINVAL;
-    if (nchunks == 0)
-        return SEC_OK;
-    if (nchunks >= (int64_t)UINT32_MAX)
-        return SEC_EINVAL;
-    const bool host = flags & SEC_F_HOST;
-    const bool digest = digests != nullptr;
-    RC(set_dev(ctx));
-
-    // preconditions of every chunk before any device work; SEC_EINVAL's first
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const sec_rchk_chunk &c = chunks[i];
-        if (c.n < 0 || c.ntargets < 0 || (c.ntargets > 0 && (!target_nums || !target_offs)))
-            return SEC_EINVAL;
-    }
-    uint64_t total_slots = 0, total_tgts = 0;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const sec_rchk_chunk &c = chunks[i];
-        RC(check_repair_check(c.k, c.m, sharenums + c.slot0, c.n, c.ntargets ? target_nums + c.tgt0 : nullptr,
-                              c.ntargets));
-        if (c.B >= (1ull << 31))
-            return SEC_ESIZE;
-        total_slots = std::max<uint64_t>(total_slots, c.slot0 + (uint64_t)c.n);
-        if (c.ntargets)
-            total_tgts = std::max<uint64_t>(total_tgts, c.tgt0 + (uint64_t)c.ntargets);
-    }
-    if (total_slots >= UINT32_MAX || total_tgts >= UINT32_MAX)
-        return SEC_EINVAL;
-    // (blocks and out may be NULL: block_offs / target_offs are then absolute addresses)
-
-    // Plan key, as sec_repair_batch's with the check's entries: host mode keys on shapes, sharenums
-    // and targets only (its entries are staged densely, zero-filled past their avail, its targets
-    // dense in the slab); device mode on every descriptor, sharenum, target, address and avail.
-    // The results' addresses are launch arguments, not part of the plan.
-    Plan &plan = ctx->rchk_plan;
-    PlanKey key;
-    if (host) {
-        for (int64_t i = 0; i < nchunks; ++i) {
-            const sec_rchk_chunk &c = chunks[i];
-            key.put(c.B);
-            key.put(c.ntargets);
-            key.put(c.n);
-            key.put(c.k);
-            key.put(c.m);
-            key.put(sharenums + c.slot0, (size_t)c.n * 4);
-            if (c.ntargets)
-                key.put(target_nums + c.tgt0, (size_t)c.ntargets * 4);
-        }
-    } else {
-        key.put(chunks, sizeof(sec_rchk_chunk) * (size_t)nchunks);
-        key.put(sharenums, total_slots * 4);
-        key.put(block_offs, total_slots * 8);
-        if (block_avail)
-            key.put(block_avail, total_slots * 8);
-        if (total_tgts) {
-            key.put(target_nums, total_tgts * 4);
-            key.put(target_offs, total_tgts * 8);
-        }
-    }
-    key.put((host ? SEC_F_HOST : 0u) | (!host && block_avail ? 0x10000u : 0u) | (digest ? 0x20000u : 0u));
-    const bool reuse = plan_reusable(plan, ctx->rchk_tabs, key);
-    SlotLayout L;
-    if (!reuse || host)
-        L = slot_layout(chunks, nchunks, sharenums);
-    if (!reuse) {
-        plan.valid = false;
-        RC(build_repair_check_plan(ctx, chunks, nchunks, sharenums, block_offs, block_avail, target_nums, target_offs,
-                                   L, host, digest));
-        plan.key.swap(key.bytes);
-        plan.valid = true;
-    }
-    // every call starts from clean flag words, whatever the last call on this plan found
-    RC(ctx->rchk_flags.ensure((size_t)plan.nflags * 4));
-    CK(hipMemsetAsync(ctx->rchk_flags.p, 0xFF, (size_t)plan.nflags * 4, ctx->stream()));
-
-    if (!host) {
-        RC(launch_repair_check_sub(ctx, plan, plan.subs[0], blocks, out, digests, (sec::ChkResult *)results, row_bad,
-                                   column, ctx->stream()));
-        if (!(flags & SEC_F_ASYNC))
-            CK(hipStreamSynchronize(ctx->stream()));
-        return SEC_OK;
-    }
-    // Host mode is always staged, as sec_check_batch's: all n entries of a chunk are gathered into
-    // pinned slabs ONCE and feed both the repair and the check; the targets, their digests and the
-    // results come back.  column passes through a buffer of its own so that a consistent chunk's
-    // bytes stay untouched.
-    ++ctx->staged_calls;
-    std::vector<uint8_t> col(column ? (size_t)total_slots : 0);
-    auto gather = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        uint64_t o = 0;
-        for (int64_t i = sp.c0; i < sp.c1; ++i) {
-            const sec_rchk_chunk &c = chunks[i];
-            for (int e = 0; e < c.n; ++e) {
-                const int from = e < c.k ? L.perm[L.first[i] + e] : e;
-                const uint64_t av = slot_avail(c, block_avail, from);
-                jobs.push_back(sec::CopyJob{stage + o, (const void *)((uintptr_t)blocks + block_offs[c.slot0 + from]), av});
-                if (av < c.B)  // the entry's bytes past its avail are zero
-                    jobs.push_back(sec::CopyJob{stage + o + av, nullptr, c.B - av});
-                o += c.B;
-            }
-        }
-    };
-    auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        jobs.push_back(sec::CopyJob{results + sp.c0, stage, (uint64_t)(sp.c1 - sp.c0) * sizeof(sec_chk_result)});
-        uint64_t o = 0, b = sp.rchk_out, g = sp.dig_off;
-        for (int64_t i = sp.c0; i < sp.c1; ++i) {
-            const sec_rchk_chunk &c = chunks[i];
-            if (row_bad)
-                jobs.push_back(sec::CopyJob{row_bad + c.slot0, stage + sp.chk_rows + o, (uint64_t)c.n});
-            if (column)
-                jobs.push_back(sec::CopyJob{col.data() + c.slot0, stage + sp.chk_col + o, (uint64_t)c.n});
-            o += (uint64_t)c.n;
-            for (int r = 0; r < c.ntargets; ++r) {
-                jobs.push_back(sec::CopyJob{(void *)((uintptr_t)out + target_offs[c.tgt0 + r]), stage + b, c.B});
-                b += c.B;
-                if (digest) {
-                    jobs.push_back(sec::CopyJob{digests + 20 * (c.tgt0 + (uint64_t)r), stage + g, 20});
-                    g += 20;
-                }
-            }
-        }
-    };
-    auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
-        return launch_repair_check_sub(ctx, plan, sp, din, dout, dout + sp.dig_off, (sec::ChkResult *)dout,
-                                       row_bad ? dout + sp.chk_rows : nullptr, column ? dout + sp.chk_col : nullptr, s);
-    };
-    RC(run_pipeline(ctx, plan, gather, scatter, launch));
-    if (column)
-        for (int64_t i = 0; i < nchunks; ++i)
-            if (results[i].first != UINT64_MAX)
-                memcpy(column + chunks[i].slot0, col.data() + chunks[i].slot0, (size_t)chunks[i].n);
-    return SEC_OK;
+    return row_op<RepairCheckOp>(ctx, chunks, nchunks,
+                                 RowArgs{sharenums, block_offs, block_avail, blocks, target_nums, target_offs, out,
+                                         digests, results, row_bad, column, flags});
 }
 
 int sec_check_locate(int k, int m, const int32_t *sharenums, int n, const uint8_t *column, int32_t *culprit)
 {
-    RC(check_repair(k, m, sharenums, sharenums ? sharenums + k : nullptr, n - k));
+    RC(check_blocks(k, m, sharenums, k, sharenums ? sharenums + k : nullptr, n - k, true));
     if (!column || !culprit)
         return SEC_EINVAL;
     int who = -2;

@@ -28,6 +28,8 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "kernels.hpp"
 
 using u8 = uint8_t;
@@ -2011,161 +2013,72 @@ hipError_t launch(K kernel, dim3 grid, dim3 block, hipStream_t s, A... args)
     return launch_shm(kernel, grid, block, 0, s, args...);
 }
 
-template <int R, int U, bool W>
-hipError_t launch_enc(const u8 *in, u8 *par, const sec::EncDesc *descs, const sec::Tile *tiles, u32 ntiles,
-                      const u32 *tabs, u32 lanes, hipStream_t s)
+// rows -> f(std::integral_constant<int, R>), R in [R0, 8] (the row counts the tile kernels are built for)
+template <int R0, class F>
+hipError_t with_rows(int rows, F f)
 {
-    return launch_shm(sec_encode_kernel<R, U, W>, dim3(ntiles), dim3(lanes),
-                      lds_tab_bytes<batch_blocks<U, W, false>(), R, false>(lanes), s, in, par, descs, tiles, tabs);
-}
-
-template <int R, int U, bool W, int KBX>
-hipError_t launch_dec(const u8 *blocks, u8 *out, const sec::DecDesc *descs, const sec::Tile *tiles, u32 ntiles,
-                      const u32 *tabs, sec::DecSlots sl, u32 lanes, hipStream_t s)
-{
-    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
-    return launch_shm(sec_decode_kernel<R, U, W, KBX>, dim3(ntiles), dim3(lanes),
-                      lds_tab_bytes<KB, R, true>(lanes), s, blocks, out, descs, tiles, tabs, sl);
+    switch (rows) {
+    case 0:
+        if constexpr (R0 == 0)
+            return f(std::integral_constant<int, 0>{});
+        return hipErrorInvalidValue;
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return hipErrorInvalidValue;
+    }
 }
 
 template <int U, bool W>
 hipError_t dispatch_enc(int rows, const u8 *in, u8 *par, const sec::EncDesc *d, const sec::Tile *t, u32 nt,
                         const u32 *tabs, u32 lanes, hipStream_t s)
 {
-    switch (rows) {
-    case 1: return launch_enc<1, U, W>(in, par, d, t, nt, tabs, lanes, s);
-    case 2: return launch_enc<2, U, W>(in, par, d, t, nt, tabs, lanes, s);
-    case 3: return launch_enc<3, U, W>(in, par, d, t, nt, tabs, lanes, s);
-    case 4: return launch_enc<4, U, W>(in, par, d, t, nt, tabs, lanes, s);
-    case 5: return launch_enc<5, U, W>(in, par, d, t, nt, tabs, lanes, s);
-    case 6: return launch_enc<6, U, W>(in, par, d, t, nt, tabs, lanes, s);
-    case 7: return launch_enc<7, U, W>(in, par, d, t, nt, tabs, lanes, s);
-    case 8: return launch_enc<8, U, W>(in, par, d, t, nt, tabs, lanes, s);
-    default: return hipErrorInvalidValue;
+    return with_rows<1>(rows, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        return launch_shm(sec_encode_kernel<R, U, W>, dim3(nt), dim3(lanes),
+                          lds_tab_bytes<batch_blocks<U, W, false>(), R, false>(lanes), s, in, par, d, t, tabs);
+    });
+}
+
+// The tile kernels that take (blocks[, out], descs, tiles, tabs, slots), by descriptor type: the
+// kernel of R rows, the lowest R built, the tail kernel, and whether there is an `out`.
+template <class Desc>
+struct RowKernels;
+#define SEC_ROW_KERNELS(Desc, R0, OUT, TILE, TAIL)                                 \
+    template <>                                                                    \
+    struct RowKernels<sec::Desc> {                                                 \
+        static constexpr int kRows0 = R0;                                          \
+        static constexpr bool kOut = OUT;                                          \
+        template <int R, bool W, int KBX>                                          \
+        static constexpr auto tile() { return TILE<R, 1, W, KBX>; }                \
+        static constexpr auto tail() { return TAIL; }                              \
     }
-}
+SEC_ROW_KERNELS(DecDesc, 0, true, sec_decode_kernel, sec_decode_tail);
+SEC_ROW_KERNELS(RepDesc, 1, true, sec_repair_kernel, sec_repair_tail);
+SEC_ROW_KERNELS(ChkDesc, 1, false, sec_check_kernel, sec_check_tail);
+SEC_ROW_KERNELS(DChkDesc, 0, true, sec_decode_check_kernel, sec_decode_check_tail);
+SEC_ROW_KERNELS(RChkDesc, 1, true, sec_repair_check_kernel, sec_repair_check_tail);
+#undef SEC_ROW_KERNELS
 
-template <int U, bool W, int KBX = 0>
-hipError_t dispatch_dec(int rows, const u8 *b, u8 *o, const sec::DecDesc *d, const sec::Tile *t, u32 nt,
-                        const u32 *tabs, sec::DecSlots sl, u32 lanes, hipStream_t s)
+template <bool W, int KBX, class Desc, class Slots>
+hipError_t dispatch_rows(int rows, const u8 *b, u8 *o, const Desc *d, const sec::Tile *t, u32 nt, const u32 *tabs,
+                         Slots sl, u32 lanes, hipStream_t s)
 {
-    switch (rows) {
-    case 0: return launch_dec<0, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 1: return launch_dec<1, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 2: return launch_dec<2, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 3: return launch_dec<3, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 4: return launch_dec<4, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 5: return launch_dec<5, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 6: return launch_dec<6, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 7: return launch_dec<7, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 8: return launch_dec<8, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int R, int U, bool W, int KBX>
-hipError_t launch_rep(const u8 *blocks, u8 *out, const sec::RepDesc *descs, const sec::Tile *tiles, u32 ntiles,
-                      const u32 *tabs, sec::RepSlots sl, u32 lanes, hipStream_t s)
-{
-    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
-    return launch_shm(sec_repair_kernel<R, U, W, KBX>, dim3(ntiles), dim3(lanes),
-                      lds_tab_bytes<KB, R, true>(lanes), s, blocks, out, descs, tiles, tabs, sl);
-}
-
-template <int U, bool W, int KBX = 0>
-hipError_t dispatch_rep(int rows, const u8 *b, u8 *o, const sec::RepDesc *d, const sec::Tile *t, u32 nt,
-                        const u32 *tabs, sec::RepSlots sl, u32 lanes, hipStream_t s)
-{
-    switch (rows) {
-    case 1: return launch_rep<1, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 2: return launch_rep<2, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 3: return launch_rep<3, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 4: return launch_rep<4, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 5: return launch_rep<5, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 6: return launch_rep<6, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 7: return launch_rep<7, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 8: return launch_rep<8, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int R, int U, bool W, int KBX>
-hipError_t launch_chk(const u8 *blocks, const sec::ChkDesc *descs, const sec::Tile *tiles, u32 ntiles, const u32 *tabs,
-                      sec::ChkSlots sl, u32 lanes, hipStream_t s)
-{
-    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
-    return launch_shm(sec_check_kernel<R, U, W, KBX>, dim3(ntiles), dim3(lanes), lds_tab_bytes<KB, R, true>(lanes), s,
-                      blocks, descs, tiles, tabs, sl);
-}
-
-template <int U, bool W, int KBX = 0>
-hipError_t dispatch_chk(int rows, const u8 *b, const sec::ChkDesc *d, const sec::Tile *t, u32 nt, const u32 *tabs,
-                        sec::ChkSlots sl, u32 lanes, hipStream_t s)
-{
-    switch (rows) {
-    case 1: return launch_chk<1, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
-    case 2: return launch_chk<2, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
-    case 3: return launch_chk<3, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
-    case 4: return launch_chk<4, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
-    case 5: return launch_chk<5, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
-    case 6: return launch_chk<6, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
-    case 7: return launch_chk<7, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
-    case 8: return launch_chk<8, U, W, KBX>(b, d, t, nt, tabs, sl, lanes, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int R, int U, bool W, int KBX>
-hipError_t launch_dchk(const u8 *blocks, u8 *out, const sec::DChkDesc *descs, const sec::Tile *tiles, u32 ntiles,
-                       const u32 *tabs, sec::DChkSlots sl, u32 lanes, hipStream_t s)
-{
-    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
-    return launch_shm(sec_decode_check_kernel<R, U, W, KBX>, dim3(ntiles), dim3(lanes),
-                      lds_tab_bytes<KB, R, true>(lanes), s, blocks, out, descs, tiles, tabs, sl);
-}
-
-template <int U, bool W, int KBX = 0>
-hipError_t dispatch_dchk(int rows, const u8 *b, u8 *o, const sec::DChkDesc *d, const sec::Tile *t, u32 nt,
-                         const u32 *tabs, sec::DChkSlots sl, u32 lanes, hipStream_t s)
-{
-    switch (rows) {
-    case 0: return launch_dchk<0, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 1: return launch_dchk<1, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 2: return launch_dchk<2, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 3: return launch_dchk<3, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 4: return launch_dchk<4, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 5: return launch_dchk<5, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 6: return launch_dchk<6, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 7: return launch_dchk<7, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 8: return launch_dchk<8, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int R, int U, bool W, int KBX>
-hipError_t launch_rchk(const u8 *blocks, u8 *out, const sec::RChkDesc *descs, const sec::Tile *tiles, u32 ntiles,
-                       const u32 *tabs, sec::RChkSlots sl, u32 lanes, hipStream_t s)
-{
-    constexpr int KB = KBX > 0 ? KBX : batch_blocks<U, W, true>();
-    return launch_shm(sec_repair_check_kernel<R, U, W, KBX>, dim3(ntiles), dim3(lanes),
-                      lds_tab_bytes<KB, R, true>(lanes), s, blocks, out, descs, tiles, tabs, sl);
-}
-
-template <int U, bool W, int KBX = 0>
-hipError_t dispatch_rchk(int rows, const u8 *b, u8 *o, const sec::RChkDesc *d, const sec::Tile *t, u32 nt,
-                         const u32 *tabs, sec::RChkSlots sl, u32 lanes, hipStream_t s)
-{
-    switch (rows) {
-    case 1: return launch_rchk<1, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 2: return launch_rchk<2, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 3: return launch_rchk<3, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 4: return launch_rchk<4, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 5: return launch_rchk<5, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 6: return launch_rchk<6, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 7: return launch_rchk<7, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    case 8: return launch_rchk<8, U, W, KBX>(b, o, d, t, nt, tabs, sl, lanes, s);
-    default: return hipErrorInvalidValue;
-    }
+    using K = RowKernels<Desc>;
+    return with_rows<K::kRows0>(rows, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        constexpr int KB = KBX > 0 ? KBX : batch_blocks<1, W, true>();
+        const u32 shm = lds_tab_bytes<KB, R, true>(lanes);
+        if constexpr (K::kOut)
+            return launch_shm(K::template tile<R, W, KBX>(), dim3(nt), dim3(lanes), shm, s, b, o, d, t, tabs, sl);
+        else
+            return launch_shm(K::template tile<R, W, KBX>(), dim3(nt), dim3(lanes), shm, s, b, d, t, tabs, sl);
+    });
 }
 
 }  // namespace
@@ -2219,29 +2132,48 @@ int sec_launch_encode_tail(const uint8_t *in, uint8_t *par, const sec::EncDesc *
                   nitems, tabs);
 }
 
-int sec_launch_decode(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
-                      const sec::DecDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
-                      sec::DecSlots sl, void *stream, int kb)
+template <class Desc, class Slots>
+int sec_launch_rows(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out, const Desc *descs,
+                    const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs, Slots sl, void *stream, int kb)
 {
     if (ntiles == 0)
         return hipSuccess;
-    if (lanes < 64 || lanes % 64 || lanes > sec::max_lanes(rows, U) || (wide && U != 1))
+    if (rows < RowKernels<Desc>::kRows0 || U != 1 || lanes < 64 || lanes % 64 || lanes > sec::max_lanes(rows, U))
         return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
     const u32 L = (u32)lanes;
-    if (kb) {  // small load batches: U = 1 tiles of chunks with k <= kb only
-        if (U != 1 || wide)
+    if (kb) {  // small load batches: tiles of chunks with k <= kb only
+        if (wide || kb != 4)
             return hipErrorInvalidValue;
-        if (kb == 4)
-            return dispatch_dec<1, false, 4>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-        return hipErrorInvalidValue;
+        return dispatch_rows<false, 4>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
     }
     if (wide)
-        return dispatch_dec<1, true>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-    if (U != 1)
-        return hipErrorInvalidValue;
-    return dispatch_dec<1, false>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
+        return dispatch_rows<true, 0>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
+    return dispatch_rows<false, 0>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
 }
+
+template <class Desc, class Slots>
+int sec_launch_rows_tail(const uint8_t *blocks, uint8_t *out, const Desc *descs, const sec::TailItem *items,
+                         uint32_t nitems, const uint32_t *tabs, Slots sl, void *stream)
+{
+    if (nitems == 0)
+        return hipSuccess;
+    using K = RowKernels<Desc>;
+    const dim3 grid((nitems + 255) / 256), block(256);
+    if constexpr (K::kOut)
+        return launch(K::tail(), grid, block, (hipStream_t)stream, blocks, out, descs, items, nitems, tabs, sl);
+    else
+        return launch(K::tail(), grid, block, (hipStream_t)stream, blocks, descs, items, nitems, tabs, sl);
+}
+
+#define SEC_ROW_LAUNCHERS(Desc, Slots)                                                                              \
+    template int sec_launch_rows(int, int, int, int, const uint8_t *, uint8_t *, const sec::Desc *,                 \
+                                 const sec::Tile *, uint32_t, const uint32_t *, sec::Slots, void *, int);           \
+    template int sec_launch_rows_tail(const uint8_t *, uint8_t *, const sec::Desc *, const sec::TailItem *,         \
+                                      uint32_t, const uint32_t *, sec::Slots, void *)
+// (kernel templates land in the code object in the order of their first use here: the decode's,
+// the SHA-1 kernels, then the other families, as tools/kres.py lists them)
+SEC_ROW_LAUNCHERS(DecDesc, DecSlots);
 
 int sec_launch_sha1(const uint8_t *base0, const uint8_t *base1, const sec::MsgDesc *msgs, uint32_t nmsgs,
                     uint8_t *digests, void *stream, int split)
@@ -2258,74 +2190,11 @@ int sec_launch_sha1(const uint8_t *base0, const uint8_t *base1, const sec::MsgDe
                   nmsgs, digests);
 }
 
-int sec_launch_decode_tail(const uint8_t *blocks, uint8_t *out, const sec::DecDesc *descs,
-                           const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::DecSlots sl,
-                           void *stream)
-{
-    if (nitems == 0)
-        return hipSuccess;
-    return launch(sec_decode_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out, descs,
-                  items, nitems, tabs, sl);
-}
-
-int sec_launch_repair(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
-                      const sec::RepDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
-                      sec::RepSlots sl, void *stream, int kb)
-{
-    if (ntiles == 0)
-        return hipSuccess;
-    if (rows < 1 || U != 1 || lanes < 64 || lanes % 64 || lanes > sec::max_lanes(rows, U))
-        return hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    const u32 L = (u32)lanes;
-    if (kb) {  // small load batches: tiles of chunks with k <= kb only
-        if (wide || kb != 4)
-            return hipErrorInvalidValue;
-        return dispatch_rep<1, false, 4>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-    }
-    if (wide)
-        return dispatch_rep<1, true>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-    return dispatch_rep<1, false>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-}
-
-int sec_launch_repair_tail(const uint8_t *blocks, uint8_t *out, const sec::RepDesc *descs,
-                           const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::RepSlots sl,
-                           void *stream)
-{
-    if (nitems == 0)
-        return hipSuccess;
-    return launch(sec_repair_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out, descs,
-                  items, nitems, tabs, sl);
-}
-
-int sec_launch_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, const sec::ChkDesc *descs,
-                     const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs, sec::ChkSlots sl, void *stream,
-                     int kb)
-{
-    if (ntiles == 0)
-        return hipSuccess;
-    if (rows < 1 || U != 1 || lanes < 64 || lanes % 64 || lanes > sec::max_lanes(rows, U))
-        return hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    const u32 L = (u32)lanes;
-    if (kb) {  // small load batches: tiles of chunks with k <= kb only
-        if (wide || kb != 4)
-            return hipErrorInvalidValue;
-        return dispatch_chk<1, false, 4>(rows, blocks, descs, tiles, ntiles, tabs, sl, L, s);
-    }
-    if (wide)
-        return dispatch_chk<1, true>(rows, blocks, descs, tiles, ntiles, tabs, sl, L, s);
-    return dispatch_chk<1, false>(rows, blocks, descs, tiles, ntiles, tabs, sl, L, s);
-}
-
-int sec_launch_check_tail(const uint8_t *blocks, const sec::ChkDesc *descs, const sec::TailItem *items,
-                          uint32_t nitems, const uint32_t *tabs, sec::ChkSlots sl, void *stream)
-{
-    if (nitems == 0)
-        return hipSuccess;
-    return launch(sec_check_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, descs, items,
-                  nitems, tabs, sl);
-}
+SEC_ROW_LAUNCHERS(RepDesc, RepSlots);
+SEC_ROW_LAUNCHERS(ChkDesc, ChkSlots);
+SEC_ROW_LAUNCHERS(DChkDesc, DChkSlots);
+SEC_ROW_LAUNCHERS(RChkDesc, RChkSlots);
+#undef SEC_ROW_LAUNCHERS
 
 int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uint32_t nentries, sec::ChkSlots sl,
                            sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, void *stream)
@@ -2334,64 +2203,4 @@ int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uin
         return hipSuccess;
     return launch(sec_check_final, dim3((nentries + 255) / 256), dim3(256), (hipStream_t)stream, blocks, descs,
                   nentries, sl, results, row_bad, column);
-}
-
-int sec_launch_decode_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
-                            const sec::DChkDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
-                            sec::DChkSlots sl, void *stream, int kb)
-{
-    if (ntiles == 0)
-        return hipSuccess;
-    if (rows < 0 || U != 1 || lanes < 64 || lanes % 64 || lanes > sec::max_lanes(rows, U))
-        return hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    const u32 L = (u32)lanes;
-    if (kb) {  // small load batches: tiles of chunks with k <= kb only
-        if (wide || kb != 4)
-            return hipErrorInvalidValue;
-        return dispatch_dchk<1, false, 4>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-    }
-    if (wide)
-        return dispatch_dchk<1, true>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-    return dispatch_dchk<1, false>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-}
-
-int sec_launch_decode_check_tail(const uint8_t *blocks, uint8_t *out, const sec::DChkDesc *descs,
-                                 const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::DChkSlots sl,
-                                 void *stream)
-{
-    if (nitems == 0)
-        return hipSuccess;
-    return launch(sec_decode_check_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out,
-                  descs, items, nitems, tabs, sl);
-}
-
-int sec_launch_repair_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
-                            const sec::RChkDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
-                            sec::RChkSlots sl, void *stream, int kb)
-{
-    if (ntiles == 0)
-        return hipSuccess;
-    if (rows < 1 || U != 1 || lanes < 64 || lanes % 64 || lanes > sec::max_lanes(rows, U))
-        return hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    const u32 L = (u32)lanes;
-    if (kb) {  // small load batches: tiles of chunks with k <= kb only
-        if (wide || kb != 4)
-            return hipErrorInvalidValue;
-        return dispatch_rchk<1, false, 4>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-    }
-    if (wide)
-        return dispatch_rchk<1, true>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-    return dispatch_rchk<1, false>(rows, blocks, out, descs, tiles, ntiles, tabs, sl, L, s);
-}
-
-int sec_launch_repair_check_tail(const uint8_t *blocks, uint8_t *out, const sec::RChkDesc *descs,
-                                 const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::RChkSlots sl,
-                                 void *stream)
-{
-    if (nitems == 0)
-        return hipSuccess;
-    return launch(sec_repair_check_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out,
-                  descs, items, nitems, tabs, sl);
 }

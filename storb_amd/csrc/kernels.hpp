@@ -289,49 +289,27 @@ int sec_launch_solve_bs(int shape, int lanes, const uint8_t *syn, uint8_t *out, 
                         const sec::Tile *t, uint32_t ntiles, const uint64_t *masks, void *stream);
 int sec_launch_encode_tail(const uint8_t *in, uint8_t *par, const sec::EncDesc *descs, const sec::TailItem *items,
                            uint32_t nitems, const uint32_t *tabs, void *stream);
-// kb (4): the kernel variant whose load batch is kb slots (every chunk of the group has
-// k <= kb; U = 1, not wide); 0: the default batch
-int sec_launch_decode(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
-                      const sec::DecDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
-                      sec::DecSlots slots, void *stream, int kb = 0);
 // split: sec_sha1_split_kernel (two waves per 64 messages: schedule and rounds) instead of
 // one lane per message
 int sec_launch_sha1(const uint8_t *base0, const uint8_t *base1, const sec::MsgDesc *msgs, uint32_t nmsgs,
                     uint8_t *digests, void *stream, int split = 0);
-int sec_launch_decode_tail(const uint8_t *blocks, uint8_t *out, const sec::DecDesc *descs,
-                           const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::DecSlots slots,
-                           void *stream);
-// Repair (sec_repair_kernel): tiles and arguments as the copy-free decode's (rows 1..8 target rows
-// of the tile's group, kb as sec_launch_decode), every target row stored whole at its own address
-int sec_launch_repair(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
-                      const sec::RepDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
-                      sec::RepSlots slots, void *stream, int kb = 0);
-int sec_launch_repair_tail(const uint8_t *blocks, uint8_t *out, const sec::RepDesc *descs,
-                           const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs, sec::RepSlots slots,
-                           void *stream);
-// Check (sec_check_kernel): tiles and arguments as repair's (rows 1..8 check rows of the tile's
-// group); nothing is stored unless a row differs, then only slots.flags words
-int sec_launch_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, const sec::ChkDesc *descs,
-                     const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs, sec::ChkSlots slots, void *stream,
-                     int kb = 0);
-int sec_launch_check_tail(const uint8_t *blocks, const sec::ChkDesc *descs, const sec::TailItem *items,
-                          uint32_t nitems, const uint32_t *tabs, sec::ChkSlots slots, void *stream);
-// Decode + check (sec_decode_check_kernel): tiles as the decode's over the chunk's e + nr rows
-// (rows 0..8 of the tile's group, kb as sec_launch_decode); the results by sec_launch_check_final
-int sec_launch_decode_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
-                            const sec::DChkDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
-                            sec::DChkSlots slots, void *stream, int kb = 0);
-int sec_launch_decode_check_tail(const uint8_t *blocks, uint8_t *out, const sec::DChkDesc *descs,
-                                 const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs,
-                                 sec::DChkSlots slots, void *stream);
-// Repair + check (sec_repair_check_kernel): tiles as the repair's over the chunk's nt + nr rows
-// (rows 1..8 of the tile's group, kb as sec_launch_decode); the results by sec_launch_check_final
-int sec_launch_repair_check(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out,
-                            const sec::RChkDesc *descs, const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs,
-                            sec::RChkSlots slots, void *stream, int kb = 0);
-int sec_launch_repair_check_tail(const uint8_t *blocks, uint8_t *out, const sec::RChkDesc *descs,
-                                 const sec::TailItem *items, uint32_t nitems, const uint32_t *tabs,
-                                 sec::RChkSlots slots, void *stream);
+// The U = 1 tile kernels over (blocks, out, descs, tiles, tabs, slots), chosen by the descriptor:
+//   DecDesc / DecSlots    sec_decode_kernel        rows 0..8 recovered rows of the tile's group
+//   RepDesc / RepSlots    sec_repair_kernel        rows 1..8 target rows, each stored whole at its own address
+//   ChkDesc / ChkSlots    sec_check_kernel         rows 1..8 check rows; `out` unused: nothing is stored
+//                                                  unless a row differs, then only slots.flags words
+//   DChkDesc / DChkSlots  sec_decode_check_kernel  rows 0..8 of the chunk's e + nr rows
+//   RChkDesc / RChkSlots  sec_repair_check_kernel  rows 1..8 of the chunk's nt + nr rows
+// (the check family's results by sec_launch_check_final).  kb (4): the kernel variant whose load
+// batch is kb slots (every chunk of the group has k <= kb; not wide); 0: the default batch.
+// sec_launch_rows_tail: the same family's byte-granular tail kernel.
+template <class Desc, class Slots>
+int sec_launch_rows(int rows, int U, int wide, int lanes, const uint8_t *blocks, uint8_t *out, const Desc *descs,
+                    const sec::Tile *tiles, uint32_t ntiles, const uint32_t *tabs, Slots slots, void *stream,
+                    int kb = 0);
+template <class Desc, class Slots>
+int sec_launch_rows_tail(const uint8_t *blocks, uint8_t *out, const Desc *descs, const sec::TailItem *items,
+                         uint32_t nitems, const uint32_t *tabs, Slots slots, void *stream);
 // One thread per entry of the launch's chunks: slots.flags into results[d.res], row_bad[d.cslot0 + ..]
 // and, for an inconsistent chunk, column[d.cslot0 + ..] (row_bad, column nullable)
 int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uint32_t nentries, sec::ChkSlots slots,

@@ -190,6 +190,110 @@ class Engine:
         self._check(self.lib.sec_decode_batch_ex(self._ctx, _ptr(descs), len(descs), _ptr(sn), _ptr(bo),
                                                  None if av is None else _ptr(av), b or None, o or None, flags))
 
+    # -- the repair / check family: shared plumbing ---------------------------
+    def _row_call(self, fn, dtype, descs, sharenums, block_offs, block_avail, targets, bufs, *, host, asynchronous,
+                  recover_only=False) -> None:
+        """One call of the repair / check family: fn(ctx, descs, n, sharenums, block_offs,
+        block_avail, blocks, [target_nums, target_offs,] *outputs, flags).  targets: (target_nums,
+        target_offs) or None; bufs: (blocks, *outputs), each an address, tensor, array or None."""
+        descs = np.ascontiguousarray(descs, dtype=dtype)
+        sn = np.ascontiguousarray(sharenums, dtype=np.int32)
+        bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
+        tn = to = None
+        if targets is not None:
+            tn = np.ascontiguousarray(targets[0], dtype=np.int32)
+            to = np.ascontiguousarray(targets[1], dtype=np.uint64)
+        av = None if block_avail is None else np.ascontiguousarray(block_avail, dtype=np.uint64)
+        if av is not None and av.size < bo.size:
+            raise ValueError("block_avail needs one entry per slot")
+        if tn is not None and tn.size != to.size:
+            raise ValueError("one target address per target")
+        held = [addr(x) for x in bufs]  # (address, keep-alive)
+        args = [_ptr(sn) or None, _ptr(bo) or None, None if av is None else _ptr(av), held[0][0] or None]
+        if tn is not None:
+            args += [_ptr(tn) or None, _ptr(to) or None]
+        args += [a or None for a, _ in held[1:]]
+        flags = ((SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0) |
+                 (SEC_F_RECOVER if recover_only else 0))
+        self._check(fn(self._ctx, _ptr(descs), len(descs), *args, flags))
+
+    @staticmethod
+    def _lay_out_blocks(items):
+        """Every item's blocks (it[2], numbered it[3]) as one sn / bo pair of host addresses:
+        (sn, bo, keep, first), first[j] = item j's first slot, keep = what must outlive the call."""
+        nslots = sum(len(it[2]) for it in items)
+        sn = np.zeros(max(nslots, 1), dtype=np.int32)
+        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
+        keep, first = [], []
+        slot = 0
+        for it in items:
+            first.append(slot)
+            for q, b in enumerate(it[2]):
+                a, kp = addr(b)
+                keep.append(kp)
+                bo[slot + q] = a
+                sn[slot + q] = int(it[3][q])
+            slot += len(it[2])
+        return sn, bo, keep, first
+
+    @staticmethod
+    def _lay_out_targets(items, digests: bool):
+        """A new bytes object per target (it[4]) of every item: (tn, to, dig, objs, first, views),
+        objs[j] = item j's unfinished targets, first[j] = its first target slot, dig = 20 bytes per
+        target slot when digests are asked for, views = what must outlive the call."""
+        from ._hostbytes import _new_bytes
+
+        ntg = sum(len(it[4]) for it in items)
+        tn = np.zeros(max(ntg, 1), dtype=np.int32)
+        to = np.zeros(max(ntg, 1), dtype=np.uint64)
+        objs, first, views = [], [], []
+        tgt = 0
+        for it in items:
+            B = len(it[2][0])
+            first.append(tgt)
+            row = []
+            for q, t in enumerate(it[4]):
+                b, v = _new_bytes(B)
+                row.append(b)
+                tn[tgt + q] = int(t)
+                to[tgt + q] = v.ctypes.data if B else 0
+                views.append(v)
+            objs.append(row)
+            tgt += len(it[4])
+        dig = np.zeros(max(20 * ntg, 1), dtype=np.uint8) if digests else None
+        return tn, to, dig, objs, first, views
+
+    @staticmethod
+    def _targets_done(objs, dig):
+        """The finished targets per item and, with digests, each one's 20 bytes."""
+        from ._hostbytes import _finalize
+
+        out = [[_finalize(b) for b in row] for row in objs]
+        if dig is None:
+            return out, None
+        dv, digs, f = memoryview(dig), [], 0
+        for row in out:
+            digs.append([bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(len(row))])
+            f += len(row)
+        return out, digs
+
+    @staticmethod
+    def _check_results(items, first, res, rb, col):
+        """Per item ``(first, bad, column)`` from a check-family call's results."""
+        out = []
+        for j, it in enumerate(items):
+            s0, nb = first[j], len(it[2])
+            if int(res[j]["first"]) == _lib.CHK_CONSISTENT:
+                out.append((None, [], None))
+            else:
+                out.append((int(res[j]["first"]), [q for q in range(nb) if rb[s0 + q]], col[s0:s0 + nb].tobytes()))
+        return out
+
+    @staticmethod
+    def _result_arrays(nitems: int, nslots: int):
+        return (np.zeros(nitems, dtype=CHK_RESULT_DTYPE), np.zeros(max(nslots, 1), dtype=np.uint8),
+                np.zeros(max(nslots, 1), dtype=np.uint8))
+
     def repair_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
                      target_nums: np.ndarray, target_offs: np.ndarray, out, *, block_avail: np.ndarray | None = None,
                      digests=None, host: bool = False, asynchronous: bool = False) -> None:
@@ -197,23 +301,8 @@ class Engine:
         written whole at out + target_offs[tgt0 + j] from the chunk's k source blocks.
         block_avail as decode_batch; digests (optional): 20 bytes per target slot, the repaired
         piece's SHA-1, where the targets live.  host: host buffers, always staged."""
-        descs = np.ascontiguousarray(descs, dtype=REP_DTYPE)
-        sn = np.ascontiguousarray(sharenums, dtype=np.int32)
-        bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
-        tn = np.ascontiguousarray(target_nums, dtype=np.int32)
-        to = np.ascontiguousarray(target_offs, dtype=np.uint64)
-        av = None if block_avail is None else np.ascontiguousarray(block_avail, dtype=np.uint64)
-        if av is not None and av.size < bo.size:
-            raise ValueError("block_avail needs one entry per slot")
-        if tn.size != to.size:
-            raise ValueError("one target address per target")
-        b, _kb = addr(blocks)
-        o, _ko = addr(out)
-        g, _kg = addr(digests)
-        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
-        self._check(self.lib.sec_repair_batch(self._ctx, _ptr(descs), len(descs), _ptr(sn) or None, _ptr(bo) or None,
-                                              None if av is None else _ptr(av), b or None, _ptr(tn) or None,
-                                              _ptr(to) or None, o or None, g or None, flags))
+        self._row_call(self.lib.sec_repair_batch, REP_DTYPE, descs, sharenums, block_offs, block_avail,
+                       (target_nums, target_offs), (blocks, out, digests), host=host, asynchronous=asynchronous)
 
     def repair_host(self, items, digests: bool = False):
         """Lost blocks of host chunks, regenerated from k survivors each, in one call.
@@ -222,49 +311,17 @@ class Engine:
         and the block numbers to regenerate.  Returns, per chunk, the target blocks as bytes in
         the order of `targets`; with ``digests=True`` also, per chunk, each one's SHA-1 digest
         (20 bytes, GPU-computed on the repaired piece)."""
-        from ._hostbytes import _finalize, _new_bytes
-
         for it in items:
             check_repair_item(*it)
-        n = len(items)
-        descs = np.zeros(n, dtype=REP_DTYPE)
-        nslots = sum(it[0] for it in items)
-        ntg = sum(len(it[4]) for it in items)
-        sn = np.zeros(max(nslots, 1), dtype=np.int32)
-        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
-        tn = np.zeros(max(ntg, 1), dtype=np.int32)
-        to = np.zeros(max(ntg, 1), dtype=np.uint64)
-        keep, objs = [], []
-        slot = tgt = 0
-        for j, (k, m, blocks, sharenums, targets) in enumerate(items):
-            B = len(blocks[0])
-            for q, b in enumerate(blocks):
-                a, kp = addr(b)
-                keep.append(kp)
-                bo[slot + q] = a
-                sn[slot + q] = int(sharenums[q])
-            row = []
-            for q, t in enumerate(targets):
-                b, v = _new_bytes(B)
-                row.append(b)
-                tn[tgt + q] = int(t)
-                to[tgt + q] = v.ctypes.data if B else 0
-                keep.append(v)
-            objs.append(row)
-            descs[j] = (B, slot, tgt, len(targets), k, m, 0)
-            slot += k
-            tgt += len(targets)
-        dig = np.zeros(max(20 * ntg, 1), dtype=np.uint8) if digests else None
-        if ntg:
+        sn, bo, _keep, slot0 = self._lay_out_blocks(items)
+        tn, to, dig, objs, tgt0, _views = self._lay_out_targets(items, digests)
+        descs = np.zeros(len(items), dtype=REP_DTYPE)
+        for j, (k, m, blocks, _sharenums, targets) in enumerate(items):
+            descs[j] = (len(blocks[0]), slot0[j], tgt0[j], len(targets), k, m, 0)
+        if any(len(it[4]) for it in items):
             self.repair_batch(descs, sn, bo, 0, tn, to, 0, digests=dig, host=True)
-        out = [[_finalize(b) for b in row] for row in objs]
-        if not digests:
-            return out
-        dv, digs, f = memoryview(dig), [], 0
-        for row in out:
-            digs.append([bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(len(row))])
-            f += len(row)
-        return out, digs
+        out, digs = self._targets_done(objs, dig)
+        return (out, digs) if digests else out
 
     def check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks, results, *,
                     block_avail: np.ndarray | None = None, row_bad=None, column=None, host: bool = False,
@@ -275,20 +332,8 @@ class Engine:
         differing position or CHK_CONSISTENT, differing rows); row_bad, column (optional): one
         byte per slot entry; all three where the blocks live.  block_avail as decode_batch.
         host: host buffers, always staged."""
-        descs = np.ascontiguousarray(descs, dtype=CHK_DTYPE)
-        sn = np.ascontiguousarray(sharenums, dtype=np.int32)
-        bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
-        av = None if block_avail is None else np.ascontiguousarray(block_avail, dtype=np.uint64)
-        if av is not None and av.size < bo.size:
-            raise ValueError("block_avail needs one entry per slot")
-        b, _kb = addr(blocks)
-        r, _kr = addr(results)
-        rb, _krb = addr(row_bad)
-        co, _kco = addr(column)
-        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
-        self._check(self.lib.sec_check_batch(self._ctx, _ptr(descs), len(descs), _ptr(sn) or None, _ptr(bo) or None,
-                                             None if av is None else _ptr(av), b or None, r or None, rb or None,
-                                             co or None, flags))
+        self._row_call(self.lib.sec_check_batch, CHK_DTYPE, descs, sharenums, block_offs, block_avail, None,
+                       (blocks, results, row_bad, column), host=host, asynchronous=asynchronous)
 
     def check_host(self, items):
         """Whether the held blocks of host chunks agree with each other, in one call.
@@ -301,35 +346,15 @@ class Engine:
         ``check_locate``."""
         for it in items:
             check_check_item(*it)
-        n = len(items)
-        if not n:
+        if not items:
             return []
-        descs = np.zeros(n, dtype=CHK_DTYPE)
-        nslots = sum(len(it[2]) for it in items)
-        sn = np.zeros(max(nslots, 1), dtype=np.int32)
-        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
-        keep = []
-        slot = 0
-        for j, (k, m, blocks, sharenums) in enumerate(items):
-            for q, b in enumerate(blocks):
-                a, kp = addr(b)
-                keep.append(kp)
-                bo[slot + q] = a
-                sn[slot + q] = int(sharenums[q])
-            descs[j] = (len(blocks[0]), slot, len(blocks), k, m, 0)
-            slot += len(blocks)
-        res = np.zeros(n, dtype=CHK_RESULT_DTYPE)
-        rb = np.zeros(max(nslots, 1), dtype=np.uint8)
-        col = np.zeros(max(nslots, 1), dtype=np.uint8)
+        sn, bo, _keep, slot0 = self._lay_out_blocks(items)
+        descs = np.zeros(len(items), dtype=CHK_DTYPE)
+        for j, (k, m, blocks, _sharenums) in enumerate(items):
+            descs[j] = (len(blocks[0]), slot0[j], len(blocks), k, m, 0)
+        res, rb, col = self._result_arrays(len(items), sn.size)
         self.check_batch(descs, sn, bo, 0, res, row_bad=rb, column=col, host=True)
-        out = []
-        for j in range(n):
-            s0, nb = int(descs[j]["slot0"]), int(descs[j]["n"])
-            if int(res[j]["first"]) == _lib.CHK_CONSISTENT:
-                out.append((None, [], None))
-            else:
-                out.append((int(res[j]["first"]), [q for q in range(nb) if rb[s0 + q]], col[s0:s0 + nb].tobytes()))
-        return out
+        return self._check_results(items, slot0, res, rb, col)
 
     def decode_check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks, out,
                            results, *, block_avail: np.ndarray | None = None, row_bad=None, column=None,
@@ -339,22 +364,9 @@ class Engine:
         decode_batch writes (recover_only: just the missing primaries), consistent or not;
         results, row_bad and column what check_batch reports.  host: host buffers, always staged,
         every entry gathered once."""
-        descs = np.ascontiguousarray(descs, dtype=DCHK_DTYPE)
-        sn = np.ascontiguousarray(sharenums, dtype=np.int32)
-        bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
-        av = None if block_avail is None else np.ascontiguousarray(block_avail, dtype=np.uint64)
-        if av is not None and av.size < bo.size:
-            raise ValueError("block_avail needs one entry per slot")
-        b, _kb = addr(blocks)
-        o, _ko = addr(out)
-        r, _kr = addr(results)
-        rb, _krb = addr(row_bad)
-        co, _kco = addr(column)
-        flags = ((SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0) |
-                 (SEC_F_RECOVER if recover_only else 0))
-        self._check(self.lib.sec_decode_check_batch(self._ctx, _ptr(descs), len(descs), _ptr(sn) or None,
-                                                    _ptr(bo) or None, None if av is None else _ptr(av), b or None,
-                                                    o or None, r or None, rb or None, co or None, flags))
+        self._row_call(self.lib.sec_decode_check_batch, DCHK_DTYPE, descs, sharenums, block_offs, block_avail, None,
+                       (blocks, out, results, row_bad, column), host=host, asynchronous=asynchronous,
+                       recover_only=recover_only)
 
     def decode_check_host(self, items):
         """Reassemble host chunks and check their spare blocks in one call.
@@ -369,30 +381,19 @@ class Engine:
         says."""
         for it in items:
             check_decode_check_item(*it)
-        n = len(items)
-        if not n:
+        if not items:
             return b"", []
-        descs = np.zeros(n, dtype=DCHK_DTYPE)
-        nslots = sum(len(it[2]) for it in items)
-        sn = np.zeros(max(nslots, 1), dtype=np.int32)
-        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
-        keep, rec = [], []
-        slot = total = 0
+        sn, bo, _keep, slot0 = self._lay_out_blocks(items)
+        descs = np.zeros(len(items), dtype=DCHK_DTYPE)
+        rec = []
+        total = 0
         for j, (k, m, blocks, sharenums, padlen) in enumerate(items):
             B = len(blocks[0])
-            for q, b in enumerate(blocks):
-                a, kp = addr(b)
-                keep.append(kp)
-                bo[slot + q] = a
-                sn[slot + q] = int(sharenums[q])
-            descs[j] = (total, B, padlen, slot, len(blocks), k, m, 0)
+            descs[j] = (total, B, padlen, slot0[j], len(blocks), k, m, 0)
             rec.append(total)
-            slot += len(blocks)
             total += sum(1 for x in sharenums[:k] if int(x) >= k) * B
         buf = self._out_buffer(max(total, 1))
-        res = np.zeros(n, dtype=CHK_RESULT_DTYPE)
-        rb = np.zeros(max(nslots, 1), dtype=np.uint8)
-        col = np.zeros(max(nslots, 1), dtype=np.uint8)
+        res, rb, col = self._result_arrays(len(items), sn.size)
         self.decode_check_batch(descs, sn, bo, 0, buf, res, row_bad=rb, column=col, host=True, recover_only=True)
         mv = memoryview(buf)
         views = []
@@ -410,16 +411,7 @@ class Engine:
                     o += B
                 views.append(v[:left] if left < B else v)
                 left -= B
-        data = self._joined(views)
-        checks = []
-        for j in range(n):
-            s0, nb = int(descs[j]["slot0"]), int(descs[j]["n"])
-            if int(res[j]["first"]) == _lib.CHK_CONSISTENT:
-                checks.append((None, [], None))
-            else:
-                checks.append((int(res[j]["first"]), [q for q in range(nb) if rb[s0 + q]],
-                               col[s0:s0 + nb].tobytes()))
-        return data, checks
+        return self._joined(views), self._check_results(items, slot0, res, rb, col)
 
     def repair_check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
                            target_nums: np.ndarray, target_offs: np.ndarray, out, results, *,
@@ -429,27 +421,9 @@ class Engine:
         on all n of them (RCHK_DTYPE descriptors) in one pass over the blocks.  The targets (and
         digests) receive what repair_batch writes, consistent or not; results, row_bad and column
         what check_batch reports.  host: host buffers, always staged, every entry gathered once."""
-        descs = np.ascontiguousarray(descs, dtype=RCHK_DTYPE)
-        sn = np.ascontiguousarray(sharenums, dtype=np.int32)
-        bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
-        tn = np.ascontiguousarray(target_nums, dtype=np.int32)
-        to = np.ascontiguousarray(target_offs, dtype=np.uint64)
-        av = None if block_avail is None else np.ascontiguousarray(block_avail, dtype=np.uint64)
-        if av is not None and av.size < bo.size:
-            raise ValueError("block_avail needs one entry per slot")
-        if tn.size != to.size:
-            raise ValueError("one target address per target")
-        b, _kb = addr(blocks)
-        o, _ko = addr(out)
-        g, _kg = addr(digests)
-        r, _kr = addr(results)
-        rb, _krb = addr(row_bad)
-        co, _kco = addr(column)
-        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
-        self._check(self.lib.sec_repair_check_batch(self._ctx, _ptr(descs), len(descs), _ptr(sn) or None,
-                                                    _ptr(bo) or None, None if av is None else _ptr(av), b or None,
-                                                    _ptr(tn) or None, _ptr(to) or None, o or None, g or None,
-                                                    r or None, rb or None, co or None, flags))
+        self._row_call(self.lib.sec_repair_check_batch, RCHK_DTYPE, descs, sharenums, block_offs, block_avail,
+                       (target_nums, target_offs), (blocks, out, digests, results, row_bad, column), host=host,
+                       asynchronous=asynchronous)
 
     def repair_check_host(self, items, digests: bool = False):
         """Lost blocks of host chunks regenerated and their spare blocks checked, in one call.
@@ -460,61 +434,20 @@ class Engine:
         `targets`; with ``digests=True`` also, per chunk, each one's SHA-1 digest) followed by
         checks = per chunk ``(first, bad, column)`` as ``check_host`` returns them.  One host
         call stages every block once.  The targets are returned whatever the check says."""
-        from ._hostbytes import _finalize, _new_bytes
-
         for it in items:
             check_repair_check_item(*it)
-        n = len(items)
-        if not n:
+        if not items:
             return ([], [], []) if digests else ([], [])
-        descs = np.zeros(n, dtype=RCHK_DTYPE)
-        nslots = sum(len(it[2]) for it in items)
-        ntg = sum(len(it[4]) for it in items)
-        sn = np.zeros(max(nslots, 1), dtype=np.int32)
-        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
-        tn = np.zeros(max(ntg, 1), dtype=np.int32)
-        to = np.zeros(max(ntg, 1), dtype=np.uint64)
-        keep, objs = [], []
-        slot = tgt = 0
-        for j, (k, m, blocks, sharenums, targets) in enumerate(items):
-            B = len(blocks[0])
-            for q, b in enumerate(blocks):
-                a, kp = addr(b)
-                keep.append(kp)
-                bo[slot + q] = a
-                sn[slot + q] = int(sharenums[q])
-            row = []
-            for q, t in enumerate(targets):
-                b, v = _new_bytes(B)
-                row.append(b)
-                tn[tgt + q] = int(t)
-                to[tgt + q] = v.ctypes.data if B else 0
-                keep.append(v)
-            objs.append(row)
-            descs[j] = (B, slot, tgt, len(targets), len(blocks), k, m)
-            slot += len(blocks)
-            tgt += len(targets)
-        dig = np.zeros(max(20 * ntg, 1), dtype=np.uint8) if digests else None
-        res = np.zeros(n, dtype=CHK_RESULT_DTYPE)
-        rb = np.zeros(max(nslots, 1), dtype=np.uint8)
-        col = np.zeros(max(nslots, 1), dtype=np.uint8)
+        sn, bo, _keep, slot0 = self._lay_out_blocks(items)
+        tn, to, dig, objs, tgt0, _views = self._lay_out_targets(items, digests)
+        descs = np.zeros(len(items), dtype=RCHK_DTYPE)
+        for j, (k, m, blocks, _sharenums, targets) in enumerate(items):
+            descs[j] = (len(blocks[0]), slot0[j], tgt0[j], len(targets), len(blocks), k, m)
+        res, rb, col = self._result_arrays(len(items), sn.size)
         self.repair_check_batch(descs, sn, bo, 0, tn, to, 0, res, digests=dig, row_bad=rb, column=col, host=True)
-        out = [[_finalize(b) for b in row] for row in objs]
-        checks = []
-        for j in range(n):
-            s0, nb = int(descs[j]["slot0"]), int(descs[j]["n"])
-            if int(res[j]["first"]) == _lib.CHK_CONSISTENT:
-                checks.append((None, [], None))
-            else:
-                checks.append((int(res[j]["first"]), [q for q in range(nb) if rb[s0 + q]],
-                               col[s0:s0 + nb].tobytes()))
-        if not digests:
-            return out, checks
-        dv, digs, f = memoryview(dig), [], 0
-        for row in out:
-            digs.append([bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(len(row))])
-            f += len(row)
-        return out, digs, checks
+        out, digs = self._targets_done(objs, dig)
+        checks = self._check_results(items, slot0, res, rb, col)
+        return (out, digs, checks) if digests else (out, checks)
 
     def encode_digest_batch(self, descs: np.ndarray, src, parity, digests, *, host: bool = False,
                             asynchronous: bool = False) -> None:

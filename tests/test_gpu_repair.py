@@ -273,6 +273,20 @@ def test_repair_host_from_bytes(engine):
         engine.repair_host([(4, 6, [b"ab"] * 4, [0, 2, 3, 4], [3])])
 
 
+def test_repair_host_targets_as_arrays(engine):
+    """targets given as numpy arrays, whose truth value is not their length: a lone target 0, and
+    two targets."""
+    s = _host_specs()[0]
+    k, m = s["k"], s["m"]
+    blocks = _blocks(k, m, s["B"], s["padlen"], s["seed"])
+    src = list(range(1, k + 1))  # block 0 lost
+    held = [blocks[b] for b in src]
+    out, digs = engine.repair_host([(k, m, held, src, np.array([0]))], digests=True)
+    assert out == [[blocks[0]]] and digs == [[hashlib.sha1(blocks[0]).digest()]]
+    two = np.array([0, m - 1]) if m - 1 > k else np.array([0])
+    assert engine.repair_host([(k, m, held, src, two)]) == [[blocks[t] for t in two]]
+
+
 def test_repair_pieces_end_to_end():
     """piece.repair_pieces on a 256 KiB chunk whose pieces come from the oracle: one data and
     one parity piece dropped, their bytes and ids regenerated on the GPU.  RS(4,2), the shape
