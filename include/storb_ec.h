@@ -520,6 +520,37 @@ int sec_bn_mulmod_batch(sec_ctx *ctx, const sec_bn_key *key, const uint8_t *a, c
 int sec_apdp_tag_batch(sec_ctx *ctx, const sec_bn_key *key, const sec_msg *msgs, int64_t nmsgs,
                        uint8_t *tags, unsigned flags);
 
+/* ---- tagged encode: parity, piece ids and APDP tags from one pass over the chunk ----------
+ * The upload's three steps per piece (encode, validator.py:1380; SHA-1 id, :1081; APDP tag,
+ * process_tag :945-947) while the chunk and its parity are on the device, so a chunk crosses
+ * PCIe once.  The composition of the calls it replaces: `parity` gets what sec_encode_batch
+ * writes; `digests`, when not NULL, what sec_encode_digest_batch writes; `tags` (256 B
+ * big-endian at tags + 256 (M_c + j), the digests' slot numbering) what sec_apdp_tag_batch
+ * returns for the chunk's m blocks as messages: data block j with len = B and
+ * avail = min(B, n - j B) (the padding zeros are part of the integer, as of the piece), parity
+ * block r with len = avail = B.  A chunk with m == k still gets its k tags; one with n == 0
+ * gets the tag of the empty message in each of its m slots.
+ * Device mode (no flag, or SEC_F_ASYNC): every pointer is device memory.  SEC_F_HOST: host
+ * memory, always staged (as digest mode: each chunk gathered once into a slab of
+ * SEC_SLAB_BYTES_DIGEST; parity, digests and tags scattered back; counted as staged by
+ * sec_ctx_host_paths).  Errors, before any device work and in this order: SEC_EINVAL for a NULL
+ * ctx / key / tags, any other flag, SEC_F_HOST | SEC_F_ASYNC, or a key of another device;
+ * SEC_ENOTAG for a key without sec_bn_key_set_tag; then sec_encode_batch's per-chunk errors.
+ * Timing: the tag kernels under kind 3, the encode and SHA-1 as sec_encode_digest_batch. */
+int sec_encode_tag_batch(sec_ctx *ctx, const sec_bn_key *key, const sec_enc_chunk *chunks,
+                         int64_t nchunks, const uint8_t *in, uint8_t *parity,
+                         uint8_t *digests /* nullable */, uint8_t *tags, unsigned flags);
+/* sec_encode_pieces (same flags, host-thread copies and ids) plus each piece's APDP tag: 256 B
+ * at tags + 256 (M_c + j), host memory.  The tags come from the GPU call of each sub-batch,
+ * which holds the staged chunk and its parity, so no piece crosses PCIe for its tag; a sub-batch
+ * is therefore bounded by its staged chunk bytes (twice the bound of its parity, at least one
+ * chunk) as well as by its parity, and chunks with m == k take the GPU call too.  key and tags both NULL: sec_encode_pieces
+ * itself.  Errors: SEC_EINVAL (NULL ctx, one of key / tags NULL, a bad flag, a key of another
+ * device), SEC_ENOTAG, then sec_encode_pieces' own. */
+int sec_encode_pieces_tags(sec_ctx *ctx, const sec_bn_key *key, const sec_enc_chunk *chunks,
+                           int64_t nchunks, const uint8_t *in, uint8_t *const *pieces,
+                           uint8_t *digests /* nullable */, uint8_t *tags, unsigned flags);
+
 /* ---- memory helpers for hosts without a device allocator ----------------- */
 int sec_malloc(sec_ctx *ctx, size_t bytes, void **dptr);
 int sec_free(sec_ctx *ctx, void *dptr);

@@ -331,6 +331,20 @@ class ChallengeSystem:
         tags = self._modkey(self._n(), tag=True).tags(list(datas))
         return [APDPTag(index=0, tag_value=t, prf_value=prf_value) for t in tags]
 
+    # The two methods the tagged encode (piece.encode_chunks_with_tags) calls: the key its GPU
+    # pass tags with, and the objects generate_tags would have built from the values it returns.
+    def tag_key(self) -> ModKey:
+        """The calling thread's ``ModKey`` of this system's modulus, ready for tags (its factors
+        and generate_tag's constants set; g's table is built on the thread's first call)."""
+        if self.key.rsa is None or self.key.g is None or self.key.prf_key is None:
+            raise APDPError("Key values are not initialized. Call initialize_keys first.")
+        return self._modkey(self._n(), tag=True)
+
+    def wrap_tags(self, values) -> list[APDPTag]:
+        """``APDPTag`` objects for tag values the GPU computed: what ``generate_tags`` builds."""
+        prf_value = CryptoUtils.prf(self.key.prf_key, 0)
+        return [APDPTag(index=0, tag_value=int(t), prf_value=prf_value) for t in values]
+
     # -- challenges (validator.py:644) --------------------------------------------
     def issue_challenge(self, tag: APDPTag) -> Challenge:
         """Random s in Z*_n, g_s = g^s mod n, fresh PRP / PRF keys (challenge/__init__.py:352-399)."""

@@ -57,6 +57,12 @@ class ModKey:
     def _check(self, rc: int) -> None:
         self.engine._check(rc)
 
+    @property
+    def handle(self):
+        """The ``sec_bn_key`` itself, for the engine's tagged encode calls (``tag_key=``); None
+        once closed."""
+        return self._key
+
     def close(self) -> None:
         if getattr(self, "_key", None):
             self.lib.sec_bn_key_destroy(self._key)

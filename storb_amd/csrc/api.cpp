@@ -293,6 +293,11 @@ struct SubPlan {
     uint32_t nsegs = 0, max_seg = 0;       // segment count; most segments of one message
     uint64_t dig_first = 0;                // first digest slot of this unit
     uint64_t dig_off = 0;                  // host mode: digests' offset in the slab output
+    // tagged encode: the messages that get an APDP tag (every block of the unit's chunks; the
+    // SHA-1 list itself where that is every block too), the segment lists above being theirs
+    size_t off_tmsgs = 0;
+    uint32_t ntmsgs = 0;
+    uint64_t tag_first = 0, tag_off = 0;   // first tag slot; host mode: tags' offset in the slab output
     // row operations (build_row_plan)
     size_t off_toff = 0;                   // the targets' addresses (RepSlots / RChkSlots::tgt_off)
     size_t off_cpos = 0, off_echunk = 0;   // the entries' caller positions and chunks (ChkSlots)
@@ -1036,10 +1041,92 @@ int check_blocks(int k, int m, const int32_t *held, int n, const int32_t *target
 
 uint64_t enc_B(const sec_enc_chunk &c) { return (c.n + (uint64_t)c.k - 1) / (uint64_t)c.k; }
 
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// APDP bignum (bignum.hip).  The key lives on the device of the context that
+// created it: a TagKey whose first member is the BnKey.
+struct sec_bn_key {
+    int device = 0;
+    DevBuf dk;     // TagKey, then 1 KiB of upload staging
+    DevBuf table;  // fixed-base table of g (sec::kGTabWords u32), once set_tag ran
+    bool has_tag = false, has_crt = false;
+    mutable DevBuf rpow;              // R^(j S) mod n (Montgomery form), j < rpow_count
+    mutable uint32_t rpow_count = 0;  // grown on demand by the segmented reductions
+};
+
+namespace {
+
+// Segmented reductions: every message is cut into kSegBytes segments from its end, one
+// wave each (so a batch of few, large pieces still fills the chip); partial residues
+// r_j * R^(j S) go to ctx->bn_part, then one wave per message sums them.
+constexpr uint64_t kSegBytes = (uint64_t)sec::kSegChunks * 256;
+
+int bn_prepare(sec_ctx *ctx, const sec_bn_key *key, const Plan &plan, bool host)
+{
+    uint32_t need = 0;
+    size_t part = 0;
+    for (const SubPlan &sp : plan.subs) {
+        need = std::max(need, sp.max_seg);
+        part = std::max(part, (size_t)sp.nsegs * 256);
+    }
+    if (need > key->rpow_count) {  // grow R^(j S) to cover the longest message
+        const uint32_t cap = std::max<uint32_t>(need, 2 * key->rpow_count);
+        DevBuf grown;
+        RC(grown.ensure((size_t)cap * 256));
+        if (key->rpow_count)
+            CK(hipMemcpyAsync(grown.p, key->rpow.p, (size_t)key->rpow_count * 256, hipMemcpyDeviceToDevice,
+                              ctx->stream()));
+        int e = sec_launch_bn_rpow(key->dk.as<sec::BnKey>(), key->rpow_count, cap, grown.as<uint32_t>(), ctx->stream());
+        if (e)
+            return hip_fail((hipError_t)e, "sec_bn_rpow_kernel");
+        CK(hipStreamSynchronize(ctx->stream()));
+        key->rpow.release();
+        key->rpow = grown;
+        grown.p = nullptr;
+        key->rpow_count = cap;
+    }
+    ctx->bn_part_stride = part;
+    return ctx->bn_part.ensure(std::max<size_t>(part, 256) * (host ? kSlots : 1));
+}
+
+uint8_t *bn_part(sec_ctx *ctx, size_t sub_index, bool host)
+{
+    return ctx->bn_part.as<uint8_t>(host ? (sub_index % kSlots) * ctx->bn_part_stride : 0);
+}
+
+// A launch unit's messages into the plan image (msg_batch and the encode plan): the SHA-1
+// list (nmsgs, off_msgs, sha_split) ...
+void put_msgs(const Options &o, SubPlan &sp, Image &img, const std::vector<sec::MsgDesc> &md)
+{
+    sp.nmsgs = (uint32_t)md.size();
+    sp.sha_split = sha1_split(o, md);
+    sp.off_msgs = img.put(md.data(), md.size() * sizeof(sec::MsgDesc));
+}
+
+// ... and, for the bignum reductions, each message's segments of seg_bytes counted from its end
+// (the least significant bytes of a big-endian integer; an empty message has one, empty)
+void put_segs(SubPlan &sp, Image &img, const std::vector<sec::MsgDesc> &md, uint64_t seg_bytes)
+{
+    std::vector<sec::SegDesc> segs;
+    std::vector<sec::SegInfo> info;
+    for (size_t i = 0; i < md.size(); ++i) {
+        const uint64_t ns = std::max<uint64_t>(1, (md[i].len + seg_bytes - 1) / seg_bytes);
+        info.push_back(sec::SegInfo{(uint32_t)segs.size(), (uint32_t)ns});
+        for (uint64_t j = 0; j < ns; ++j)
+            segs.push_back(sec::SegDesc{(uint32_t)i, (uint32_t)j});
+        sp.max_seg = std::max<uint32_t>(sp.max_seg, (uint32_t)ns);
+    }
+    sp.nsegs = (uint32_t)segs.size();
+    sp.off_segs = img.put(segs.data(), segs.size() * sizeof(sec::SegDesc));
+    sp.off_seginfo = img.put(info.data(), info.size() * sizeof(sec::SegInfo));
+}
+
 // ---- encode plan ------------------------------------------------------------
 // digest: 0 none, 1 every block's SHA-1 (sec_encode_digest_batch), 2 the parity blocks' only
 // (sec_encode_pieces with SEC_F_GPU_PARITY_IDS: digest slot s of a chunk's m - k)
-int build_encode_plan(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks, bool host, int digest)
+// tag: every block's APDP tag too (sec_encode_tag_batch), tag slot j of a chunk's m
+int build_encode_plan(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks, bool host, int digest, bool tag)
 {
     Plan &plan = ctx->enc_plan;
     TableCache &tc = ctx->enc_tabs;
@@ -1065,23 +1152,26 @@ int build_encode_plan(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks
     // SHA-1 is one sequential chain per piece: a slab's hashing takes as long as
     // one piece, whatever the slab size, so digest mode uses few large slabs
     const auto ranges = slab_ranges(host, nchunks, [&](int64_t i) { return chunks[i].n; },
-                                    (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
+                                    (size_t)ctx->opt[digest || tag ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
     Image img;
     plan.subs.clear();
     bool narrow = true;  // every block of the batch >= 64 KiB: one-wave encode tiles (full_lanes)
     for (int64_t i = 0; i < nchunks && narrow; ++i)
         if (chunks[i].m > chunks[i].k && enc_B(chunks[i]) < ((uint64_t)64 << 10))
             narrow = false;
-    uint64_t dig = 0;
+    uint64_t dig = 0, tags = 0;
     for (auto [c0, c1] : ranges) {
         SubPlan sp;
         sp.c0 = c0;
         sp.c1 = c1;
         sp.dig_first = dig;
+        sp.tag_first = tags;
         std::vector<sec::EncDesc> descs((size_t)(c1 - c0));
         Bins bins;
         std::vector<sec::TailItem> tail;
-        std::vector<sec::MsgDesc> msgs;
+        // the SHA-1 messages, and the tagged ones where they are not the same blocks
+        std::vector<sec::MsgDesc> msgs, tmsgs;
+        const bool all = digest == 1 || (tag && !digest);  // msgs: every block (else the parity)
         for (int64_t i = c0; i < c1; ++i) {
             const sec_enc_chunk &c = chunks[i];
             const uint64_t B = enc_B(c);
@@ -1097,16 +1187,21 @@ int build_encode_plan(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks
             d.tab = tab_of[i];
             d.valid = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(valid, (int64_t)B));
             d.pad = 0;
-            if (digest) {  // data blocks from the input (padding synthesised), then parity
-                for (int j = 0; j < c.k && digest == 1; ++j) {
+            if (digest || tag) {  // data blocks from the input (padding synthesised), then parity
+                for (int j = 0; j < c.k && (all || tag); ++j) {
                     const int64_t av = (int64_t)c.n - (int64_t)j * (int64_t)B;
-                    msgs.push_back(sec::MsgDesc{d.in_off + (uint64_t)j * B, B,
+                    (all ? msgs : tmsgs)
+                        .push_back(sec::MsgDesc{d.in_off + (uint64_t)j * B, B,
                                                 (uint64_t)std::max<int64_t>(0, std::min<int64_t>(av, (int64_t)B)), 0,
                                                 0});
                 }
-                for (int r = 0; r < p; ++r)
+                for (int r = 0; r < p; ++r) {
                     msgs.push_back(sec::MsgDesc{d.par_off + (uint64_t)r * d.par_stride, B, B, 1, 0});
-                dig += (uint64_t)(digest == 1 ? c.m : p);
+                    if (tag && !all)
+                        tmsgs.push_back(msgs.back());
+                }
+                dig += (uint64_t)(digest == 1 ? c.m : digest ? p : 0);
+                tags += (uint64_t)(tag ? c.m : 0);
             }
             sp.in_bytes += c.n;
             sp.out_bytes += (uint64_t)p * B;
@@ -1119,15 +1214,24 @@ int build_encode_plan(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks
         std::vector<sec::Tile> tiles;
         flatten(bins, sp.groups, tiles, false);
         sp.ntail = (uint32_t)tail.size();
-        sp.nmsgs = (uint32_t)msgs.size();
-        sp.sha_split = sha1_split(ctx->opt, msgs);
-        sp.dig_off = sp.out_bytes;  // host mode: digests follow the slab's parity
-        if (host)
+        sp.dig_off = sp.out_bytes;  // host mode: digests follow the slab's parity, tags the digests
+        if (host && digest)
             sp.out_bytes += (uint64_t)msgs.size() * 20;
+        sp.tag_off = sp.out_bytes;
         sp.off_desc = img.put(descs.data(), descs.size() * sizeof(sec::EncDesc));
         sp.off_tiles = img.put(tiles.data(), tiles.size() * sizeof(sec::Tile));
         sp.off_tail = img.put(tail.data(), tail.size() * sizeof(sec::TailItem));
-        sp.off_msgs = img.put(msgs.data(), msgs.size() * sizeof(sec::MsgDesc));
+        put_msgs(ctx->opt, sp, img, msgs);
+        if (tag) {
+            const std::vector<sec::MsgDesc> &tm = all ? msgs : tmsgs;
+            sp.ntmsgs = (uint32_t)tm.size();
+            sp.off_tmsgs = all ? sp.off_msgs : img.put(tm.data(), tm.size() * sizeof(sec::MsgDesc));
+            put_segs(sp, img, tm, kSegBytes);
+            if (host)
+                sp.out_bytes += (uint64_t)tm.size() * 256;
+            if (!digest)
+                sp.nmsgs = 0;  // no SHA-1 launch: the list is the tags' alone
+        }
         plan.subs.push_back(std::move(sp));
     }
     RC(upload_plan(ctx, plan, img, tc, pending));
@@ -1159,6 +1263,24 @@ int launch_encode_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
             return hip_fail((hipError_t)e, "sec_sha1_kernel");
     }
     return SEC_OK;
+}
+
+// Tagged encode: the APDP tags of the sub-plan's blocks, behind its encode on the same stream
+// (bn_prepare ran for this call).  The partials are those of the sub-plan's pipeline slot, and
+// the kernels are timed under kind 3 as sec_apdp_tag_batch's are.
+int launch_encode_tags(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const sec_bn_key *key, const uint8_t *in,
+                       const uint8_t *par, uint8_t *tags, bool host, hipStream_t s)
+{
+    hipEvent_t t0;
+    RC(timing_begin(ctx, &t0, s, false));
+    int e = sec_launch_apdp_tag(key->dk.as<sec::TagKey>(), key->table.as<uint32_t>(), key->rpow.as<uint32_t>(), in, par,
+                                plan.meta.as<sec::MsgDesc>(sp.off_tmsgs), sp.ntmsgs,
+                                plan.meta.as<sec::SegDesc>(sp.off_segs), sp.nsegs,
+                                plan.meta.as<sec::SegInfo>(sp.off_seginfo),
+                                bn_part(ctx, (size_t)(&sp - plan.subs.data()), host), tags, s);
+    if (e)
+        return hip_fail((hipError_t)e, "sec_apdp_tag");
+    return timing_end(ctx, t0, 3, s);
 }
 
 // ---- decode plan ------------------------------------------------------------
@@ -2362,24 +2484,10 @@ int msg_batch(sec_ctx *ctx, Plan &plan, const sec_msg *msgs, int64_t nmsgs, uint
                 md.push_back(sec::MsgDesc{host ? sp.in_bytes : msgs[i].addr, msgs[i].len, av, 0, 0});
                 sp.in_bytes += av;
             }
-            sp.nmsgs = (uint32_t)md.size();
-            sp.sha_split = sha1_split(ctx->opt, md);
             sp.out_bytes = (uint64_t)md.size() * out_per;
-            sp.off_msgs = img.put(md.data(), md.size() * sizeof(sec::MsgDesc));
-            if (seg_bytes) {
-                std::vector<sec::SegDesc> segs;
-                std::vector<sec::SegInfo> info;
-                for (int64_t i = c0; i < c1; ++i) {
-                    const uint64_t ns = std::max<uint64_t>(1, (msgs[i].len + seg_bytes - 1) / seg_bytes);
-                    info.push_back(sec::SegInfo{(uint32_t)segs.size(), (uint32_t)ns});
-                    for (uint64_t j = 0; j < ns; ++j)
-                        segs.push_back(sec::SegDesc{(uint32_t)(i - c0), (uint32_t)j});
-                    sp.max_seg = std::max<uint32_t>(sp.max_seg, (uint32_t)ns);
-                }
-                sp.nsegs = (uint32_t)segs.size();
-                sp.off_segs = img.put(segs.data(), segs.size() * sizeof(sec::SegDesc));
-                sp.off_seginfo = img.put(info.data(), info.size() * sizeof(sec::SegInfo));
-            }
+            put_msgs(ctx->opt, sp, img, md);
+            if (seg_bytes)
+                put_segs(sp, img, md, seg_bytes);
             plan.subs.push_back(std::move(sp));
         }
         std::vector<PendingExpand> none;
@@ -3001,10 +3109,14 @@ bool host_direct(sec_ctx *ctx, const std::vector<HostRange> &rs, HostLock &lock,
     }
 }
 
-// sec_encode_batch (digests == nullptr, digest == false) and sec_encode_digest_batch.
+// sec_encode_batch (digests == nullptr, digest == false), sec_encode_digest_batch and, with a
+// key (its tag constants set, on this context's device: the callers' check) and `tags`,
+// sec_encode_tag_batch: every block's APDP tag from the same staged chunk and device parity.
 int encode_impl(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks, const uint8_t *in, uint8_t *parity,
-                uint8_t *digests, unsigned flags, int digest)
+                uint8_t *digests, unsigned flags, int digest, const sec_bn_key *tag_key = nullptr,
+                uint8_t *tags = nullptr)
 {
+    const bool tag = tag_key != nullptr;
     if (!ctx || nchunks < 0 || (nchunks > 0 && !chunks) || (flags & ~(SEC_F_HOST | SEC_F_ASYNC | SEC_F_STAGED)) ||
         ((flags & SEC_F_STAGED) && !(flags & SEC_F_HOST)))
         return SEC_EINVAL;
@@ -3032,18 +3144,18 @@ int encode_impl(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks, cons
         total_par += p * B;
         total_in += c.n;
     }
-    if (total_par == 0 && !digest)
+    if (total_par == 0 && !digest && !tag)
         return SEC_OK;  // nothing to compute (m == k, or empty chunks)
-    if ((!in && !host && total_in) || (!parity && total_par) || (digest && !digests))
+    if ((!in && !host && total_in) || (!parity && total_par) || (digest && !digests) || (tag && !tags))
         return SEC_EINVAL;
     // pinned (or lockable) caller buffers: run the device path on them directly (synchronous,
     // as every host call).  Digest mode keeps the staged path: SHA-1 is one latency-bound lane
-    // per piece, which would stall on every PCIe read.
+    // per piece, which would stall on every PCIe read; so does tag mode (one wave per 8 KiB).
     HostLock lock(ctx->stream());
-    if (host && !digest && host_direct(ctx, encode_ranges(chunks, nchunks, in, parity), lock, flags)) {
+    if (host && !digest && !tag && host_direct(ctx, encode_ranges(chunks, nchunks, in, parity), lock, flags)) {
         host = false;
         flags &= ~(SEC_F_HOST | SEC_F_ASYNC);
-    } else if (host && digest) {
+    } else if (host && (digest || tag)) {
         ++ctx->staged_calls;  // (host_direct counted the other staged calls)
     }
 
@@ -3063,19 +3175,23 @@ int encode_impl(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks, cons
         key.put(chunks, sizeof(sec_enc_chunk) * (size_t)nchunks);
     }
     // ASYNC and STAGED do not change the plan
-    key.put((flags & ~(SEC_F_ASYNC | SEC_F_STAGED)) | ((unsigned)digest << 16));
+    key.put((flags & ~(SEC_F_ASYNC | SEC_F_STAGED)) | ((unsigned)digest << 16) | ((unsigned)tag << 20));
     if (!plan_reusable(plan, ctx->enc_tabs, key)) {
         plan.valid = false;
-        RC(build_encode_plan(ctx, chunks, nchunks, host, digest));
+        RC(build_encode_plan(ctx, chunks, nchunks, host, digest, tag));
         plan.key.swap(key.bytes);
         plan.valid = true;
     }
+    if (tag)  // once per call: R^(j S) for the longest block, partials for every pipeline slot
+        RC(bn_prepare(ctx, tag_key, plan, host));
 
     if (!host) {
         hipEvent_t t0 = nullptr;
         RC(timing_begin(ctx, &t0, ctx->stream()));
         RC(launch_encode_sub(ctx, plan, plan.subs[0], in, parity, digests, ctx->stream()));
         RC(timing_end(ctx, t0, 0, ctx->stream()));
+        if (tag)
+            RC(launch_encode_tags(ctx, plan, plan.subs[0], tag_key, in, parity, tags, false, ctx->stream()));
         if (!(flags & SEC_F_ASYNC))
             CK(hipStreamSynchronize(ctx->stream()));
         return SEC_OK;
@@ -3102,11 +3218,14 @@ int encode_impl(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks, cons
         }
         if (sp.nmsgs)
             jobs.push_back(sec::CopyJob{digests + sp.dig_first * 20, stage + sp.dig_off, (size_t)sp.nmsgs * 20});
+        if (sp.ntmsgs)
+            jobs.push_back(sec::CopyJob{tags + sp.tag_first * 256, stage + sp.tag_off, (size_t)sp.ntmsgs * 256});
     };
     auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
-        return launch_encode_sub(ctx, plan, sp, din, dout, dout + sp.dig_off, s);
+        RC(launch_encode_sub(ctx, plan, sp, din, dout, dout + sp.dig_off, s));
+        return tag ? launch_encode_tags(ctx, plan, sp, tag_key, din, dout, dout + sp.tag_off, true, s) : (int)SEC_OK;
     };
-    return run_pipeline(ctx, plan, gather, scatter, launch, !digest);
+    return run_pipeline(ctx, plan, gather, scatter, launch, !digest && !tag);
 }
 
 }  // namespace
@@ -3125,6 +3244,21 @@ int sec_encode_digest_batch(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t n
     return encode_impl(ctx, chunks, nchunks, in, parity, digests, flags, 1);
 }
 
+int sec_encode_tag_batch(sec_ctx *ctx, const sec_bn_key *key, const sec_enc_chunk *chunks, int64_t nchunks,
+                         const uint8_t *in, uint8_t *parity, uint8_t *digests, uint8_t *tags, unsigned flags)
+{
+    if (!ctx || !key || !tags || (flags & ~(SEC_F_HOST | SEC_F_ASYNC)) ||
+        ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)) || key->device != ctx->device)
+        return SEC_EINVAL;
+    if (!key->has_tag)
+        return SEC_ENOTAG;
+    return encode_impl(ctx, chunks, nchunks, in, parity, digests, flags, digests ? 1 : 0, key, tags);
+}
+
+}  // extern "C"
+
+namespace {
+
 // easyfec's Encoder.encode output for every chunk, as pieces in caller buffers: the k data
 // slices (copies, the last zero-padded to B) and the m - k parity blocks, each in its own buffer,
 // plus (digests) each piece's SHA-1.  The data pieces are copied and hashed on the context's
@@ -3132,8 +3266,10 @@ int sec_encode_digest_batch(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t n
 // pieces are copied and hashed as soon as it returns.  Everything but the GPU call is host work
 // that the Python layer would otherwise do on its own threads, under the GIL's hand-offs
 // (VERDICT r04 next #7).
-int sec_encode_pieces(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks, const uint8_t *in,
-                      uint8_t *const *pieces, uint8_t *digests, unsigned flags)
+// With a key (sec_encode_pieces_tags) every piece's APDP tag comes from the GPU call of its
+// sub-batch, which holds the staged chunk and its parity: no piece crosses PCIe for its tag.
+int encode_pieces_impl(sec_ctx *ctx, const sec_bn_key *key, const sec_enc_chunk *chunks, int64_t nchunks,
+                       const uint8_t *in, uint8_t *const *pieces, uint8_t *digests, uint8_t *tags, unsigned flags)
 {
     if (!ctx || nchunks < 0 || (nchunks > 0 && (!chunks || !pieces)) || !(flags & SEC_F_HOST) ||
         (flags & ~(SEC_F_HOST | SEC_F_STAGED | SEC_F_GPU_PARITY_IDS)))
@@ -3167,8 +3303,15 @@ int sec_encode_pieces(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks
     // 2 cap whatever the call's size (one allocation of the whole call's parity).
     // With gpu_ids the GPU hashes a sub-batch's parity pieces in one chain time (one lane per
     // piece), so the sub-batches are SEC_SLAB_BYTES_DIGEST: as many pieces in flight as it allows.
-    const uint64_t cap =
-        std::max<uint64_t>((uint64_t)ctx->opt[gpu_ids ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES], max_par);
+    // With a key the sub-batch is one tagged encode, whose whole chunks are staged: its input
+    // bytes are bounded as well (a larger chunk alone), by twice the parity bound, which is what
+    // that bound admits at the policy's parity of k / 2: 128 MiB by default.  Measured on 1 GiB
+    // calls (profiles/upload_tags_subbatch_ab.jsonl): 110-113 ms with 128 MiB sub-batches against
+    // 120-133 with 64 (the tag kernels' latency per sub-batch) and 226-330 with 256 or 512 (one
+    // or two sub-batches overlap no piece copies, and their slabs outgrow the pinned pool).
+    const uint64_t slab = (uint64_t)ctx->opt[gpu_ids ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES];
+    const uint64_t cap = std::max<uint64_t>(slab, max_par);
+    const uint64_t cap_in = key ? 2 * slab : UINT64_MAX;
     std::vector<uint8_t> par_dig;  // gpu_ids: a sub-batch's parity digests, chunk by chunk
     sec::TaskPool &tp = hash_tasks(ctx);
     sec::TaskPool::Group data, par[2];
@@ -3204,29 +3347,31 @@ int sec_encode_pieces(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks
     int buf = 0;
     for (int64_t c0 = 0; c0 < nchunks && rc == SEC_OK;) {
         // the next sub-batch [c0, c1): chunks whose parity sums to at most cap
+        // (with a key also to at most cap_in staged bytes, and run even without parity)
         int64_t c1 = c0;
-        uint64_t po = 0;
+        uint64_t po = 0, staged = 0;
         while (c1 < nchunks) {
             const sec_enc_chunk &c = chunks[c1];
             const uint64_t B = enc_B(c), p = (uint64_t)(c.m - c.k) * B;
-            if (c1 > c0 && po + p > cap)
+            if (c1 > c0 && (po + p > cap || staged + c.n > cap_in))
                 break;
             tmp[c1].parity_off = po;
             tmp[c1].parity_stride = B;
             po += p;
+            staged += c.n;
             ++c1;
         }
-        if (po) {
+        if (po || key) {
             par_failed |= !tp.wait(par[buf]);  // the scratch's previous pieces are copied out
             par[buf].failed.store(false);
             PinBuf &scratch = ctx->piece_par[buf];
             rc = scratch.ensure(po);
-            if (rc == SEC_OK && gpu_ids) {
+            uint64_t np = 0;  // parity pieces (a tagged sub-batch may have none)
+            for (int64_t i = c0; i < c1; ++i)
+                np += (uint64_t)(chunks[i].m - chunks[i].k);
+            if (rc == SEC_OK && gpu_ids && np) {
                 // parity and its ids in one staged call: the SHA-1 kernel runs on the device
                 // parity right after the encode (slots: each chunk's m - k, in chunk order)
-                uint64_t np = 0;
-                for (int64_t i = c0; i < c1; ++i)
-                    np += (uint64_t)(chunks[i].m - chunks[i].k);
                 try {
                     par_dig.resize((size_t)np * 20);
                 } catch (const std::bad_alloc &) {
@@ -3234,14 +3379,16 @@ int sec_encode_pieces(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks
                 }
                 if (rc == SEC_OK)
                     rc = encode_impl(ctx, tmp.data() + c0, c1 - c0, in, (uint8_t *)scratch.p, par_dig.data(),
-                                     SEC_F_HOST | (flags & SEC_F_STAGED), 2);
+                                     SEC_F_HOST | (flags & SEC_F_STAGED), 2, key,
+                                     key ? tags + first_piece[c0] * 256 : nullptr);
                 for (int64_t i = c0, q = 0; i < c1 && rc == SEC_OK; ++i)
                     for (int r = 0; r < chunks[i].m - chunks[i].k; ++r, ++q)
                         if (enc_B(chunks[i]) > 0)  // (an empty chunk's ids are sha1(b"") from above)
                             memcpy(digests + (first_piece[i] + chunks[i].k + r) * 20, par_dig.data() + q * 20, 20);
             } else if (rc == SEC_OK) {
                 rc = encode_impl(ctx, tmp.data() + c0, c1 - c0, in, (uint8_t *)scratch.p, nullptr,
-                                 SEC_F_HOST | (flags & SEC_F_STAGED), 0);
+                                 SEC_F_HOST | (flags & SEC_F_STAGED), 0, key,
+                                 key ? tags + first_piece[c0] * 256 : nullptr);
             }
             for (int64_t i = c0; i < c1 && rc == SEC_OK; ++i) {
                 const sec_enc_chunk &c = chunks[i];
@@ -3271,6 +3418,28 @@ int sec_encode_pieces(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks
     return rc;
 }
 
+}  // namespace
+
+extern "C" {
+
+int sec_encode_pieces(sec_ctx *ctx, const sec_enc_chunk *chunks, int64_t nchunks, const uint8_t *in,
+                      uint8_t *const *pieces, uint8_t *digests, unsigned flags)
+{
+    return encode_pieces_impl(ctx, nullptr, chunks, nchunks, in, pieces, digests, nullptr, flags);
+}
+
+int sec_encode_pieces_tags(sec_ctx *ctx, const sec_bn_key *key, const sec_enc_chunk *chunks, int64_t nchunks,
+                           const uint8_t *in, uint8_t *const *pieces, uint8_t *digests, uint8_t *tags,
+                           unsigned flags)
+{
+    if (!ctx || !key != !tags || !(flags & SEC_F_HOST) ||
+        (flags & ~(SEC_F_HOST | SEC_F_STAGED | SEC_F_GPU_PARITY_IDS)) || (key && key->device != ctx->device))
+        return SEC_EINVAL;
+    if (key && !key->has_tag)
+        return SEC_ENOTAG;
+    return encode_pieces_impl(ctx, key, chunks, nchunks, in, pieces, digests, tags, flags);
+}
+
 int sec_sha1_batch(sec_ctx *ctx, const sec_msg *msgs, int64_t nmsgs, uint8_t *digests, unsigned flags)
 {
     if (!ctx)
@@ -3284,18 +3453,8 @@ int sec_sha1_batch(sec_ctx *ctx, const sec_msg *msgs, int64_t nmsgs, uint8_t *di
 }
 
 // ---------------------------------------------------------------------------
-// APDP bignum (bignum.hip).  The key lives on the device of the context that
-// created it: a TagKey whose first member is the BnKey.
+// APDP bignum (bignum.hip): the keys (sec_bn_key, above the encode plan) and the calls on them.
 }  // extern "C"
-
-struct sec_bn_key {
-    int device = 0;
-    DevBuf dk;     // TagKey, then 1 KiB of upload staging
-    DevBuf table;  // fixed-base table of g (sec::kGTabWords u32), once set_tag ran
-    bool has_tag = false, has_crt = false;
-    mutable DevBuf rpow;              // R^(j S) mod n (Montgomery form), j < rpow_count
-    mutable uint32_t rpow_count = 0;  // grown on demand by the segmented reductions
-};
 
 namespace {
 constexpr size_t kKeyStage = sizeof(sec::TagKey);
@@ -3311,44 +3470,6 @@ uint32_t neg_inv32(const uint8_t *be, size_t nbytes)  // -n^-1 mod 2^32 from n's
 }
 
 bool odd_top(const uint8_t *be, size_t nbytes) { return (be[0] & 0x80) && (be[nbytes - 1] & 1); }
-
-// Segmented reductions: every message is cut into kSegBytes segments from its end, one
-// wave each (so a batch of few, large pieces still fills the chip); partial residues
-// r_j * R^(j S) go to ctx->bn_part, then one wave per message sums them.
-constexpr uint64_t kSegBytes = (uint64_t)sec::kSegChunks * 256;
-
-int bn_prepare(sec_ctx *ctx, const sec_bn_key *key, const Plan &plan, bool host)
-{
-    uint32_t need = 0;
-    size_t part = 0;
-    for (const SubPlan &sp : plan.subs) {
-        need = std::max(need, sp.max_seg);
-        part = std::max(part, (size_t)sp.nsegs * 256);
-    }
-    if (need > key->rpow_count) {  // grow R^(j S) to cover the longest message
-        const uint32_t cap = std::max<uint32_t>(need, 2 * key->rpow_count);
-        DevBuf grown;
-        RC(grown.ensure((size_t)cap * 256));
-        if (key->rpow_count)
-            CK(hipMemcpyAsync(grown.p, key->rpow.p, (size_t)key->rpow_count * 256, hipMemcpyDeviceToDevice,
-                              ctx->stream()));
-        int e = sec_launch_bn_rpow(key->dk.as<sec::BnKey>(), key->rpow_count, cap, grown.as<uint32_t>(), ctx->stream());
-        if (e)
-            return hip_fail((hipError_t)e, "sec_bn_rpow_kernel");
-        CK(hipStreamSynchronize(ctx->stream()));
-        key->rpow.release();
-        key->rpow = grown;
-        grown.p = nullptr;
-        key->rpow_count = cap;
-    }
-    ctx->bn_part_stride = part;
-    return ctx->bn_part.ensure(std::max<size_t>(part, 256) * (host ? kSlots : 1));
-}
-
-uint8_t *bn_part(sec_ctx *ctx, size_t sub_index, bool host)
-{
-    return ctx->bn_part.as<uint8_t>(host ? (sub_index % kSlots) * ctx->bn_part_stride : 0);
-}
 }  // namespace
 
 extern "C" {
@@ -3467,7 +3588,7 @@ int sec_bn_reduce_batch(sec_ctx *ctx, const sec_bn_key *key, const sec_msg *msgs
                              RC(bn_prepare(ctx, key, plan, host));
                              prepared = true;
                          }
-                         return sec_launch_bn_reduce(dk, key->rpow.as<uint32_t>(), base0,
+                         return sec_launch_bn_reduce(dk, key->rpow.as<uint32_t>(), base0, nullptr,
                                                      plan.meta.as<sec::MsgDesc>(sp.off_msgs), sp.nmsgs,
                                                      plan.meta.as<sec::SegDesc>(sp.off_segs), sp.nsegs,
                                                      plan.meta.as<sec::SegInfo>(sp.off_seginfo),
@@ -3494,7 +3615,7 @@ int sec_apdp_tag_batch(sec_ctx *ctx, const sec_bn_key *key, const sec_msg *msgs,
                              RC(bn_prepare(ctx, key, plan, host));
                              prepared = true;
                          }
-                         return sec_launch_apdp_tag(tk, table, key->rpow.as<uint32_t>(), base0,
+                         return sec_launch_apdp_tag(tk, table, key->rpow.as<uint32_t>(), base0, nullptr,
                                                     plan.meta.as<sec::MsgDesc>(sp.off_msgs), sp.nmsgs,
                                                     plan.meta.as<sec::SegDesc>(sp.off_segs), sp.nsegs,
                                                     plan.meta.as<sec::SegInfo>(sp.off_seginfo),

@@ -467,9 +467,11 @@ __global__ __launch_bounds__(64) void sec_bn_rpow_kernel(const sec::BnKey *__res
 }
 
 // One segment of one message: its bytes as an integer mod n, times R^(j S) (its weight
-// in the message), plain limbs into partials.
+// in the message), plain limbs into partials.  A message lies at (base ? base1 : base0) + off,
+// as the SHA-1 kernel reads it.
 __global__ __launch_bounds__(64) void sec_bn_reduce_seg_kernel(const sec::BnKey *__restrict__ key,
                                                                const u32 *__restrict__ P, const u8 *base0,
+                                                               const u8 *base1,
                                                                const sec::MsgDesc *__restrict__ msgs,
                                                                const sec::SegDesc *__restrict__ segs, u32 nsegs,
                                                                u32 *partials)
@@ -485,7 +487,7 @@ __global__ __launch_bounds__(64) void sec_bn_reduce_seg_kernel(const sec::BnKey 
     const u64 end = m.len - (u64)sd.j * seg;
     const u64 start = end > seg ? end - seg : 0;
     const u64 avail = m.avail > start ? m.avail - start : 0;
-    u32 r = reduce_msg(N, base0 + m.off + start, end - start, avail, l);
+    u32 r = reduce_msg(N, (m.base ? base1 : base0) + m.off + start, end - start, avail, l);
     if (sd.j)
         r = mmul<64>(N, r, P[(u64)sd.j * 64 + l], l);
     partials[(u64)b * 64 + l] = r;
@@ -656,14 +658,14 @@ int sec_launch_bn_rpow(const sec::BnKey *key, uint32_t j0, uint32_t j1, uint32_t
     return hipGetLastError();
 }
 
-int sec_launch_bn_reduce(const sec::BnKey *key, const uint32_t *P, const uint8_t *base0, const sec::MsgDesc *msgs,
-                         uint32_t nmsgs, const sec::SegDesc *segs, uint32_t nsegs, const sec::SegInfo *info,
-                         uint8_t *partials, uint8_t *out, void *stream)
+int sec_launch_bn_reduce(const sec::BnKey *key, const uint32_t *P, const uint8_t *base0, const uint8_t *base1,
+                         const sec::MsgDesc *msgs, uint32_t nmsgs, const sec::SegDesc *segs, uint32_t nsegs,
+                         const sec::SegInfo *info, uint8_t *partials, uint8_t *out, void *stream)
 {
     if (nmsgs == 0)
         return hipSuccess;
-    hipLaunchKernelGGL(sec_bn_reduce_seg_kernel, dim3(nsegs), dim3(64), 0, (hipStream_t)stream, key, P, base0, msgs,
-                       segs, nsegs, (u32 *)partials);
+    hipLaunchKernelGGL(sec_bn_reduce_seg_kernel, dim3(nsegs), dim3(64), 0, (hipStream_t)stream, key, P, base0, base1,
+                       msgs, segs, nsegs, (u32 *)partials);
     hipLaunchKernelGGL(sec_bn_reduce_sum_kernel, dim3(nmsgs), dim3(64), 0, (hipStream_t)stream, key, info, nmsgs,
                        (const u32 *)partials, out);
     return hipGetLastError();
@@ -709,13 +711,13 @@ int sec_launch_apdp_gpow(const sec::TagKey *tk, const uint32_t *table, const uin
 }
 
 int sec_launch_apdp_tag(const sec::TagKey *tk, const uint32_t *table, const uint32_t *P, const uint8_t *base0,
-                        const sec::MsgDesc *msgs, uint32_t nmsgs, const sec::SegDesc *segs, uint32_t nsegs,
-                        const sec::SegInfo *info, uint8_t *partials, uint8_t *tags, void *stream)
+                        const uint8_t *base1, const sec::MsgDesc *msgs, uint32_t nmsgs, const sec::SegDesc *segs,
+                        uint32_t nsegs, const sec::SegInfo *info, uint8_t *partials, uint8_t *tags, void *stream)
 {
     if (nmsgs == 0)
         return hipSuccess;
     hipLaunchKernelGGL(sec_bn_reduce_seg_kernel, dim3(nsegs), dim3(64), 0, (hipStream_t)stream, &tk->k, P, base0,
-                       msgs, segs, nsegs, (u32 *)partials);
+                       base1, msgs, segs, nsegs, (u32 *)partials);
     hipLaunchKernelGGL(sec_apdp_tag_kernel, dim3(nmsgs), dim3(128), 0, (hipStream_t)stream, tk, table, info, nmsgs,
                        (const u32 *)partials, tags);
     return hipGetLastError();

@@ -62,10 +62,11 @@ int sec_launch_crt_setup(const uint8_t *cp_be, const uint8_t *cq_be, sec::TagKey
 // P_j = R^(j * kSegChunks) mod n in Montgomery form, for j in [j0, j1) (one wave each).
 int sec_launch_bn_rpow(const sec::BnKey *key, uint32_t j0, uint32_t j1, uint32_t *P, void *stream);
 // int.from_bytes(message, "big") mod n per message, 256 B big-endian each: one wave per
-// segment into `partials` (256 B per segment), then one wave per message sums them.
-int sec_launch_bn_reduce(const sec::BnKey *key, const uint32_t *P, const uint8_t *base0, const sec::MsgDesc *msgs,
-                         uint32_t nmsgs, const sec::SegDesc *segs, uint32_t nsegs, const sec::SegInfo *info,
-                         uint8_t *partials, uint8_t *out, void *stream);
+// segment into `partials` (256 B per segment), then one wave per message sums them.  Message
+// i lies at (msgs[i].base ? base1 : base0) + msgs[i].off, as sec_launch_sha1 reads it.
+int sec_launch_bn_reduce(const sec::BnKey *key, const uint32_t *P, const uint8_t *base0, const uint8_t *base1,
+                         const sec::MsgDesc *msgs, uint32_t nmsgs, const sec::SegDesc *segs, uint32_t nsegs,
+                         const sec::SegInfo *info, uint8_t *partials, uint8_t *out, void *stream);
 int sec_launch_bn_modexp(const sec::BnKey *key, const uint8_t *bases, const uint8_t *exps, uint32_t exp_bytes,
                          uint32_t count, uint8_t *out, void *stream);
 int sec_launch_bn_crt_modexp(const sec::TagKey *tk, const uint8_t *bases, const uint8_t *exps_p,
@@ -75,6 +76,6 @@ int sec_launch_bn_mulmod(const sec::BnKey *key, const uint8_t *a, const uint8_t 
 int sec_launch_apdp_gpow(const sec::TagKey *tk, const uint32_t *table, const uint8_t *exps, uint32_t exp_bytes,
                          uint32_t count, uint8_t *out, void *stream);
 int sec_launch_apdp_tag(const sec::TagKey *tk, const uint32_t *table, const uint32_t *P, const uint8_t *base0,
-                        const sec::MsgDesc *msgs, uint32_t nmsgs, const sec::SegDesc *segs, uint32_t nsegs,
-                        const sec::SegInfo *info, uint8_t *partials, uint8_t *tags, void *stream);
+                        const uint8_t *base1, const sec::MsgDesc *msgs, uint32_t nmsgs, const sec::SegDesc *segs,
+                        uint32_t nsegs, const sec::SegInfo *info, uint8_t *partials, uint8_t *tags, void *stream);
 }

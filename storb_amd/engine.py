@@ -460,6 +460,39 @@ class Engine:
         self._check(self.lib.sec_encode_digest_batch(self._ctx, _ptr(descs), len(descs), s or None, p or None,
                                                      g or None, flags))
 
+    @staticmethod
+    def _key_handle(key):
+        """The sec_bn_key of a ``bn.ModKey`` (or a raw handle), for the tagged encode calls."""
+        h = getattr(key, "handle", key)
+        if not h:
+            raise ECRuntimeError("tagged encode needs an open ModKey")
+        return h
+
+    def encode_tag_batch(self, descs: np.ndarray, src, parity, tags, key, *, digests=None, host: bool = False,
+                         asynchronous: bool = False) -> None:
+        """Encode + the APDP tag of every block (256 B big-endian per block, chunk-major, the
+        slot numbering of ``encode_digest_batch``) and, with ``digests``, every block's SHA-1:
+        one pass over the chunk (sec_encode_tag_batch).  key: a ``bn.ModKey`` of this engine
+        with ``set_tag`` done."""
+        descs = np.ascontiguousarray(descs, dtype=ENC_DTYPE)
+        s, _ks = addr(src)
+        p, _kp = addr(parity)
+        t, _kt = addr(tags)
+        g, _kg = addr(digests) if digests is not None else (0, None)
+        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
+        self._check(self.lib.sec_encode_tag_batch(self._ctx, self._key_handle(key), _ptr(descs), len(descs),
+                                                  s or None, p or None, g or None, t or None, flags))
+
+    @staticmethod
+    def _tag_ints(tags: np.ndarray, ms) -> list[list[int]]:
+        """Per chunk, its m tags as Python ints (tags: 256 bytes per slot, chunk-major)."""
+        tv = memoryview(tags)
+        out, f = [], 0
+        for m in ms:
+            out.append([int.from_bytes(tv[256 * (f + j):256 * (f + j + 1)], "big") for j in range(m)])
+            f += m
+        return out
+
     def sha1_batch(self, msgs: np.ndarray, digests, *, host: bool = False, asynchronous: bool = False) -> None:
         """SHA-1 of each (addr, len, avail) message into 20-byte digests — sec_sha1_batch."""
         msgs = np.ascontiguousarray(msgs, dtype=MSG_DTYPE)
@@ -539,13 +572,15 @@ class Engine:
         mv = memoryview(out)
         return [bytes(mv[20 * i:20 * (i + 1)]) for i in range(len(datas))]
 
-    def encode_host_raw(self, chunks, shapes, digests: bool = False, staged: bool = False):
+    def encode_host_raw(self, chunks, shapes, digests: bool = False, staged: bool = False, tag_key=None):
         """``encode_host`` without the per-block ``bytes``: returns (buf, layout) where buf is
         this engine's pinned result scratch and layout[i] = (offset, B, m - k) of chunk i's
         parity blocks in it, back to back.  buf is reused by the engine's next call.  With
         ``digests=True``: (buf, layout, dig), dig = the SHA-1 of every chunk's m blocks in order,
         20 bytes each (GPU-computed after the encode, sec_encode_digest_batch).  staged: as
-        encode_batch."""
+        encode_batch.  With ``tag_key`` (a ``bn.ModKey`` with ``set_tag`` done) the result gains a
+        last element: per chunk, the APDP tags of its m blocks as Python ints, from the same pass
+        (sec_encode_tag_batch)."""
         n = len(chunks)
         descs = np.zeros(n, dtype=ENC_DTYPE)
         keep = []
@@ -560,6 +595,14 @@ class Engine:
             layout.append((total, B, m - k))
             total += (m - k) * B
         out = self._out_buffer(total)
+        if tag_key is not None:
+            ms = [m for (_, m) in shapes]
+            dig = np.empty(max(20 * sum(ms), 1), dtype=np.uint8) if digests else None
+            tags = np.empty(max(256 * sum(ms), 1), dtype=np.uint8)
+            if n:
+                self.encode_tag_batch(descs, 0, out, tags, tag_key, digests=dig, host=True)
+            ints = self._tag_ints(tags, ms)
+            return (out, layout, dig, ints) if digests else (out, layout, ints)
         if digests:
             dig = np.empty(max(20 * sum(m for (_, m) in shapes), 1), dtype=np.uint8)
             if n:
@@ -570,13 +613,16 @@ class Engine:
         return out, layout
 
     def encode_pieces_into(self, chunks, shapes, piece_addrs, digests: np.ndarray | None = None,
-                           staged: bool = False, gpu_parity_ids: bool = False) -> None:
+                           staged: bool = False, gpu_parity_ids: bool = False, tags: np.ndarray | None = None,
+                           tag_key=None) -> None:
         """easyfec's Encoder.encode output for every chunk written to caller buffers
         (sec_encode_pieces): piece_addrs[M_c + j] = the address of a writable B-byte buffer for
         piece j of chunk c (M_c = sum of m over the chunks before c); digests (optional, a
         writable uint8 array of 20 bytes per piece) receives each piece's SHA-1, computed on the
         library's host threads while the GPU encodes (``gpu_parity_ids``: the parity pieces' on
-        the GPU, SEC_F_GPU_PARITY_IDS).  shapes: [(k, m)] per chunk."""
+        the GPU, SEC_F_GPU_PARITY_IDS).  shapes: [(k, m)] per chunk.  tags (a writable uint8 array
+        of 256 bytes per piece) with tag_key (a ``bn.ModKey`` with ``set_tag`` done): each
+        piece's APDP tag, big-endian, from the GPU call that encodes it (sec_encode_pieces_tags)."""
         n = len(chunks)
         descs = np.zeros(n, dtype=ENC_DTYPE)
         keep = []
@@ -591,16 +637,26 @@ class Engine:
             raise ValueError("encode_pieces_into: one piece address per piece")
         if digests is not None and digests.size < 20 * pa.size:
             raise ValueError("encode_pieces_into: digests needs 20 bytes per piece")
+        if (tags is None) != (tag_key is None):
+            raise ValueError("encode_pieces_into: tags and tag_key go together")
+        if tags is not None and tags.size < 256 * pa.size:
+            raise ValueError("encode_pieces_into: tags needs 256 bytes per piece")
         flags = SEC_F_HOST | (SEC_F_STAGED if staged else 0) | (SEC_F_GPU_PARITY_IDS if gpu_parity_ids else 0)
-        if n:
+        if n and tags is not None:
+            self._check(self.lib.sec_encode_pieces_tags(self._ctx, self._key_handle(tag_key), _ptr(descs), n, None,
+                                                        _ptr(pa), None if digests is None else _ptr(digests),
+                                                        _ptr(tags), flags))
+        elif n:
             self._check(self.lib.sec_encode_pieces(self._ctx, _ptr(descs), n, None, _ptr(pa),
                                                    None if digests is None else _ptr(digests), flags))
 
-    def encode_host(self, chunks, shapes, digests: bool = False):
+    def encode_host(self, chunks, shapes, digests: bool = False, tag_key=None):
         """Parity blocks for each chunk.  chunks: bytes-like list; shapes: [(k, m)] per chunk.
 
         Returns, per chunk, the m-k secondary blocks (block numbers k..m-1) as bytes; with
-        ``digests=True`` also, per chunk, the SHA-1 digests of all m blocks (GPU-computed).
+        ``digests=True`` also, per chunk, the SHA-1 digests of all m blocks (GPU-computed); with
+        ``tag_key`` (a ``bn.ModKey`` with ``set_tag`` done) also, last, per chunk the APDP tags of
+        all m blocks as Python ints, from the same pass over the chunk.
         """
         n = len(chunks)
         descs = np.zeros(n, dtype=ENC_DTYPE)
@@ -616,6 +672,22 @@ class Engine:
             blocks.append((total, B, m - k))
             total += (m - k) * B
         out = self._out_buffer(total)
+        if tag_key is not None:
+            ms = [m for (_, m) in shapes]
+            dig = np.empty(max(20 * sum(ms), 1), dtype=np.uint8) if digests else None
+            tags = np.empty(max(256 * sum(ms), 1), dtype=np.uint8)
+            if n:
+                self.encode_tag_batch(descs, 0, out, tags, tag_key, digests=dig, host=True)
+            mv = memoryview(out)
+            par = [[bytes(mv[o + r * B:o + (r + 1) * B]) for r in range(p)] for (o, B, p) in blocks]
+            ints = self._tag_ints(tags, ms)
+            if not digests:
+                return par, ints
+            dv, f, digs = memoryview(dig), 0, []
+            for m in ms:
+                digs.append([bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(m)])
+                f += m
+            return par, digs, ints
         if not digests:
             self.encode_batch(descs, 0, out, host=True)
             mv = memoryview(out)

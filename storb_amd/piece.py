@@ -74,7 +74,8 @@ logger = logging.getLogger(__name__)
 __all__ = [
     "PieceType", "Piece", "EncodedChunk", "ProcessedPieceInfo", "EncodedPieces", "piece_hash", "piece_length",
     "encode_chunk", "decode_chunk", "reconstruct_data", "reconstruct_data_stream", "encode_chunks",
-    "decode_chunks", "chunk_shape", "piece_hashes", "encode_chunks_with_ids", "encode_chunks_stream", "Encoder",
+    "decode_chunks", "chunk_shape", "piece_hashes", "encode_chunks_with_ids", "encode_chunks_with_tags",
+    "encode_chunks_stream", "Encoder",
     "Decoder", "Error", "use_devices", "repair_chunks", "repair_pieces", "ChunkCheck", "check_chunks", "check_pieces",
     "decode_chunks_checked", "reconstruct_data_checked", "PieceCheckError", "repair_chunks_checked",
     "repair_pieces_checked",
@@ -496,11 +497,13 @@ class _Done:
         return False
 
 
-def _encode_pieces(chunks: list, shapes: list, ids: bool, gpu_parity_ids: bool = False):
+def _encode_pieces(chunks: list, shapes: list, ids: bool, gpu_parity_ids: bool = False, tag_key=None):
     """Every chunk's m pieces as new bytes objects, filled by the library (sec_encode_pieces:
     the k data slices, zero-padded, then the parity), and with `ids` each piece's SHA-1 hex
     (the library's host threads, OpenSSL: hashlib's bytes; with `gpu_parity_ids` the parity
-    pieces' from the GPU SHA-1 kernel).  Returns (pieces, ids or None)."""
+    pieces' from the GPU SHA-1 kernel).  Returns (pieces, ids or None); with `tag_key` (a
+    ``ModKey`` ready for tags) also, third, each chunk's m APDP tag values as ints, computed by
+    the GPU call that encodes the chunk (sec_encode_pieces_tags)."""
     objs, addrs = [], []
     for (k, m, B, _) in shapes:
         row = []
@@ -513,8 +516,13 @@ def _encode_pieces(chunks: list, shapes: list, ids: bool, gpu_parity_ids: bool =
     # staged, not page-locked: the library's threads fault in the new pieces meanwhile, and locking
     # waits on the same memory-map lock (6.4 against 0.55 ms for one 8 MiB chunk on MI355X,
     # profiles/r03_upload_ab.jsonl)
-    get_engine().encode_pieces_into(chunks, [(k, m) for (k, m, _, _) in shapes], addrs, dig, staged=True,
-                                    gpu_parity_ids=ids and gpu_parity_ids)
+    if tag_key is None:
+        get_engine().encode_pieces_into(chunks, [(k, m) for (k, m, _, _) in shapes], addrs, dig, staged=True,
+                                        gpu_parity_ids=ids and gpu_parity_ids)
+    else:
+        tags = np.empty(max(256 * len(addrs), 1), dtype=np.uint8)
+        get_engine().encode_pieces_into(chunks, [(k, m) for (k, m, _, _) in shapes], addrs, dig, staged=True,
+                                        gpu_parity_ids=ids and gpu_parity_ids, tags=tags, tag_key=tag_key)
     pieces = [[_finalize(b) for b, _ in row] for row in objs]
     hexes = None
     if ids:
@@ -522,6 +530,12 @@ def _encode_pieces(chunks: list, shapes: list, ids: bool, gpu_parity_ids: bool =
         for (_, m, _, _) in shapes:
             hexes.append([hx[40 * (f + j):40 * (f + j + 1)] for j in range(m)])
             f += m
+    if tag_key is not None:
+        tv, values, f = memoryview(tags), [], 0
+        for (_, m, _, _) in shapes:
+            values.append([int.from_bytes(tv[256 * (f + j):256 * (f + j + 1)], "big") for j in range(m)])
+            f += m
+        return pieces, hexes, values
     return pieces, hexes
 
 
@@ -629,6 +643,32 @@ def encode_chunks_with_ids(chunks: typing.Sequence[bytes],
     for i, (c, (k, m, B, padlen), par) in enumerate(zip(chunks, shapes, parity)):
         out.append(_build(first_chunk_idx + i, k, m, B, padlen, len(c), _split(c, k, B) + par))
     return out, [[d.hex() for d in ds] for ds in digs]
+
+
+def encode_chunks_with_tags(chunks: typing.Sequence[bytes], challenge_system, first_chunk_idx: int = 0, *,
+                            piece_ids: bool = True):
+    """``encode_chunks`` plus, from the same pass over each chunk, every piece's APDP tag (what
+    the validator's ``process_tag`` computes per stored piece, validator.py:945-947) and, with
+    ``piece_ids``, every piece's id: the chunk is staged to the GPU once, and its pieces are not
+    staged again for ``generate_tags``.
+
+    challenge_system: an ``apdp.ChallengeSystem`` (anything with its ``tag_key()`` and
+    ``wrap_tags(values)``).  Returns (chunks, ids or None, tags): tags[i] = the ``APDPTag`` of
+    each of chunk i's m pieces, equal to ``challenge_system.generate_tags`` over those pieces'
+    data; chunks and ids as ``encode_chunks_with_ids``.  Errors as ``encode_chunks``."""
+    shapes = []
+    for c in chunks:
+        n = len(c)
+        piece_length(n)  # same ValueError as encode_chunk for n == 0
+        shapes.append(chunk_shape(n))
+    if not chunks:
+        return [], ([] if piece_ids else None), []
+    _short_middle(shapes, chunks)
+    pieces, ids, values = _encode_pieces(list(chunks), shapes, piece_ids, GPU_PARITY_IDS,
+                                         tag_key=challenge_system.tag_key())
+    out = [_build(first_chunk_idx + i, k, m, B, padlen, len(c), ps)
+           for i, (c, (k, m, B, padlen), ps) in enumerate(zip(chunks, shapes, pieces))]
+    return out, ids, [challenge_system.wrap_tags(v) for v in values]
 
 
 def _sharenums(encoded_chunk: EncodedChunk, positional: bool):
@@ -1161,16 +1201,21 @@ def _window_shapes(window: list):
     return shapes, None
 
 
-def _encode_window(window: list, first_idx: int, piece_ids: bool):
+def _encode_window(window: list, first_idx: int, piece_ids: bool, tags=None):
     """Worker side of encode_chunks_stream: one batched GPU encode for the window (+ SHA-1 piece
     ids: on the GPU for large pieces, else on the hash pool, data pieces starting before the GPU
     call and parity pieces after it).  Returns (results, error): a chunk encode_chunk would
-    reject ends the window there, and the chunks before it are still encoded and returned."""
+    reject ends the window there, and the chunks before it are still encoded and returned.
+    tags (a challenge system): the results are (chunk, ids or None, tags), from the tagged
+    encode; this worker thread's key and table are built on its first window."""
     shapes, err = _window_shapes(window)
     window = window[:len(shapes)]
     if not window:
         return [], err
     try:
+        if tags is not None:
+            out, ids, tgs = encode_chunks_with_tags(window, tags, first_idx, piece_ids=piece_ids)
+            return list(zip(out, ids if piece_ids else [None] * len(out), tgs)), err
         if not piece_ids:
             return [(c, None) for c in encode_chunks(window, first_idx)], err
         hp = _pool("hash")
@@ -1202,7 +1247,7 @@ def _encode_window(window: list, first_idx: int, piece_ids: bool):
 
 
 def encode_chunks_stream(chunks: Iterable[bytes], first_chunk_idx: int = 0, *, piece_ids: bool = False,
-                         window_bytes: int | None = None, devices=None) -> Iterator:
+                         window_bytes: int | None = None, devices=None, tags=None) -> Iterator:
     """``encode_chunk`` over a stream of chunks (the validator's upload loop: chunks read from
     the request, encoded, handed to the miners, validator.py:1338-1446), pipelined.
 
@@ -1215,7 +1260,19 @@ def encode_chunks_stream(chunks: Iterable[bytes], first_chunk_idx: int = 0, *, p
     come from the library's host threads for the data pieces and from the GPU for the parity
     pieces (GPU_PARITY_IDS; default window STREAM_WINDOW_PARITY_IDS_BYTES), or all from the GPU
     (GPU_PIECE_IDS) for windows of large pieces, whose default window is then
-    STREAM_WINDOW_IDS_BYTES."""
+    STREAM_WINDOW_IDS_BYTES.
+
+    tags (an ``apdp.ChallengeSystem``): yields ``(EncodedChunk, ids or None, [APDPTag of each of
+    its m pieces])``, ids and tags from the window's one GPU pass (``encode_chunks_with_tags``).
+    Not with `devices`: a tag key lives on one context."""
+    if tags is not None and devices is not None:
+        raise ValueError("encode_chunks_stream: tags= cannot be combined with devices= (a tag key lives on one "
+                         "device)")
+    return _encode_stream(chunks, first_chunk_idx, piece_ids, window_bytes, devices, tags)
+
+
+def _encode_stream(chunks, first_chunk_idx, piece_ids, window_bytes, devices, tags) -> Iterator:
+    """encode_chunks_stream's generator (its argument check runs at the call, not at the first item)."""
     wb = window_bytes
     if wb is None:
         wb = (STREAM_WINDOW_IDS_BYTES if piece_ids and GPU_PIECE_IDS else
@@ -1228,10 +1285,11 @@ def encode_chunks_stream(chunks: Iterable[bytes], first_chunk_idx: int = 0, *, p
             idx += len(win)
 
     def run(wi, pid):
-        return _encode_window(wi[0], wi[1], pid)
+        return _encode_window(wi[0], wi[1], pid, tags)
 
-    for outs, err in _pipeline(numbered(), run, (piece_ids,), _group(devices)):
-        for ec, ids in outs:
-            yield (ec, ids) if piece_ids else ec
+    # (tagged windows run on the one stream worker, whatever use_devices set)
+    for outs, err in _pipeline(numbered(), run, (piece_ids,), None if tags is not None else _group(devices)):
+        for res in outs:
+            yield res if tags is not None else (res if piece_ids else res[0])
         if err is not None:
             raise err
