@@ -520,6 +520,47 @@ int sec_bn_mulmod_batch(sec_ctx *ctx, const sec_bn_key *key, const uint8_t *a, c
 int sec_apdp_tag_batch(sec_ctx *ctx, const sec_bn_key *key, const sec_msg *msgs, int64_t nmsgs,
                        uint8_t *tags, unsigned flags);
 
+/* ---- the challenge round: prove (miner) and verify (validator), one call each ----------
+ * Flags of the first two calls: none or SEC_F_ASYNC (device pointers), or SEC_F_HOST (host
+ * pointers).  Errors of all three, before any device work and in this order: SEC_EINVAL for a
+ * NULL ctx, key or (with a non-zero count) data pointer, a count < 0, any other flag,
+ * SEC_F_HOST | SEC_F_ASYNC, or a key of another device; SEC_ENOCRT (sec_bn_crt_modexp2_batch,
+ * sec_apdp_verify_batch) for a key without sec_bn_key_set_crt; SEC_EINVAL for exp_bytes outside
+ * 1..4096.  A count of 0 then succeeds and touches nothing.  Timing: kind 3, as every bignum
+ * kernel. */
+/* out[i] = a[i]^ea[i] * b[i]^eb[i] mod n by CRT: one simultaneous two-base exponentiation per
+ * factor.  a, b: 256 B each (any values < 2^2048); ea_p / ea_q and eb_p / eb_q: exp_bytes each,
+ * big-endian, congruent to ea[i] (eb[i]) mod p-1 / q-1 and nonzero when it is, as
+ * sec_bn_crt_modexp_batch's: exact for every base.  A negative power of a base invertible mod
+ * n is the exponent (-e) mod (p-1) / (q-1).  Needs sec_bn_key_set_crt. */
+int sec_bn_crt_modexp2_batch(sec_ctx *ctx, const sec_bn_key *key, const uint8_t *a, const uint8_t *b,
+                             const uint8_t *ea_p, const uint8_t *ea_q, const uint8_t *eb_p,
+                             const uint8_t *eb_q, uint32_t exp_bytes, int64_t count, uint8_t *out,
+                             unsigned flags);
+/* generate_proof (challenge/__init__.py:401-463) per message, X = message mod n (messages as
+ * in sec_bn_reduce_batch), T = tags[i], g_s = g_ss[i] (256 B each, any values < 2^2048),
+ * c = coefs[i] (32 B big-endian: prf(challenge key, 0)):
+ *   tag_c[i] = T^c mod n (256 B), block[i] = c * X (288 B big-endian, the plain product),
+ *   rho[i] = g_s^(c * X) mod n (256 B).
+ * Needs the modulus only (the miner's side): no CRT factors, no tag constants.  SEC_F_HOST
+ * stages the messages through pinned slabs as sec_apdp_tag_batch does. */
+int sec_apdp_prove_batch(sec_ctx *ctx, const sec_bn_key *key, const sec_msg *msgs, int64_t nmsgs,
+                         const uint8_t *tags, const uint8_t *g_ss, const uint8_t *coefs,
+                         uint8_t *tag_c, uint8_t *block, uint8_t *rho, unsigned flags);
+/* verify_proof's tau_s (challenge/__init__.py:497-524) per item:
+ *   values[i] = (T^e * (F^c)^-1)^s mod n, T = proof_tags[i], F = fdhs[i], s = ss[i] (256 B
+ *   each), c = coefs[i] (32 B), e = e_be (the public exponent, 256 B), all big-endian;
+ * the caller compares SHA-256 of values[i] (minimal big-endian bytes) with the proof's hash.
+ * status[i] = 1 and values[i] = 0 where F^c is not invertible mod n (c != 0 and F a multiple of
+ * p or q: gmpy2's powmod(x, -1, n) raises there), else 0.  The library reduces the exponents
+ * e*s and -c*s for p-1 and q-1 on its host threads and makes one sec_bn_crt_modexp2 launch.
+ * Host memory only: SEC_F_HOST is required, any other flag is SEC_EINVAL.  Needs
+ * sec_bn_key_set_crt. */
+int sec_apdp_verify_batch(sec_ctx *ctx, const sec_bn_key *key, const uint8_t *proof_tags,
+                          const uint8_t *fdhs, const uint8_t *coefs, const uint8_t *ss,
+                          const uint8_t e_be[256], int64_t count, uint8_t *values, int32_t *status,
+                          unsigned flags);
+
 /* ---- tagged encode: parity, piece ids and APDP tags from one pass over the chunk ----------
  * The upload's three steps per piece (encode, validator.py:1380; SHA-1 id, :1081; APDP tag,
  * process_tag :945-947) while the chunk and its parity are on the device, so a chunk crosses

@@ -157,6 +157,12 @@ _SIGS = {
     "sec_apdp_gpow_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int64, _vp, ctypes.c_uint]),
     "sec_bn_mulmod_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_uint]),
     "sec_apdp_tag_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_uint]),
+    "sec_bn_crt_modexp2_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32,
+                                                ctypes.c_int64, _vp, ctypes.c_uint]),
+    "sec_apdp_prove_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            ctypes.c_uint]),
+    "sec_apdp_verify_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp,
+                                             ctypes.c_uint]),
     "sec_encode_tag_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_uint]),
     "sec_encode_pieces_tags": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_uint]),
     "sec_malloc": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),

@@ -19,9 +19,13 @@ Deliberate differences:
 * the validator holds p and q, so its exponentiations (the d power of ``generate_tag``,
   everything in ``verify_proof``) run by CRT as two 1024-bit halves, and g's powers
   (``g^X`` in tags, ``g^s`` in challenges) come from a per-key fixed-base table; the
-  results are the same integers.  The modular inverse in ``verify_proof`` is
-  ``den^(p-2)`` / ``den^(q-2)`` per factor, checked by ``den * inv == 1``; a
-  non-invertible denominator raises APDPError as gmpy2's ``powmod(x, -1, n)`` does.
+  results are the same integers.  ``verify_proofs`` is one GPU launch
+  (``ModKey.verify_values``): ``(tag^e / fdh^c)^s`` is ``tag^(e*s) * fdh^(-c*s)`` mod each
+  factor, one two-base exponentiation per CRT half, with no modular inverse computed; a
+  non-invertible denominator (c != 0 and fdh a multiple of p or q, reported per item by the
+  library) raises APDPError as gmpy2's ``powmod(x, -1, n)`` does.  ``generate_proofs`` is one
+  call too (``ModKey.prove``): the piece is reduced, and ``tag^c``, ``c * X`` and
+  ``g_s^(c*X)`` formed, without an integer returning to the host in between.
 * ``generate_proof`` / ``verify_proof`` take ``n`` (and ``e``) as optional: they default to
   the system's own key, which is how the reference's own tests call them
   (challenge_test.py:79,82).  A modulus other than the key's makes ``verify_proof`` return
@@ -399,16 +403,13 @@ class ChallengeSystem:
             return []
         n = self._n() if n is None else n
         mk = self._modkey(n)
-        xs = mk.reduce([d for d, _, _ in items])
         coefs = [int.from_bytes(CryptoUtils.prf(ch.prf_key, 0), "big") % n for _, _, ch in items]
-        aggs = [c * x for c, x in zip(coefs, xs)]
-        res = mk.powmod([_fit(t.tag_value, n) for _, t, _ in items] + [_fit(ch.g_s, n) for _, _, ch in items],
-                        coefs + aggs)
-        k = len(items)
+        tag_cs, aggs, rhos = mk.prove([d for d, _, _ in items], [_fit(t.tag_value, n) for _, t, _ in items],
+                                      [_fit(ch.g_s, n) for _, _, ch in items], coefs)
         out = []
-        for i in range(k):
-            digest = hashlib.sha256(int_to_bytes(res[k + i])).digest()
-            out.append(Proof(tag_value=res[i], block_value=aggs[i],
+        for tag_c, agg, rho in zip(tag_cs, aggs, rhos):
+            digest = hashlib.sha256(int_to_bytes(rho)).digest()
+            out.append(Proof(tag_value=tag_c, block_value=agg,
                              hashed_result=base64.b64encode(digest).decode("utf-8")))
         return out
 
@@ -420,7 +421,7 @@ class ChallengeSystem:
         return self.verify_proofs([(proof, challenge, tag)], n, e)[0]
 
     def verify_proofs(self, items, n: Optional[int] = None, e: Optional[int] = None) -> list[bool]:
-        """``verify_proof`` over [(proof, challenge, tag)] in four GPU launches."""
+        """``verify_proof`` over [(proof, challenge, tag)] in one GPU launch."""
         for proof, challenge, tag in items:
             if proof is None or challenge is None or tag is None:
                 raise APDPError("Invalid proof, challenge, or tag.")
@@ -436,17 +437,15 @@ class ChallengeSystem:
             return [False] * len(items)
         priv = rsa_key.private_numbers()
         mk = self._modkey(n)  # the system's own key: CRT over p, q
-        k = len(items)
         coefs = [int.from_bytes(CryptoUtils.prf(ch.prf_key, 0), "big") % n for _, ch, _ in items]
         fdhs = [CryptoUtils.full_domain_hash(rsa_key, t.prf_value) for _, _, t in items]
-        r1 = mk.crt_powmod([_fit(p.tag_value, n) for p, _, _ in items] + fdhs, [e] * k + coefs)
-        taus, dens = r1[:k], r1[k:]
-        # den^-1: den^(p-2) mod p and den^(q-2) mod q (Fermat per factor), checked below
-        invs = mk.crt_powmod_pq(dens, [priv.p - 2] * k, [priv.q - 2] * k)
-        r2 = mk.mulmod(dens + taus, invs + invs)
-        if any(v != 1 for v in r2[:k]):
+        # exponents wider than the call's 2048 bits, folded: congruent mod p-1 and q-1, nonzero
+        lam = (priv.p - 1) * (priv.q - 1)
+        fold = lambda x: x if x < _TOP else (x - 1) % lam + 1  # noqa: E731
+        tau_s, status = mk.verify_values([_fit(p.tag_value, n) for p, _, _ in items], fdhs, coefs,
+                                         [fold(ch.s) for _, ch, _ in items], fold(e))
+        if any(status):
             raise APDPError("Failed to invert denominator modulo n.")
-        tau_s = mk.crt_powmod(r2[k:], [ch.s for _, ch, _ in items])
         out = []
         for (proof, _, _), v in zip(items, tau_s):
             expected = base64.b64encode(hashlib.sha256(int_to_bytes(v)).digest()).decode("utf-8")

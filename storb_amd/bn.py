@@ -147,6 +147,23 @@ class ModKey:
         self._check(self.lib.sec_bn_mulmod_batch(self.engine._ctx, self._key, pa or None, pb or None, count,
                                                  o or None, _flags(host, asynchronous)))
 
+    def crt_modexp2_batch(self, a, b, ea_p, ea_q, eb_p, eb_q, exp_bytes: int, count: int, out, *,
+                          host: bool = False, asynchronous: bool = False) -> None:
+        ptrs = [addr(x) for x in (a, b, ea_p, ea_q, eb_p, eb_q, out)]
+        self._check(self.lib.sec_bn_crt_modexp2_batch(self.engine._ctx, self._key, *(p or None for p, _ in ptrs[:6]),
+                                                      exp_bytes, count, ptrs[6][0] or None,
+                                                      _flags(host, asynchronous)))
+
+    def prove_batch(self, msgs: np.ndarray, tags, g_ss, coefs, tag_c, block, rho, *, host: bool = False,
+                    asynchronous: bool = False) -> None:
+        """``sec_apdp_prove_batch``: per message 256 B of tag, 256 B of g_s and 32 B of coefficient in;
+        256 B of tag^c, 288 B of c * X and 256 B of rho out."""
+        msgs = np.ascontiguousarray(msgs, dtype=MSG_DTYPE)
+        ptrs = [addr(x) for x in (tags, g_ss, coefs, tag_c, block, rho)]
+        self._check(self.lib.sec_apdp_prove_batch(self.engine._ctx, self._key, int(msgs.ctypes.data) if len(msgs)
+                                                  else None, len(msgs), *(p or None for p, _ in ptrs),
+                                                  _flags(host, asynchronous)))
+
     # -- Python-int conveniences (host memory) --------------------------------------
     @staticmethod
     def _msgs(datas) -> tuple[np.ndarray, list]:
@@ -216,6 +233,59 @@ class ModKey:
             raise ValueError("negative exponent")
         return self.crt_powmod_pq(bases, [self._half_exp(e, self.p - 1) for e in exps],
                                   [self._half_exp(e, self.q - 1) for e in exps])
+
+    def crt_powmod2(self, a, b, ea, eb) -> list[int]:
+        """``[pow(x, s, n) * pow(y, t, n) % n ...]`` by CRT, one joint exponentiation per factor
+        (needs set_crt); 0 <= x, y < 2^2048, s, t >= 0."""
+        if self.p is None:
+            raise ECRuntimeError("ModKey.crt_powmod2 needs set_crt(p, q) first")
+        if not (len(a) == len(b) == len(ea) == len(eb)):
+            raise ValueError("operands differ in length")
+        if not a:
+            return []
+        if any(e < 0 for e in list(ea) + list(eb)):
+            raise ValueError("negative exponent")
+        halves = [[self._half_exp(e, m) for e in es] for es in (ea, eb) for m in (self.p - 1, self.q - 1)]
+        width = max(1, max((e.bit_length() + 7) // 8 for h in halves for e in h))
+        out = np.empty((len(a), NBYTES), dtype=np.uint8)
+        self.crt_modexp2_batch(to_be(a), to_be(b), *(to_be(h, width) for h in halves), width, len(a), out,
+                               host=True)
+        return from_be(out)
+
+    def prove(self, datas, tag_values, g_ss, coefs) -> tuple[list[int], list[int], list[int]]:
+        """generate_proof's three integers per piece in one call: ``pow(T, c, n)``, ``c * X`` and
+        ``pow(g_s, c * X, n)`` with X = piece mod n; 0 <= T, g_s < 2^2048, 0 <= c < 2^256."""
+        k = len(datas)
+        if not (k == len(tag_values) == len(g_ss) == len(coefs)):
+            raise ValueError("operands differ in length")
+        if not k:
+            return [], [], []
+        msgs, _keep = self._msgs(datas)
+        tag_c, rho = (np.empty((k, NBYTES), dtype=np.uint8) for _ in range(2))
+        block = np.empty((k, NBYTES + 32), dtype=np.uint8)
+        self.prove_batch(msgs, to_be(tag_values), to_be(g_ss), to_be(coefs, 32), tag_c, block, rho, host=True)
+        return from_be(tag_c), [int.from_bytes(r.tobytes(), "big") for r in block], from_be(rho)
+
+    def verify_values(self, proof_tags, fdhs, coefs, ss, e: int) -> tuple[list[int], list[int]]:
+        """verify_proof's ``pow(pow(T, e, n) * pow(pow(F, c, n), -1, n) % n, s, n)`` per item in one
+        call (needs set_crt), and a status per item: 1 (value 0) where F^c has no inverse mod n.
+        0 <= T, F, s, e < 2^2048, 0 <= c < 2^256."""
+        if self.p is None:
+            raise ECRuntimeError("ModKey.verify_values needs set_crt(p, q) first")
+        k = len(proof_tags)
+        if not (k == len(fdhs) == len(coefs) == len(ss)):
+            raise ValueError("operands differ in length")
+        if any(s < 0 for s in ss) or e < 0:
+            raise ValueError("negative exponent")
+        if not k:
+            return [], []
+        values = np.empty((k, NBYTES), dtype=np.uint8)
+        status = np.zeros(k, dtype=np.int32)
+        ins = [to_be(proof_tags), to_be(fdhs), to_be(coefs, 32), to_be(ss)]  # alive across the call
+        self._check(self.lib.sec_apdp_verify_batch(
+            self.engine._ctx, self._key, *(x.ctypes.data for x in ins), e.to_bytes(NBYTES, "big"), k,
+            values.ctypes.data, status.ctypes.data, SEC_F_HOST))
+        return from_be(values), [int(x) for x in status]
 
     def gpow(self, exps) -> list[int]:
         """``[pow(g, e, n) ...]`` from the key's fixed-base table of g (needs set_tag), e < 2^2048."""

@@ -32,6 +32,7 @@
 
 #include "task_pool.hpp"
 #include "bignum.hpp"
+#include "bn_host.hpp"
 #include "gf_host.hpp"
 #include "kernels.hpp"
 #include "storb_ec.h"
@@ -1051,6 +1052,7 @@ struct sec_bn_key {
     DevBuf dk;     // TagKey, then 1 KiB of upload staging
     DevBuf table;  // fixed-base table of g (sec::kGTabWords u32), once set_tag ran
     bool has_tag = false, has_crt = false;
+    sec::bnh::Limbs hp, hq;  // the factors on the host too (set_crt): sec_apdp_verify_batch's exponents
     mutable DevBuf rpow;              // R^(j S) mod n (Montgomery form), j < rpow_count
     mutable uint32_t rpow_count = 0;  // grown on demand by the segmented reductions
 };
@@ -2440,9 +2442,12 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
 // sub-plan's messages (descriptors device-resident at plan.meta + sp.off_msgs).
 // seg_bytes > 0 also splits each message into segments of seg_bytes counted from its end
 // (the least significant bytes of a big-endian integer) for the bignum reductions.
-template <class Launch>
+// `scatter_out(sp, stage, jobs)`, when given, replaces the host-mode copy of a sub-plan's
+// out_per * nmsgs staged output bytes into `out` (a kernel with several output arrays).
+template <class Launch, class ScatterOut = std::nullptr_t>
 int msg_batch(sec_ctx *ctx, Plan &plan, const sec_msg *msgs, int64_t nmsgs, uint8_t *out, size_t out_per,
-              unsigned flags, size_t slab, int kind, const char *what, uint64_t seg_bytes, Launch launch_kernel)
+              unsigned flags, size_t slab, int kind, const char *what, uint64_t seg_bytes, Launch launch_kernel,
+              ScatterOut scatter_out = nullptr)
 {
     // SHA-1 launches through kernels.hip, whose dispatches carry the timing events; the bignum
     // kernels (kind 3) are launched plainly, so their timing takes event records around them
@@ -2467,6 +2472,7 @@ int msg_batch(sec_ctx *ctx, Plan &plan, const sec_msg *msgs, int64_t nmsgs, uint
     key.put(flags & ~SEC_F_ASYNC);  // ASYNC does not change the plan
     key.put(slab);
     key.put(seg_bytes);
+    key.put(out_per);  // the calls that share a plan differ in it (a sub-plan's out_bytes)
     if (!(plan.valid && plan.key == key.bytes)) {
         plan.valid = false;
         const auto ranges =
@@ -2516,7 +2522,10 @@ int msg_batch(sec_ctx *ctx, Plan &plan, const sec_msg *msgs, int64_t nmsgs, uint
         }
     };
     auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        jobs.push_back(sec::CopyJob{out + sp.dig_first * out_per, stage, (size_t)sp.nmsgs * out_per});
+        if constexpr (std::is_same_v<ScatterOut, std::nullptr_t>)
+            jobs.push_back(sec::CopyJob{out + sp.dig_first * out_per, stage, (size_t)sp.nmsgs * out_per});
+        else
+            scatter_out(sp, stage, jobs);
     };
     auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
         hipEvent_t t0;
@@ -3535,6 +3544,8 @@ int sec_bn_key_set_crt(sec_ctx *ctx, sec_bn_key *key, const uint8_t *p_be, const
     const uint32_t off = 0;  // tags need dp / dq too: CRT tags switch on in set_tag
     CK(hipMemcpyAsync(&tk->crt, &off, sizeof(off), hipMemcpyHostToDevice, s));
     CK(hipStreamSynchronize(s));
+    key->hp = sec::bnh::load_be(p_be, 128);
+    key->hq = sec::bnh::load_be(q_be, 128);
     key->has_crt = true;
     return SEC_OK;
 }
@@ -3692,6 +3703,148 @@ int sec_bn_mulmod_batch(sec_ctx *ctx, const sec_bn_key *key, const uint8_t *a, c
                        [&](const std::vector<const uint8_t *> &in, uint8_t *o, hipStream_t s) {
                            return sec_launch_bn_mulmod(dk, in[0], in[1], (uint32_t)count, o, s);
                        });
+}
+
+int sec_bn_crt_modexp2_batch(sec_ctx *ctx, const sec_bn_key *key, const uint8_t *a, const uint8_t *b,
+                             const uint8_t *ea_p, const uint8_t *ea_q, const uint8_t *eb_p, const uint8_t *eb_q,
+                             uint32_t exp_bytes, int64_t count, uint8_t *out, unsigned flags)
+{
+    if (!ctx || !key || key->device != ctx->device || count < 0 || count >= (int64_t)INT32_MAX ||
+        (count > 0 && (!a || !b || !ea_p || !ea_q || !eb_p || !eb_q || !out)) ||
+        (flags & ~(SEC_F_HOST | SEC_F_ASYNC)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
+        return SEC_EINVAL;
+    if (!key->has_crt)
+        return SEC_ENOCRT;
+    if (exp_bytes < 1 || exp_bytes > 4096)
+        return SEC_EINVAL;
+    if (count == 0)
+        return SEC_OK;
+    const sec::TagKey *tk = key->dk.as<sec::TagKey>();
+    const size_t nb = (size_t)count * 256, eb = (size_t)count * exp_bytes;
+    return dense_batch(ctx, {{a, nb}, {b, nb}, {ea_p, eb}, {ea_q, eb}, {eb_p, eb}, {eb_q, eb}}, out, nb, flags,
+                       "sec_bn_crt_modexp2_kernel",
+                       [&](const std::vector<const uint8_t *> &in, uint8_t *o, hipStream_t s) {
+                           return sec_launch_bn_crt_modexp2(tk, in[0], in[1], in[2], in[3], in[4], in[5], exp_bytes,
+                                                            (uint32_t)count, o, s);
+                       });
+}
+
+int sec_apdp_prove_batch(sec_ctx *ctx, const sec_bn_key *key, const sec_msg *msgs, int64_t nmsgs,
+                         const uint8_t *tags, const uint8_t *g_ss, const uint8_t *coefs, uint8_t *tag_c,
+                         uint8_t *block, uint8_t *rho, unsigned flags)
+{
+    if (!ctx || !key || key->device != ctx->device || nmsgs < 0 || nmsgs >= (int64_t)INT32_MAX ||
+        (nmsgs > 0 && (!msgs || !tags || !g_ss || !coefs || !tag_c || !block || !rho)) ||
+        (flags & ~(SEC_F_HOST | SEC_F_ASYNC)) || ((flags & SEC_F_HOST) && (flags & SEC_F_ASYNC)))
+        return SEC_EINVAL;
+    if (nmsgs == 0)
+        return SEC_OK;
+    const bool host = flags & SEC_F_HOST;
+    const sec::BnKey *dk = key->dk.as<sec::BnKey>();
+    const size_t n = (size_t)nmsgs;
+    // per-message operands: the caller's device arrays, or (host) uploaded whole ahead of the slabs
+    const uint8_t *dtags = tags, *dgs = g_ss, *dcoefs = coefs;
+    if (host) {
+        RC(set_dev(ctx));
+        RC(ctx->bn_scratch.ensure(n * 544));
+        uint8_t *d = ctx->bn_scratch.as<uint8_t>();
+        CK(hipMemcpyAsync(d, tags, n * 256, hipMemcpyHostToDevice, ctx->stream()));
+        CK(hipMemcpyAsync(d + n * 256, g_ss, n * 256, hipMemcpyHostToDevice, ctx->stream()));
+        CK(hipMemcpyAsync(d + n * 512, coefs, n * 32, hipMemcpyHostToDevice, ctx->stream()));
+        dtags = d;
+        dgs = d + n * 256;
+        dcoefs = d + n * 512;
+    }
+    bool prepared = false;
+    // host mode: a sub-plan's staged output is its tag_c rows, then its block rows, then its rho rows
+    return msg_batch(
+        ctx, ctx->bn_plan, msgs, nmsgs, tag_c, 800, flags, (size_t)ctx->opt[O_SLAB_BYTES_DIGEST], 3, "sec_apdp_prove",
+        kSegBytes,
+        [&](const uint8_t *base0, const Plan &plan, const SubPlan &sp, size_t idx, uint8_t *o, hipStream_t s) {
+            if (!prepared) {
+                RC(bn_prepare(ctx, key, plan, host));
+                prepared = true;
+            }
+            const size_t f = host ? (size_t)sp.dig_first : 0, m = sp.nmsgs;
+            return sec_launch_apdp_prove(dk, key->rpow.as<uint32_t>(), base0, nullptr,
+                                         plan.meta.as<sec::MsgDesc>(sp.off_msgs), sp.nmsgs,
+                                         plan.meta.as<sec::SegDesc>(sp.off_segs), sp.nsegs,
+                                         plan.meta.as<sec::SegInfo>(sp.off_seginfo), bn_part(ctx, idx, host),
+                                         dtags + f * 256, dgs + f * 256, dcoefs + f * 32, host ? o : tag_c,
+                                         host ? o + m * 256 : block, host ? o + m * 544 : rho, s);
+        },
+        [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
+            const size_t f = (size_t)sp.dig_first, m = sp.nmsgs;
+            jobs.push_back(sec::CopyJob{tag_c + f * 256, stage, m * 256});
+            jobs.push_back(sec::CopyJob{block + f * 288, stage + m * 256, m * 288});
+            jobs.push_back(sec::CopyJob{rho + f * 256, stage + m * 544, m * 256});
+        });
+}
+
+int sec_apdp_verify_batch(sec_ctx *ctx, const sec_bn_key *key, const uint8_t *proof_tags, const uint8_t *fdhs,
+                          const uint8_t *coefs, const uint8_t *ss, const uint8_t *e_be, int64_t count,
+                          uint8_t *values, int32_t *status, unsigned flags)
+{
+    if (!ctx || !key || key->device != ctx->device || count < 0 || count >= (int64_t)INT32_MAX ||
+        (count > 0 && (!proof_tags || !fdhs || !coefs || !ss || !e_be || !values || !status)) || flags != SEC_F_HOST)
+        return SEC_EINVAL;
+    if (!key->has_crt)
+        return SEC_ENOCRT;
+    if (count == 0)
+        return SEC_OK;
+    // (T^e * (F^c)^-1)^s = T^(e s) * F^(-c s) mod each factor h when F^c is invertible: the
+    // exponents reduced for h - 1 here, then one joint exponentiation per factor on the device
+    namespace bnh = sec::bnh;
+    const size_t n = (size_t)count;
+    std::vector<uint8_t> exps;
+    try {
+        exps.resize(n * 512);  // ea_p, ea_q, eb_p, eb_q: n x 128 B each
+        const bnh::Limbs one(1, 1u), e = bnh::load_be(e_be, 256);
+        const bnh::Limbs pm1 = bnh::sub(key->hp, one), qm1 = bnh::sub(key->hq, one);
+        auto derive = [&](size_t i0, size_t i1) {
+            for (size_t i = i0; i < i1; ++i) {
+                const bnh::Limbs c = bnh::load_be(coefs + i * 32, 32), s = bnh::load_be(ss + i * 256, 256);
+                const bnh::Limbs f = bnh::load_be(fdhs + i * 256, 256);
+                const bnh::Limbs es = bnh::mul(e, s), cs = bnh::mul(c, s);
+                // c == 0: F^c = 1, invertible whatever F is (and cs = 0 gives b = 0)
+                status[i] = !bnh::is_zero(c) &&
+                            (bnh::is_zero(bnh::mod(f, key->hp)) || bnh::is_zero(bnh::mod(f, key->hq)));
+                uint8_t *x = exps.data() + i * 128;
+                bnh::store_be(bnh::pos_exp(es, pm1), x, 128);
+                bnh::store_be(bnh::pos_exp(es, qm1), x + n * 128, 128);
+                bnh::store_be(bnh::neg_exp(cs, pm1), x + n * 256, 128);
+                bnh::store_be(bnh::neg_exp(cs, qm1), x + n * 384, 128);
+            }
+            return true;
+        };
+        constexpr size_t kPer = 64;  // items per task
+        if (n <= kPer) {
+            derive(0, n);
+        } else {
+            sec::TaskPool &tp = tasks(ctx);
+            sec::TaskPool::Group g;
+            for (size_t i0 = 0; i0 < n; i0 += kPer)
+                tp.submit(g, [&derive, i0, n] { return derive(i0, std::min(n, i0 + kPer)); });
+            if (!tp.wait(g))  // a task threw: no memory for its limbs
+                return SEC_ENOMEM;
+        }
+    } catch (const std::bad_alloc &) {
+        return SEC_ENOMEM;
+    }
+    const sec::TagKey *tk = key->dk.as<sec::TagKey>();
+    const uint8_t *x = exps.data();
+    RC(dense_batch(ctx,
+                   {{proof_tags, n * 256}, {fdhs, n * 256}, {x, n * 128}, {x + n * 128, n * 128},
+                    {x + n * 256, n * 128}, {x + n * 384, n * 128}},
+                   values, n * 256, SEC_F_HOST, "sec_bn_crt_modexp2_kernel",
+                   [&](const std::vector<const uint8_t *> &in, uint8_t *o, hipStream_t s) {
+                       return sec_launch_bn_crt_modexp2(tk, in[0], in[1], in[2], in[3], in[4], in[5], 128,
+                                                        (uint32_t)count, o, s);
+                   }));
+    for (size_t i = 0; i < n; ++i)
+        if (status[i])
+            memset(values + i * 256, 0, 256);
+    return SEC_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -369,6 +369,107 @@ __device__ u32 crt_half(const sec::TagKey *__restrict__ tk, const Mod &N, u32 x,
     return mmul<64>(N, t, h ? tk->cq_m[l] : tk->cp_m[l], l);
 }
 
+// Simultaneous two-base exponentiation a^ea * b^eb in Montgomery form by joint 2-bit windows
+// (Shamir's trick): two squarings per digit pair, then one product by tab[4i + j] = a^i * b^j
+// for the pair (i, j) != (0, 0).  `da(k)` / `db(k)` = 2-bit digit k of ea / eb counted from the
+// least significant, k < ndig.  tab: 16 x 64 u32 of LDS (mont_pow's), built with 13 products;
+// each lane reads back only what it wrote.  Leading pairs zero in both exponents cost nothing;
+// both exponents zero give M.one.  Two mont_mul call sites, as in mont_pow.
+template <int ROWS, class DigA, class DigB>
+__device__ u32 mont_pow2(const Mod &M, u32 a_m, u32 b_m, u32 l, u32 ndig, DigA da, DigB db, u32 *tab)
+{
+    tab[l] = M.one;
+    tab[64 + l] = b_m;
+    tab[4 * 64 + l] = a_m;
+#pragma unroll 1
+    for (u32 w = 2; w < 16; ++w) {
+        if (w == 4)
+            continue;
+        // a row's first entry a^i from the row above, the others from their left neighbour
+        const bool left = (w & 3u) != 0;
+        tab[w * 64 + l] = mmul<ROWS>(M, tab[(left ? w - 1 : w - 4) * 64 + l], left ? b_m : a_m, l);
+    }
+    u32 i = ndig, r = M.one;
+    while (i > 0) {
+        --i;
+        const u32 v = 4 * da(i) + db(i);
+        if (v) {
+            r = tab[v * 64 + l];
+            break;
+        }
+    }
+#pragma unroll 1
+    for (; i > 0; --i) {
+        const u32 v = 4 * da(i - 1) + db(i - 1);
+        const u32 ops = v ? 3u : 2u;  // 2 squarings, then the table product
+#pragma unroll 1
+        for (u32 s = 0; s < ops; ++s)
+            r = mmul<ROWS>(M, r, s < 2 ? r : tab[v * 64 + l], l);
+    }
+    return r;
+}
+
+// 2-bit digit k (from the least significant) of an nbytes-long big-endian integer
+__device__ __forceinline__ u32 be_dig2(const u8 *e, u32 nbytes, u32 k) { return (e[nbytes - 1 - k / 4] >> (2 * (k % 4))) & 3u; }
+
+__device__ __forceinline__ void add96(u64 &lo, u32 &hi, u64 p)
+{
+    const u64 s = lo + p;
+    hi += s < lo ? 1u : 0u;
+    lo = s;
+}
+
+// The plain product c * X (c < 2^256 in limbs 0..7 of `c`, X < 2^2048 one limb per lane) as 72
+// limbs, big-endian into the 288 bytes at `be`.  Lane l sums column l (the products c_i *
+// X_(l-i)) and, in a second pass, lanes 0..7 column 64 + l, each in a 96-bit accumulator (8
+// products < 2^64); the carries are then resolved one column after another, every lane running
+// the same scalar chain over the broadcast columns and keeping its own limbs.
+__device__ void store_cx(u8 *be, u32 c, u32 X, u32 l)
+{
+    u64 lo = 0, lo2 = 0;
+    u32 hi = 0, hi2 = 0;
+#pragma unroll
+    for (u32 i = 0; i < 8; ++i) {
+        const u32 ci = bcast(c, i);
+        // lane l < i reads X_(64+l-i): its term of column 64 + l
+        const u32 x = (u32)__builtin_amdgcn_ds_bpermute((int)(((l - i) & 63u) << 2), (int)X);
+        const u64 p = (u64)ci * x;
+        if (l >= i)
+            add96(lo, hi, p);
+        else
+            add96(lo2, hi2, p);
+    }
+    u64 carry = 0;  // < 2^36: a column is < 2^67
+    u32 limb = 0, limb2 = 0;
+#pragma unroll 1
+    for (u32 k = 0; k < 72; ++k) {
+        const u32 src = k & 63u;
+        const u32 w0 = bcast(k < 64 ? (u32)lo : (u32)lo2, src);
+        const u32 w1 = bcast(k < 64 ? (u32)(lo >> 32) : (u32)(lo2 >> 32), src);
+        const u32 w2 = bcast(k < 64 ? hi : hi2, src);
+        const u64 s = carry + w0;
+        carry = (s >> 32) + ((u64)w2 << 32 | w1);
+        if (l == src) {
+            if (k < 64)
+                limb = (u32)s;
+            else
+                limb2 = (u32)s;
+        }
+    }
+    u8 *p = be + 284 - 4 * l;
+    p[0] = (u8)(limb >> 24);
+    p[1] = (u8)(limb >> 16);
+    p[2] = (u8)(limb >> 8);
+    p[3] = (u8)limb;
+    if (l < 8) {
+        u8 *q = be + 28 - 4 * l;
+        q[0] = (u8)(limb2 >> 24);
+        q[1] = (u8)(limb2 >> 16);
+        q[2] = (u8)(limb2 >> 8);
+        q[3] = (u8)limb2;
+    }
+}
+
 // ---- kernels (one wave per integer unless stated) ---------------------------------
 
 // BnKey from a big-endian modulus of `bits` (2048 or 1024, top bit set, odd):
@@ -626,7 +727,96 @@ __global__ __launch_bounds__(128) void sec_apdp_tag_kernel(const sec::TagKey *__
     }
 }
 
+// out_i = a_i^ea * b_i^eb mod n by CRT with per-item exponents for p and q (exp_bytes each).
+// Two waves per item as sec_bn_crt_modexp_kernel: wave 0 the p half, wave 1 the q half; each
+// reduces both bases to its factor, runs one joint exponentiation and weighs the result with
+// cp / cq; the halves are summed through LDS.
+__global__ __launch_bounds__(128) void sec_bn_crt_modexp2_kernel(const sec::TagKey *__restrict__ tk, const u8 *a,
+                                                                 const u8 *b, const u8 *ea_p, const u8 *ea_q,
+                                                                 const u8 *eb_p, const u8 *eb_q, u32 exp_bytes,
+                                                                 u32 count, u8 *out)
+{
+    __shared__ u32 tab[2][16 * 64];
+    __shared__ u32 part[64];
+    const u32 i = blockIdx.x;
+    if (i >= count)
+        return;
+    const u32 l = lane_id(), w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);  // wave-uniform
+    const Mod N = load_mod(&tk->k, l);
+    const Mod H = load_mod(w ? &tk->q : &tk->p, l);
+    const u8 *ea = (w ? ea_q : ea_p) + (u64)i * exp_bytes;
+    const u8 *eb = (w ? eb_q : eb_p) + (u64)i * exp_bytes;
+    const u32 am = to_half_m(H, load_be_limb(a + (u64)i * 256, l), l);
+    const u32 bm = to_half_m(H, load_be_limb(b + (u64)i * 256, l), l);
+    const u32 rm = mont_pow2<32>(
+        H, am, bm, l, 4 * exp_bytes, [&](u32 k) { return be_dig2(ea, exp_bytes, k); },
+        [&](u32 k) { return be_dig2(eb, exp_bytes, k); }, tab[w]);
+    const u32 t = mmul<32>(H, rm, l == 0 ? 1u : 0u, l);  // plain, < h
+    const u32 y = mmul<64>(N, t, w ? tk->cq_m[l] : tk->cp_m[l], l);
+    if (w)
+        part[l] = y;
+    __syncthreads();
+    if (!w)
+        store_be_limb(out + (u64)i * 256, l, add_mod(y, part[l], N.n, l));
+}
+
+// APDP generate_proof for one piece, X = piece mod n (summed from its segments' residues) and
+// c = the challenge coefficient (32 B).  Two waves per piece: wave 0 writes T^c mod n and the
+// plain product c * X, wave 1 rho = (g_s^c)^X mod n, which is g_s^(c * X) without a 2304-bit
+// exponent.  Both take the c power through the same code (base T or g_s); wave 1 goes round
+// once more with X's 512 nibbles.  The waves share nothing, so there is no barrier, and each is
+// a workgroup of its own: wave 1 does nine times wave 0's products, and as the two waves of one
+// workgroup the long ones were placed unevenly over a CU's SIMDs (measured: DESIGN.md §5).  The
+// long waves are blocks 0 .. nmsgs-1 so that they start first.
+__global__ __launch_bounds__(64) void sec_apdp_prove_kernel(const sec::BnKey *__restrict__ key,
+                                                            const sec::SegInfo *__restrict__ info, u32 nmsgs,
+                                                            const u32 *__restrict__ partials, const u8 *tags,
+                                                            const u8 *g_ss, const u8 *coefs, u8 *tag_c, u8 *block,
+                                                            u8 *rho)
+{
+    __shared__ u32 tab[16 * 64];
+    if (blockIdx.x >= 2 * nmsgs)
+        return;
+    const u32 w = blockIdx.x < nmsgs ? 1u : 0u, i = blockIdx.x - (w ? 0u : nmsgs);  // block-uniform
+    const u32 l = lane_id();
+    const Mod N = load_mod(key, l);
+    const u32 X = combine(N, partials, info[i], l);
+    const u32 c = load_be(coefs + (u64)i * 32, 32, l);
+    u32 r = mmul<64>(N, load_be_limb((w ? g_ss : tags) + (u64)i * 256, l), N.r2, l);
+#pragma unroll 1
+    for (u32 pass = 0; pass <= w; ++pass)
+        r = mont_pow<64>(N, r, l, pass ? 512u : 64u, [&](u32 k) { return limb_nib(pass ? X : c, k); }, tab);
+    store_be_limb((w ? rho : tag_c) + (u64)i * 256, l, mmul<64>(N, r, l == 0 ? 1u : 0u, l));
+    if (!w)
+        store_cx(block + (u64)i * 288, c, X, l);
+}
+
 }  // namespace
+
+int sec_launch_bn_crt_modexp2(const sec::TagKey *tk, const uint8_t *a, const uint8_t *b, const uint8_t *ea_p,
+                              const uint8_t *ea_q, const uint8_t *eb_p, const uint8_t *eb_q, uint32_t exp_bytes,
+                              uint32_t count, uint8_t *out, void *stream)
+{
+    if (count == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(sec_bn_crt_modexp2_kernel, dim3(count), dim3(128), 0, (hipStream_t)stream, tk, a, b, ea_p, ea_q,
+                       eb_p, eb_q, exp_bytes, count, out);
+    return hipGetLastError();
+}
+
+int sec_launch_apdp_prove(const sec::BnKey *key, const uint32_t *P, const uint8_t *base0, const uint8_t *base1,
+                          const sec::MsgDesc *msgs, uint32_t nmsgs, const sec::SegDesc *segs, uint32_t nsegs,
+                          const sec::SegInfo *info, uint8_t *partials, const uint8_t *tags, const uint8_t *g_ss,
+                          const uint8_t *coefs, uint8_t *tag_c, uint8_t *block, uint8_t *rho, void *stream)
+{
+    if (nmsgs == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(sec_bn_reduce_seg_kernel, dim3(nsegs), dim3(64), 0, (hipStream_t)stream, key, P, base0, base1,
+                       msgs, segs, nsegs, (u32 *)partials);
+    hipLaunchKernelGGL(sec_apdp_prove_kernel, dim3(2 * nmsgs), dim3(64), 0, (hipStream_t)stream, key, info, nmsgs,
+                       (const u32 *)partials, tags, g_ss, coefs, tag_c, block, rho);
+    return hipGetLastError();
+}
 
 int sec_launch_bn_setup(const uint8_t *n_be, uint32_t n0inv, uint32_t bits, sec::BnKey *key, void *stream)
 {

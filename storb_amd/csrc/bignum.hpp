@@ -71,6 +71,11 @@ int sec_launch_bn_modexp(const sec::BnKey *key, const uint8_t *bases, const uint
                          uint32_t count, uint8_t *out, void *stream);
 int sec_launch_bn_crt_modexp(const sec::TagKey *tk, const uint8_t *bases, const uint8_t *exps_p,
                              const uint8_t *exps_q, uint32_t exp_bytes, uint32_t count, uint8_t *out, void *stream);
+// out_i = a_i^ea_i * b_i^eb_i mod n by CRT: one joint exponentiation per factor (exponents per
+// factor as sec_launch_bn_crt_modexp's, exp_bytes each).
+int sec_launch_bn_crt_modexp2(const sec::TagKey *tk, const uint8_t *a, const uint8_t *b, const uint8_t *ea_p,
+                              const uint8_t *ea_q, const uint8_t *eb_p, const uint8_t *eb_q, uint32_t exp_bytes,
+                              uint32_t count, uint8_t *out, void *stream);
 int sec_launch_bn_mulmod(const sec::BnKey *key, const uint8_t *a, const uint8_t *b, uint32_t count, uint8_t *out,
                          void *stream);
 int sec_launch_apdp_gpow(const sec::TagKey *tk, const uint32_t *table, const uint8_t *exps, uint32_t exp_bytes,
@@ -78,4 +83,11 @@ int sec_launch_apdp_gpow(const sec::TagKey *tk, const uint32_t *table, const uin
 int sec_launch_apdp_tag(const sec::TagKey *tk, const uint32_t *table, const uint32_t *P, const uint8_t *base0,
                         const uint8_t *base1, const sec::MsgDesc *msgs, uint32_t nmsgs, const sec::SegDesc *segs,
                         uint32_t nsegs, const sec::SegInfo *info, uint8_t *partials, uint8_t *tags, void *stream);
+// generate_proof per message (messages and segments as sec_launch_apdp_tag's): tag_c = tags_i^c_i
+// mod n (256 B), block = c_i * (message mod n) (288 B, plain), rho = g_ss_i^(c_i * X_i) mod n
+// (256 B); tags, g_ss: 256 B each, coefs: 32 B each, all big-endian.
+int sec_launch_apdp_prove(const sec::BnKey *key, const uint32_t *P, const uint8_t *base0, const uint8_t *base1,
+                          const sec::MsgDesc *msgs, uint32_t nmsgs, const sec::SegDesc *segs, uint32_t nsegs,
+                          const sec::SegInfo *info, uint8_t *partials, const uint8_t *tags, const uint8_t *g_ss,
+                          const uint8_t *coefs, uint8_t *tag_c, uint8_t *block, uint8_t *rho, void *stream);
 }
