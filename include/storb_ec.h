@@ -302,7 +302,9 @@ typedef struct sec_chk_result {
  * bytes of the block exist, the rest read as zero (so the prediction there must be zero), and
  * nothing past them is read.
  * A chunk with n == k has nothing to check: it is consistent and launches nothing.  More than 8
- * check rows take ceil((n - k) / 8) passes over the basis.
+ * check rows take ceil((n - k) / 8) passes over the basis on the direct (v_perm) kernels; a chunk
+ * whose basis is its k data blocks may take the bit-sliced check kernel instead, one pass per
+ * 16-row group whatever n - k (sec_check_method, option "SEC_CHECK_BS").  The results are the same.
  * results, row_bad and column live where the blocks live: device memory, or host memory with
  * SEC_F_HOST.  Nothing is ever written to the blocks.  Every call starts from clean state.
  * Flags: none (device pointers; SEC_F_ASYNC allowed) or SEC_F_HOST (host pointers, always staged
@@ -330,10 +332,12 @@ int sec_check_batch(sec_ctx *ctx, const sec_chk_chunk *chunks, int64_t nchunks,
  * The first k entries may be any k distinct blocks in any order.  block_avail (nullable) has the
  * meaning both calls give it, for basis entries and check rows alike.  A chunk with n == k is a
  * plain decode and is reported consistent.  `blocks` may be NULL (absolute block_offs).  Nothing is
- * ever written to the blocks; every call starts from clean state.  The call always takes the
- * direct (v_perm) kernels, never the syndrome path; sec_ctx_decode_paths and
- * sec_ctx_decode_methods do not count it, and sec_ctx_host_paths counts a SEC_F_HOST call as staged
- * (as sec_check_batch's).
+ * ever written to the blocks; every call starts from clean state.  A chunk that lost a
+ * primary always takes the direct (v_perm) kernels, never the syndrome path; one whose first k
+ * entries are its k data blocks may take the bit-sliced check kernel, which copies them to `out`
+ * while it checks (sec_check_method, option "SEC_CHECK_BS"; one call may hold both kinds).
+ * sec_ctx_decode_paths and sec_ctx_decode_methods do not count this call (sec_ctx_check_methods
+ * does), and sec_ctx_host_paths counts a SEC_F_HOST call as staged (as sec_check_batch's).
  * Aliasing: sec_decode_batch's rule (no output range may overlap any block of the call).
  * Flags: none or SEC_F_ASYNC (device pointers); SEC_F_RECOVER in either mode; SEC_F_HOST (host
  * pointers) is ALWAYS staged through pinned slabs as sec_check_batch's: n*B bytes per chunk are
@@ -423,6 +427,23 @@ int sec_repair_check_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t n
  * also for a NULL column or culprit. */
 int sec_check_locate(int k, int m, const int32_t *sharenums, int n, const uint8_t *column,
                      int32_t *culprit);
+
+/* Whether a chunk of sec_check_batch / sec_decode_check_batch is eligible for the bit-sliced check
+ * kernel (host logic, no device needed): *method = 1 when (k, m) is one of the bit-sliced shapes
+ * ((10,14), (8,12), (16,24), (32,48), (64,96), (8,11)), B >= 16, n > k, the first k sharenums are
+ * the data blocks 0 .. k-1 in any order, every entry but data block k-1 is readable to B
+ * (block_avail: the chunk's n entries, nullable = all B) and padlen < B (0 for a check); else 0.
+ * Eligibility alone: whether an eligible chunk takes that kernel is option "SEC_CHECK_BS" (-1 the
+ * measured rule, 0 never, 1 always).
+ * Errors: sec_check_batch's for the same arguments, in its order (SEC_EINVAL also for a NULL
+ * method or padlen < 0). */
+int sec_check_method(int k, int m, const int32_t *sharenums, int n, uint64_t B,
+                     const uint64_t *block_avail, int64_t padlen, int *method);
+
+/* Chunks with at least one check row that sec_check_batch and sec_decode_check_batch have sent to
+ * the bit-sliced check kernel and to the direct kernels on this context (cumulative; either
+ * pointer nullable). */
+int sec_ctx_check_methods(sec_ctx *ctx, int64_t *bitsliced, int64_t *direct);
 
 /* ---- piece ids: SHA-1 (piece_hash, /root/reference/storb/util/piece.py:54-68) ----
  * A message is `len` bytes at `addr`, of which the first `avail` exist in

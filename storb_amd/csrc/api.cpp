@@ -229,6 +229,7 @@ enum Opt {
     O_COPY_THREADS,      // 0 rule, or host copy-pool threads
     O_REGISTER_MIN,      // page-lock pageable host buffers for calls moving >= this many bytes (0: never)
     O_HOST_JOIN,         // 0: the GPU writes every byte of a host reassembly
+    O_CHECK_BS,          // bit-sliced check: -1 rule (check_bs_rule), 0 never, 1 every eligible chunk
     O_COUNT
 };
 
@@ -249,6 +250,7 @@ constexpr OptSpec kOpts[O_COUNT] = {
     {"SEC_COPY_THREADS", 0, 0, 256},
     {"SEC_REGISTER_MIN", (int64_t)4 << 20, 0, (int64_t)1 << 62},
     {"SEC_HOST_JOIN", 1, 0, 1},
+    {"SEC_CHECK_BS", -1, -1, 1},
 };
 
 struct Options {
@@ -304,6 +306,10 @@ struct SubPlan {
     size_t off_cpos = 0, off_echunk = 0;   // the entries' caller positions and chunks (ChkSlots)
     uint32_t nentries = 0;                 // entries of the unit's chunks (operations with compared rows)
     size_t off_cdesc = 0;                  // the chunks' ChkDesc (sec_check_final)
+    // bit-sliced checks (sec_check_bs_kernel): launches as (shape, (first, count)) in their tiles;
+    // their descriptors, tiles and per-block addresses, avails and parity-row -> check-row maps
+    std::vector<std::pair<int, std::pair<uint32_t, uint32_t>>> cbs;
+    size_t off_bdesc = 0, off_btiles = 0, off_bsoff = 0, off_bsavail = 0, off_brmap = 0;
     // host mode's slab output: the results at 0, then row_bad and column, then the stored rows
     // (targets or decoded bytes), then the digests (dig_off)
     uint64_t chk_rows = 0, chk_col = 0, pay_off = 0;
@@ -326,6 +332,8 @@ struct Plan {
     DevBuf meta;  // device copy of the metadata image of every sub-plan
     bool valid = false;
     int64_t nsyn = 0, ndirect = 0, nfused = 0;  // decode: chunks with a lost primary, by method
+                                                // (check, decode + check: chunks with a check row,
+                                                // bit-sliced in nsyn, direct in ndirect)
     uint64_t nflags = 0;                        // check: flag words of the whole call
 };
 
@@ -719,6 +727,7 @@ struct sec_ctx {
     // SEC_F_HOST encode / decode calls by path (sec_ctx_host_paths)
     int64_t zero_copy_calls = 0, registered_calls = 0, staged_calls = 0;
     int64_t syn_chunks = 0, direct_chunks = 0, fused_chunks = 0;  // decodes by method (sec_ctx_decode_paths)
+    int64_t chk_bs_chunks = 0, chk_direct_chunks = 0;  // checked chunks by kernel (sec_ctx_check_methods)
 
     hipStream_t stream() const { return ext ? ext : own; }
     hipEvent_t ev()
@@ -1316,6 +1325,59 @@ template <class Chunk>
 uint64_t slot_avail(const Chunk &c, const uint64_t *block_avail, int j)
 {
     return block_avail ? std::min<uint64_t>(block_avail[c.slot0 + j], c.B) : c.B;
+}
+
+// Bit-sliced check (kernels_bs.hip sec_check_bs_kernel): the shape of its kernel for a chunk of a
+// check or a decode + check whose arguments passed the call's screen, or -1 (the direct kernels).
+// Eligible when
+//   * (k, m) is one of the bit-sliced shapes, 16 <= B (below it the tail kernel) and at least one
+//     check row is held (n > k);
+//   * the first k entries are the data blocks 0 .. k-1 in any order, so the check rows are zfec's
+//     own parity rows and nothing is recovered (a decode + check with a missing primary holds a
+//     parity row in its basis);
+//   * every entry's avail is one phase 1's loader honours: that loader clamps its addresses to
+//     B - 16 and reads whole 16-byte pieces, taking the zero-filling byte path for data block k-1
+//     alone (zfec's padded last block read in place), so every other entry, data or parity, must
+//     be readable to B; block k-1 may have any avail;
+//   * padlen < B (only output row k-1 is short), as the syndrome decode asks.
+// avail: the chunk's n entries in the caller's order, or NULL (all B).
+int check_bs_shape(int k, int m, const int32_t *sn, int n, uint64_t B, const uint64_t *avail, uint64_t padlen)
+{
+    const int sh = sec_bs_shape(k, m);
+    if (sh < 0 || n <= k || B < 16 || B > 0xFFFFFFFFull - 8192 || padlen >= B)
+        return -1;
+    for (int j = 0; j < k; ++j)
+        if (sn[j] >= k)
+            return -1;
+    for (int e = 0; avail && e < n; ++e)
+        if (sn[e] != k - 1 && avail[e] < B)
+            return -1;
+    return sh;
+}
+
+// Whether an eligible chunk takes the bit-sliced check.  SEC_CHECK_BS = 0 never, 1 always; the
+// default takes it only where it measured at least 5 % faster than the direct kernels (rounds differ
+// by up to 3 %, boxes by 1-3 %), by shape, block size and whether the kernel also copies the data
+// blocks (a decode + check that reassembles); everything else, and every size not measured, stays
+// direct (tools/bench_check_bs.py [--extra], profiles/check_bs_rate.json; DESIGN §5 "Check,
+// bit-sliced").
+bool check_bs_rule(const Options &o, int shape, uint64_t B, bool copies)
+{
+    if (o[O_CHECK_BS] >= 0)
+        return o[O_CHECK_BS] == 1;
+    // direct ms / bit-sliced ms, check | decode + check (copies), every piece held:
+    //   (32,48)  B 4 KiB 1.33 | 1.39, 32 KiB 1.99 | 1.42, 2 MiB 2.20 | 1.55
+    //   (64,96)  B 4 KiB 1.57 | 1.64, 16 KiB 2.45 | 2.09, 4 MiB 2.69 | 2.61
+    //   (16,24)  B 64 KiB 1.26 | 0.91, 512 KiB 1.27 | 0.90, but 4 KiB 0.86 | 0.83: the check alone, from 64 KiB
+    //   (10,14)  B 6554 1.14 | 1.22, but 102 KiB 0.94 | 1.00, 819 KiB 0.95 | 0.98: small blocks only
+    //   (8,12)   B 8 KiB 1.03 | 0.92, 512 KiB 1.00 | 0.91;  (8,11) mixed sizes 0.87 | 0.91: never
+    switch (shape) {
+    case 0: return B <= (8u << 10);
+    case 2: return !copies && B >= (64u << 10);
+    case 3:
+    case 4: return B >= (4u << 10);
+    default: return false;
+    }
 }
 
 // The cache key of a table made from the k blocks idx[0..k) of a (k, m) code
@@ -1955,6 +2017,25 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
     std::vector<PendingExpand> pending;
     std::vector<uint32_t> tab_of, ns_of((size_t)nchunks, 0);
     std::vector<int> rows;
+    // check and decode + check: the chunks the bit-sliced check kernel takes (its shape, else -1);
+    // they need no table and get no tile of the direct kernels.  Staged entries are all B long.
+    constexpr bool bs_op = Op::kChecks && !Op::kTargets;
+    std::vector<int> bs_of((size_t)nchunks, -1);
+    plan.nsyn = plan.ndirect = 0;
+    for (int64_t i = 0; bs_op && i < nchunks; ++i) {
+        const RowChunk c = Op::view(chunks[i]);
+        if (c.n <= c.k)
+            continue;
+        const int sh = check_bs_shape(c.k, c.m, a.sharenums + c.slot0, c.n, c.B,
+                                      host || !a.block_avail ? nullptr : a.block_avail + c.slot0, c.padlen);
+        const bool copies = Op::kDecodes && !recover && (uint64_t)c.k * c.B > c.padlen;
+        if (sh >= 0 && check_bs_rule(ctx->opt, sh, c.B, copies)) {
+            bs_of[(size_t)i] = sh;
+            ++plan.nsyn;
+        } else {
+            ++plan.ndirect;
+        }
+    }
     auto rows_of = [&](int64_t i) {  // -> rows; ns_of[i] = how many of them are stored
         const RowChunk c = Op::view(chunks[i]);
         const int *idx = &L.idx[L.first[i]];
@@ -1971,6 +2052,8 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         return idx;
     };
     auto want = [&](int64_t i, std::string &key) -> size_t {
+        if (bs_of[(size_t)i] >= 0)  // the matrix is in the kernel (and nothing is lost: ns_of stays 0)
+            return 0;
         const int *idx = rows_of(i);
         if (rows.empty())
             return 0;
@@ -1982,6 +2065,7 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         return rows_coef(chunks[i].k, chunks[i].m, idx, rows, cf);
     };
     RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
+    const int bs_lanes = ctx->opt.lanes(O_BS_LANES);
 
     // with digests few large slabs, as the encode's digest mode (one SHA-1 chain per piece)
     const auto ranges = slab_ranges(
@@ -2001,6 +2085,10 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         std::vector<sec::MsgDesc> msgs;
         Bins bins;
         std::vector<sec::TailItem> tail;
+        std::vector<sec::CbsDesc> bdescs;
+        std::vector<uint64_t> bsoff;
+        std::vector<uint32_t> bsavail, brmap;
+        std::map<int, std::vector<sec::Tile>> btiles;  // by shape
         uint64_t nent = 0;
         if (Op::kChecks) {
             for (int64_t i = c0; i < c1; ++i)
@@ -2076,6 +2164,46 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             }
             sp.in_bytes += (uint64_t)c.n * c.B;
             sp.out_bytes += nstore;
+            if (bs_of[(size_t)i] >= 0) {
+                // its blocks by number (data j at j, parity row p at k + p), the held parity rows'
+                // check-row indices, and one tile per span and row group with a held row, in runs of
+                // 8 tiles of each group: workgroup b runs on XCD b % 8, so the tiles reading the
+                // same data blocks share an L2.  The first such group copies the data blocks.
+                const int sh = bs_of[(size_t)i], NR = sec_bs_rows(sh);
+                sec::CbsDesc b{};
+                b.out_off = r.out_off;
+                b.B = r.B;
+                b.last = (uint32_t)(Op::kDecodes && !recover ? c.B - c.padlen : c.B);
+                b.slot0 = (uint32_t)bsoff.size();
+                b.flag0 = r.flag0;
+                b.rmap0 = (uint32_t)brmap.size();
+                bsoff.resize(bsoff.size() + (size_t)c.m, 0);
+                bsavail.resize(bsavail.size() + (size_t)c.m, 0);
+                brmap.resize(brmap.size() + (size_t)(c.m - c.k), 0);
+                for (int e = 0; e < c.n; ++e) {
+                    const int sn = a.sharenums[c.slot0 + entry_from(L, i, c.k, e)];
+                    bsoff[b.slot0 + (size_t)sn] = soff[r.slot0 + (size_t)e];
+                    bsavail[b.slot0 + (size_t)sn] = savail[r.slot0 + (size_t)e];
+                    if (e >= c.k) {
+                        b.pmask |= 1ull << (sn - c.k);
+                        brmap[b.rmap0 + (size_t)(sn - c.k)] = (uint32_t)(e - c.k);
+                    }
+                }
+                const bool copies = Op::kDecodes && !recover && r.nout > 0;
+                const uint64_t step = (uint64_t)sec_bs_span() * (bs_lanes / 64);
+                std::vector<int> held;  // row groups with a held row
+                for (int g = 0; g < sec_bs_groups(sh); ++g)
+                    if ((b.pmask >> (g * NR)) & ((1ull << NR) - 1ull))
+                        held.push_back(g);
+                auto &bt = btiles[sh];
+                for (uint64_t t0 = 0; t0 < c.B; t0 += 8 * step)
+                    for (size_t gi = 0; gi < held.size(); ++gi)
+                        for (uint64_t t = t0; t < c.B && t < t0 + 8 * step; t += step)
+                            bt.push_back(sec::Tile{(uint32_t)bdescs.size(), (uint32_t)t, (uint32_t)(held[gi] * NR),
+                                                   gi == 0 && copies ? 1u : 0u});
+                bdescs.push_back(b);
+                continue;
+            }
             // (a chunk with no row and nothing to copy has no work)
             if (r.ns + r.nr > 0 || (Op::kDecodes && !recover && r.nout > 0))
                 add_work(bins, tail, (uint32_t)(i - c0), c.B, valid, (int)(r.ns + r.nr), c.k, true, false,
@@ -2097,6 +2225,18 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         if (Op::kDecodes) {
             sp.off_srow = img.put(srow.data(), srow.size() * 4);
             sp.off_mrow = img.put(mrow.data(), mrow.size() * 4);
+        }
+        if (!bdescs.empty()) {
+            std::vector<sec::Tile> bt;
+            for (auto &kv : btiles) {
+                sp.cbs.push_back({kv.first, {(uint32_t)bt.size(), (uint32_t)kv.second.size()}});
+                bt.insert(bt.end(), kv.second.begin(), kv.second.end());
+            }
+            sp.off_bdesc = img.put(bdescs.data(), bdescs.size() * sizeof(sec::CbsDesc));
+            sp.off_btiles = img.put(bt.data(), bt.size() * sizeof(sec::Tile));
+            sp.off_bsoff = img.put(bsoff.data(), bsoff.size() * 8);
+            sp.off_bsavail = img.put(bsavail.data(), bsavail.size() * 4);
+            sp.off_brmap = img.put(brmap.data(), brmap.size() * 4);
         }
         if (Op::kTargets) {
             sp.nmsgs = (uint32_t)msgs.size();
@@ -2134,11 +2274,21 @@ int launch_row_sub(sec_ctx *ctx, const SubPlan &sp, bool host, const uint8_t *bl
     const uint32_t *tabs = st.tabs.buf.as<uint32_t>();
     uint32_t *flags = st.flags.as<uint32_t>();
     const typename Op::Slots sl = Op::slots(plan.meta, sp, flags);
-    const bool work = !sp.groups.empty() || sp.ntail || !sp.sha_runs.empty();
+    const bool work = !sp.groups.empty() || sp.ntail || !sp.sha_runs.empty() || !sp.cbs.empty();
     const bool timed = Op::kChecks ? work : !host;
     hipEvent_t t0 = nullptr;
     if (timed)
         RC(timing_begin(ctx, &t0, s));
+    // the chunks of the bit-sliced check, one launch per shape, into the same flag words
+    for (const auto &b : sp.cbs) {
+        const sec::CbsSlots bsl{plan.meta.as<uint64_t>(sp.off_bsoff), plan.meta.as<uint32_t>(sp.off_bsavail),
+                                plan.meta.as<uint32_t>(sp.off_brmap), flags};
+        int e = sec_launch_check_bs(b.first, ctx->opt.lanes(O_BS_LANES), blocks, out,
+                                    plan.meta.as<sec::CbsDesc>(sp.off_bdesc),
+                                    plan.meta.as<sec::Tile>(sp.off_btiles) + b.second.first, b.second.second, bsl, s);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_check_bs_kernel");
+    }
     for (const Group &g : sp.groups) {
         int e = sec_launch_rows(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
                                 g.mfma);
@@ -2351,6 +2501,10 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
         RC(build_row_plan<Op>(ctx, chunks, nchunks, a, L, host));
         plan.key.swap(key.bytes);
         plan.valid = true;
+    }
+    if (Op::kChecks && !Op::kTargets) {  // sec_ctx_check_methods
+        ctx->chk_bs_chunks += plan.nsyn;
+        ctx->chk_direct_chunks += plan.ndirect;
     }
     if (Op::kChecks) {
         // every call starts from clean flag words (0xFFFFFFFF: no position yet, row agrees), whatever
@@ -4183,6 +4337,18 @@ int sec_repair_check_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t n
                                          digests, results, row_bad, column, flags});
 }
 
+int sec_check_method(int k, int m, const int32_t *sharenums, int n, uint64_t B, const uint64_t *block_avail,
+                     int64_t padlen, int *method)
+{
+    if (!method || padlen < 0)
+        return SEC_EINVAL;
+    RC(check_blocks(k, m, sharenums, n, nullptr, 0, false));
+    if (B >= (1ull << 31))
+        return SEC_ESIZE;
+    *method = check_bs_shape(k, m, sharenums, n, B, block_avail, (uint64_t)padlen) >= 0 ? 1 : 0;
+    return SEC_OK;
+}
+
 int sec_check_locate(int k, int m, const int32_t *sharenums, int n, const uint8_t *column, int32_t *culprit)
 {
     RC(check_blocks(k, m, sharenums, k, sharenums ? sharenums + k : nullptr, n - k, true));
@@ -4273,6 +4439,17 @@ int sec_ctx_decode_methods(sec_ctx *ctx, int64_t *fused, int64_t *pair, int64_t 
         *two_kernel = ctx->syn_chunks - ctx->fused_chunks;
     if (direct)
         *direct = ctx->direct_chunks;
+    return SEC_OK;
+}
+
+int sec_ctx_check_methods(sec_ctx *ctx, int64_t *bitsliced, int64_t *direct)
+{
+    if (!ctx)
+        return SEC_EINVAL;
+    if (bitsliced)
+        *bitsliced = ctx->chk_bs_chunks;
+    if (direct)
+        *direct = ctx->chk_direct_chunks;
     return SEC_OK;
 }
 

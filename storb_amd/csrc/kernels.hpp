@@ -204,6 +204,29 @@ struct SolveDesc {
     uint32_t recover;  // 1: recovered row t at out_off + t * B (else row l at out_off + l * B)
 };
 
+// One chunk of a bit-sliced check (kernels_bs.hip sec_check_bs_kernel; 40 B): all k data blocks are
+// held and are the basis, so check row r is zfec's own parity row.  Block j of the chunk (data
+// j < k, parity row r at j = k + r) is at blocks + off[slot0 + j] with avail[slot0 + j] readable
+// bytes (parity rows: when their bit in pmask is set); rmap[rmap0 + r] is parity row r's check-row
+// index, its flag word flags[flag0 + 1 + that] (ChkDesc::flag0: sec_check_final reads them).
+struct CbsDesc {
+    uint64_t out_off;  // decode + check: the chunk in `out`, the data blocks copied there (tile flag)
+    uint64_t pmask;    // bit r: parity row r held (m - k <= 64)
+    uint32_t B;
+    uint32_t last;     // bytes of output row k-1 (B - padlen): its stores stop there
+    uint32_t slot0;
+    uint32_t flag0;
+    uint32_t rmap0;
+    uint32_t pad;
+};
+
+struct CbsSlots {
+    const uint64_t *off;
+    const uint32_t *avail;
+    const uint32_t *rmap;
+    uint32_t *flags;
+};
+
 // Syndromes are stored bit-sliced (a lane's 8 planes where its 32 bytes would be), at the
 // lanes' unclamped positions: rows of whole 2048-position wave spans.
 constexpr uint64_t kSynSpan = 2048;
@@ -276,6 +299,11 @@ int sec_launch_syndrome_bs_pair(int shape, const uint8_t *blocks, uint8_t *out, 
 // the syndromes stay in registers
 int sec_launch_decode_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::SynDesc *descs,
                          const sec::Tile *t, uint32_t ntiles, sec::SynSlots sl, void *stream);
+// Bit-sliced check (and the copy half of a decode + check that lost nothing) of chunks whose basis
+// is their k data blocks: tiles as phase 1's (r0 = the row group's first parity row, one tile per
+// span and row group with a held row; ntail bit 0 = this tile also copies the data blocks to `out`)
+int sec_launch_check_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::CbsDesc *descs,
+                        const sec::Tile *t, uint32_t ntiles, sec::CbsSlots sl, void *stream);
 // The shapes with the two-wave phase-1 kernel (zfec(64,96): both 16-row parity groups)
 int sec_syn_pair(int shape);
 // Phase 2: the lost data rows of row group r0 / sec_solve_rows(shape) of each tile's chunk

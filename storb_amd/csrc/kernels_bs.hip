@@ -850,6 +850,208 @@ __global__ __launch_bounds__(128) void sec_syndrome_bs_pair_kernel(
         syn_span<K, M, NR, NR, D>(blocks, out, syn, d, sl, tl.t0, copies, lring);
 }
 
+// ---- check: the held parity rows of a chunk against the encode of its k data blocks ----------
+// A check whose basis is the chunk's k data blocks predicts zfec's own parity rows, so it is phase 1
+// with nothing lost and another ending: the items, their loaders (register ring for k <= 16, the
+// global_load_lds rank ring for k >= 32, block k-1 alone honouring its avail) and the rows'
+// accumulation are phase 1's; a held parity row, once loaded and transposed, is XORed UNSCALED into
+// its accumulators, which then hold the planes of predicted ^ stored: a byte is nonzero exactly where
+// the two differ.  The ending is check_main's (kernels.hip): the planes ORed, and a lane whose
+// planes are all zero goes on without a store; otherwise the planes are transposed back, the first
+// nonzero byte of the lane's 32 found, its true position (the lane's clamped piece address + its
+// index) goes into the chunk's flag word by atomicMin and the row's flag word is cleared (plain
+// store), in ChkDesc::flag0's layout, so sec_check_final runs unchanged after it.  One pass over
+// n B for the one-group shapes; zfec(64,96) runs each 16-row group with a held row as a tile of its
+// own (the plan interleaves runs of 8 tiles of each group, so the second read of a span's data
+// comes from the same XCD's L2).  With `copies` the tile also stores the data blocks to the chunk's
+// output rows (a decode + check that lost nothing), row k-1 stopping at `last`.
+
+// parity row R0 + r, loaded and transposed in x: compare and report
+template <int NR, int R0, int r>
+__device__ __forceinline__ void chk_compare(const u32 (&acc)[NR * 8], const u32 (&x)[8], const SynCtx &c,
+                                            const u32 *rmap, u32 *flags)
+{
+    u32 y[8], any = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        y[i] = acc[r * 8 + i] ^ x[i];
+        any |= y[i];
+    }
+    if (any == 0)
+        return;
+    transpose8(y);
+    const u64 a0 = y[0] | (u64)y[1] << 32, a1 = y[2] | (u64)y[3] << 32;
+    const u64 b0 = y[4] | (u64)y[5] << 32, b1 = y[6] | (u64)y[7] << 32;
+    // the piece at pa lies at or before the one at pb, and where they overlap they hold the same
+    // bytes: the first nonzero byte of the first nonzero piece is the lane's first
+    u32 at;
+    if (a0 | a1)
+        at = c.pa + (a0 ? (u32)__builtin_ctzll(a0) >> 3 : 8u + ((u32)__builtin_ctzll(a1) >> 3));
+    else
+        at = c.pb + (b0 ? (u32)__builtin_ctzll(b0) >> 3 : 8u + ((u32)__builtin_ctzll(b1) >> 3));
+    atomicMin(flags, at);
+    flags[1 + rmap[R0 + r]] = 0u;
+}
+
+// Item J once its 8 dwords are in x: a data block (copy to its output row, bit-sliced rows of the
+// held parity rows) or a held parity row (compared)
+template <int K, int M, int R0, int NR, int J>
+__device__ __forceinline__ void chk_process(u32 (&acc)[NR * 8], u32 (&x)[8], const SynCtx &c, u8 *orow0, u32 B,
+                                            u32 last, bool copies, const u32 *rmap, u32 *flags)
+{
+    if constexpr (J < K) {
+        if (copies) {
+            u8 *o = orow0 + (u64)J * B;
+            if constexpr (J == K - 1) {
+                st16_clamped(o, c.pa, last, x[0], x[1], x[2], x[3]);
+                st16_clamped(o, c.pb, last, x[4], x[5], x[6], x[7]);
+            } else {
+                st16(o + c.pa, x[0], x[1], x[2], x[3]);
+                st16(o + c.pb, x[4], x[5], x[6], x[7]);
+            }
+        }
+        transpose8(x);
+        u32 lo[16], hi[16];
+        subsets(x[0], x[1], x[2], x[3], lo);
+        subsets(x[4], x[5], x[6], x[7], hi);
+        syn_rows<K, M, R0, J>(std::make_integer_sequence<int, NR>{}, acc, lo, hi, c.pmask);  // held rows only
+    } else {
+        transpose8(x);
+        chk_compare<NR, R0, J - K>(acc, x, c, rmap, flags);
+    }
+}
+
+template <int K, int M, int R0, int NR, int D, int J>
+__device__ __forceinline__ void chk_item(u32 (&acc)[NR * 8], u32 (&ring)[D][8], const SynCtx &c, u8 *orow0, u32 B,
+                                         u32 last, bool copies, const u32 *rmap, u32 *flags)
+{
+    constexpr int NI = K + NR;
+    const bool here = item_present<K, NR, R0>(c, J);
+    u32 x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        x[i] = ring[J % D][i];
+    if constexpr (J + D < NI)
+        if (item_present<K, NR, R0>(c, J + D))
+            load_syn_item<K, NR, R0, J + D>(ring[J % D], c);
+    if (!here)
+        return;
+    chk_process<K, M, R0, NR, J>(acc, x, c, orow0, B, last, copies, rmap, flags);
+}
+
+template <int K, int M, int R0, int NR, int D, int... Js>
+__device__ __forceinline__ void chk_items(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], u32 (&ring)[D][8],
+                                          const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies, const u32 *rmap,
+                                          u32 *flags)
+{
+    (chk_item<K, M, R0, NR, D, Js>(acc, ring, c, orow0, B, last, copies, rmap, flags), ...);
+}
+
+// k >= 32: the items through phase 1's rank ring (syn_item_rank)
+template <int K, int M, int R0, int NR, int D, int J, class Ring>
+__device__ __forceinline__ void chk_item_rank(u32 (&acc)[NR * 8], Ring &ring, u32 w, u32 (&xs)[8], const SynCtx &c,
+                                              const RankRing &rr, u32 &p, u8 *orow0, u32 B, u32 last, bool copies,
+                                              const u32 *rmap, u32 *flags)
+{
+    if (!item_present<K, NR, R0>(c, J))
+        return;
+    u32 x[8];
+    if constexpr (J == K - 1) {
+        wait_vm<2 * D>();  // the ring's 2 D loads in flight are all younger than block K-1's
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            x[i] = xs[i];
+    } else {
+        wait_vm<2 * (D - 1)>();  // rank p has landed
+        const u32 slot = p % D;
+        const u32x4 a = ring.v[w][slot][0][threadIdx.x & 63], b = ring.v[w][slot][1][threadIdx.x & 63];
+        x[0] = a.x;
+        x[1] = a.y;
+        x[2] = a.z;
+        x[3] = a.w;
+        x[4] = b.x;
+        x[5] = b.y;
+        x[6] = b.z;
+        x[7] = b.w;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot is read before it is refilled
+        rank_issue(ring, w, rr, c, p + D, slot);
+        ++p;
+    }
+    chk_process<K, M, R0, NR, J>(acc, x, c, orow0, B, last, copies, rmap, flags);
+}
+
+template <int K, int M, int R0, int NR, int D, class Ring, int... Js>
+__device__ __forceinline__ void chk_items_rank(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], Ring &ring,
+                                               u32 w, const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies,
+                                               const u32 *rmap, u32 *flags)
+{
+    u32 xs[8];
+    load_syn_item<K, NR, R0, K - 1>(xs, c);
+    asm volatile("" ::: "memory");  // block K-1's loads are issued before (older than) every ring load
+    const RankRing rr = rank_ring<K, NR, R0>(ring, w, c);
+#pragma unroll
+    for (u32 r = 0; r < (u32)D; ++r)
+        rank_issue(ring, w, rr, c, r, r);
+    u32 p = 0;
+    (chk_item_rank<K, M, R0, NR, D, Js>(acc, ring, w, xs, c, rr, p, orow0, B, last, copies, rmap, flags), ...);
+}
+
+template <int K, int M, int R0, int NR, int D, class Ring>
+__device__ __forceinline__ void chk_span(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CbsDesc &d,
+                                         const sec::CbsSlots &sl, u32 s, bool copies, Ring &lring)
+{
+    const u32 B = d.B;
+    const u32 lane = (threadIdx.x & 63) * 16;
+    const uint64_t all = K >= 64 ? ~0ull : (1ull << K) - 1ull;  // every data block is held
+    SynCtx c{blocks,  sl.off,   sl.avail, nullptr, d.slot0, min(s + lane, B - 16), min(s + 1024 + lane, B - 16),
+             s + lane, s + 1024 + lane, all, d.pmask, 0};
+    u32 acc[NR * 8];
+#pragma unroll
+    for (int i = 0; i < NR * 8; ++i)
+        acc[i] = 0;
+    const u32 *rmap = sl.rmap + d.rmap0;
+    u32 *flags = sl.flags + d.flag0;
+    if constexpr (K >= 32) {
+        constexpr int DL = SEC_FUSED_LDS_RING;
+        const u32 w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        chk_items_rank<K, M, R0, NR, DL>(std::make_integer_sequence<int, K + NR>{}, acc, lring, w, c, out + d.out_off,
+                                         B, d.last, copies, rmap, flags);
+    } else {
+        u32 ring[D][8];
+        load_syn_first<K, NR, R0>(std::make_integer_sequence<int, D>{}, ring, c);
+        chk_items<K, M, R0, NR, D>(std::make_integer_sequence<int, K + NR>{}, acc, ring, c, out + d.out_off, B,
+                                   d.last, copies, rmap, flags);
+    }
+}
+
+template <int K, int M, int NR, int D>
+__global__ __launch_bounds__(256) void sec_check_bs_kernel(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                           const sec::CbsDesc *__restrict__ descs,
+                                                           const sec::Tile *__restrict__ tiles,
+                                                           const sec::CbsSlots sl)
+{
+    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::CbsDesc d = descs[tl.chunk];
+    const u32 s = tl.t0 + (threadIdx.x >> 6) * kSpan;
+    if (s >= d.B)
+        return;
+    const bool copies = tl.ntail & 1;  // the chunk's first row group with a held row copies the data blocks
+    __shared__ Phase1Lds<K> lring;     // one ring for both row-group variants
+    if constexpr (M - K <= NR) {
+        chk_span<K, M, 0, NR, D>(blocks, out, d, sl, s, copies, lring);
+    } else {
+        static_assert(M - K == 2 * NR, "two row groups");
+        if (tl.r0 == 0)
+            chk_span<K, M, 0, NR, D>(blocks, out, d, sl, s, copies, lring);
+        else
+            chk_span<K, M, NR, NR, D>(blocks, out, d, sl, s, copies, lring);
+    }
+}
+
+// (The two-wave pair form of sec_syndrome_bs_pair_kernel, both groups of a zfec(64,96) span in one
+// workgroup, measured slower here on three cases of four and is archived:
+// tools/archive/kernels_bs_check_pair.diff.)
+
 // ---- decode, phase 2: lost row l = z_l * XOR_{r in S} c[r][l] * (w_r s_r) ----------------------
 struct SolveCtx {
     const u8 *syn;  // the chunk's syndrome rows
@@ -1386,6 +1588,38 @@ int sec_launch_syndrome_bs(int shape, int lanes, const uint8_t *blocks, uint8_t 
     case 3: return launch_syn<32, 48, 16, SEC_SYN_RING>(lanes, blocks, out, syn, descs, t, ntiles, sl, s);
     case 4: return launch_syn<64, 96, 16, SEC_SYN_RING>(lanes, blocks, out, syn, descs, t, ntiles, sl, s);
     case 5: return launch_syn<8, 11, 3, 4>(lanes, blocks, out, syn, descs, t, ntiles, sl, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+namespace {
+template <int K, int M, int NR, int D>
+hipError_t launch_chk(int lanes, const u8 *blocks, u8 *out, const sec::CbsDesc *d, const sec::Tile *t, u32 nt,
+                      sec::CbsSlots sl, hipStream_t s)
+{
+    void *a = nullptr, *b = nullptr;
+    sec_next_launch_events(&a, &b);
+    hipExtLaunchKernelGGL((sec_check_bs_kernel<K, M, NR, D>), dim3(nt), dim3(lanes), 0, s, (hipEvent_t)a,
+                          (hipEvent_t)b, 0, blocks, out, d, t, sl);
+    return hipGetLastError();
+}
+}  // namespace
+
+int sec_launch_check_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::CbsDesc *descs,
+                        const sec::Tile *t, uint32_t ntiles, sec::CbsSlots sl, void *stream)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    if (lanes < 64 || lanes > 256 || lanes % 64)
+        return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    switch (shape) {  // ring depths as phase 1's (sec_launch_syndrome_bs)
+    case 0: return launch_chk<10, 14, 4, 5>(lanes, blocks, out, descs, t, ntiles, sl, s);
+    case 1: return launch_chk<8, 12, 4, 4>(lanes, blocks, out, descs, t, ntiles, sl, s);
+    case 2: return launch_chk<16, 24, 8, 10>(lanes, blocks, out, descs, t, ntiles, sl, s);
+    case 3: return launch_chk<32, 48, 16, SEC_SYN_RING>(lanes, blocks, out, descs, t, ntiles, sl, s);
+    case 4: return launch_chk<64, 96, 16, SEC_SYN_RING>(lanes, blocks, out, descs, t, ntiles, sl, s);
+    case 5: return launch_chk<8, 11, 3, 4>(lanes, blocks, out, descs, t, ntiles, sl, s);
     default: return hipErrorInvalidValue;
     }
 }

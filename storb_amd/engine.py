@@ -543,6 +543,13 @@ class Engine:
                                                     ctypes.byref(d)))
         return f.value, p.value, t.value, d.value
 
+    def check_methods(self) -> tuple[int, int]:
+        """(bit-sliced, direct): chunks with at least one check row that check and decode + check
+        calls have checked so far, by kernel (option ``SEC_CHECK_BS``)."""
+        b, d = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.lib.sec_ctx_check_methods(self._ctx, ctypes.byref(b), ctypes.byref(d)))
+        return b.value, d.value
+
     _SCRATCH_CAP = 256 << 20  # largest result staged in the reusable pinned scratch
 
     def _out_buffer(self, nbytes: int) -> np.ndarray:

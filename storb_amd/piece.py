@@ -936,8 +936,10 @@ def decode_chunks_checked(encoded_chunks: typing.Sequence[EncodedChunk], *,
     What "trustworthy" means: corruption confined to at most n - k of a chunk's n held pieces is
     always detected, and a chunk with exactly k pieces is not checked at all; more than n - k
     pieces altered together can form another code word, which only the recorded piece ids
-    exclude.  ``devices=`` / ``EngineGroup`` splitting and a streaming variant are not provided:
-    one device, one call."""
+    exclude.  ``devices=`` / ``EngineGroup`` splitting is not provided: one device, one call; the
+    streaming form is ``reconstruct_data_stream_checked``.  With every piece of a chunk held,
+    ``choose_blocks`` picks the k data pieces (every present primary first, for every shape), so
+    the fused call may take the one-pass bit-sliced check kernel (option ``SEC_CHECK_BS``)."""
     chunks = list(encoded_chunks)
     out: list[ChunkCheck] = []
     held: list[list[Piece]] = []
@@ -1064,7 +1066,8 @@ def reconstruct_data_checked(pieces: list[Piece], chunks: list[EncodedChunk]) ->
     ``ValueError("Not enough pieces to reconstruct chunk N")`` as ``reconstruct_data`` does, before
     any decode, and ``PieceCheckError`` (carrying ``.checks``) when some chunk is neither
     consistent nor located; otherwise returns the bytes, all trustworthy in
-    ``decode_chunks_checked``'s sense, and the checks.  One device, no streaming variant."""
+    ``decode_chunks_checked``'s sense, and the checks.  One device, one call: objects too large
+    for that stream through ``reconstruct_data_stream_checked``."""
     by_chunk: dict[int, list[Piece]] = {}
     for p in pieces:
         by_chunk.setdefault(p.chunk_idx, []).append(p)
@@ -1144,6 +1147,71 @@ def reconstruct_data_stream(pieces: list[Piece], chunks: list[EncodedChunk], *,
     wins = _windows(chunks, wb, lambda c: max(c.original_chunk_size, 1))
     for outs, err in _pipeline(wins, _decode_window, (by_chunk,), _group(devices)):
         yield from outs
+        if err is not None:
+            raise err
+
+
+def _decode_checked_window(window: list, by_chunk: dict):
+    """Worker side of reconstruct_data_stream_checked: (per-chunk ``(bytes, ChunkCheck)``, error)
+    for one window.  The window's chunks up to the first one without enough pieces go through one
+    ``decode_chunks_checked`` (one fused GPU call, then the locate rounds and the second decode of
+    the located chunks, all confined to this window); that chunk's error is returned, to be raised
+    in order."""
+    good, err = [], None
+    for chunk in window:
+        relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
+        if len(relevant) < chunk.k:
+            err = ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
+            break
+        chunk.pieces = relevant
+        good.append(chunk)
+    if not good:
+        return [], err
+    try:
+        data, checks = decode_chunks_checked(good)
+    except Exception as e:  # noqa: BLE001 - a precondition or device failure: nothing of the window is trusted
+        return [], e
+    view, at, pairs = memoryview(data), 0, []
+    for chunk, ck in zip(good, checks):
+        n = chunk.k * len(chunk.pieces[0].data) - chunk.padlen
+        pairs.append((bytes(view[at:at + n]), ck))
+        at += n
+    return pairs, err
+
+
+def reconstruct_data_stream_checked(pieces: list[Piece], chunks: list[EncodedChunk], *,
+                                    window_bytes: int | None = None) -> Iterator[tuple[bytes, ChunkCheck]]:
+    """``reconstruct_data_checked``'s contract, delivered as ``reconstruct_data_stream`` delivers:
+    yield ``(bytes, ChunkCheck)`` chunk by chunk, in order.
+
+    Chunks go in windows of about `window_bytes` (default STREAM_WINDOW_BYTES) of output.  Each
+    window is one ``decode_chunks_checked`` on the stream worker (one fused GPU call over every
+    piece handed over, then the locate rounds and the second decode of located chunks, confined to
+    that window), and window w+1 runs while the caller consumes window w.  With every piece of a
+    chunk held, ``choose_blocks`` picks its k data pieces (every present primary is taken first,
+    for every shape), so the check rows are zfec's own parity rows and the fused call may take the
+    one-pass bit-sliced check kernel (``Engine.check_methods``, option ``SEC_CHECK_BS``).
+
+    A yielded chunk's bytes are trustworthy in ``decode_chunks_checked``'s sense: its check is
+    ``consistent or located``.  Errors are raised when the stream reaches the chunk, after every
+    earlier chunk has been yielded: ``ValueError("Not enough pieces to reconstruct chunk N")``, and
+    ``PieceCheckError`` (``.checks``: the checks of the chunks seen so far, that chunk's last) for
+    a chunk that is neither consistent nor located.  Closing the generator early cancels the
+    windows not yet started.  One device: ``devices=`` is not provided, as for the whole check
+    family."""
+    by_chunk: dict[int, list[Piece]] = {}
+    for p in pieces:
+        by_chunk.setdefault(p.chunk_idx, []).append(p)
+    wb = STREAM_WINDOW_BYTES if window_bytes is None else window_bytes
+    wins = _windows(chunks, wb, lambda c: max(c.original_chunk_size, 1))
+    seen: list[ChunkCheck] = []
+    for pairs, err in _pipeline(wins, _decode_checked_window, (by_chunk,), None):
+        for data, ck in pairs:
+            seen.append(ck)
+            if not (ck.consistent or ck.located):
+                raise PieceCheckError(
+                    f"Held pieces disagree and no corrupt piece could be named in chunk {ck.chunk_idx}", list(seen))
+            yield data, ck
         if err is not None:
             raise err
 
