@@ -281,6 +281,8 @@ struct Group {
     int mfma = 0;              // bin kind.  Encode: 3 = sec_encode_bs_kernel of shape `rows`, row group U;
                                // decode: the small-batch variant's batch (dec_small_kb), or 0
 };
+// launches of the bit-sliced decode and check kernels: (key, (first, count)) in their tile array
+using KeyedLaunches = std::vector<std::pair<int, std::pair<uint32_t, uint32_t>>>;
 
 // One launch unit: all chunks (device mode) or one slab of chunks (host mode).
 struct SubPlan {
@@ -308,7 +310,7 @@ struct SubPlan {
     size_t off_cdesc = 0;                  // the chunks' ChkDesc (sec_check_final)
     // bit-sliced checks (sec_check_bs_kernel): launches as (shape, (first, count)) in their tiles;
     // their descriptors, tiles and per-block addresses, avails and parity-row -> check-row maps
-    std::vector<std::pair<int, std::pair<uint32_t, uint32_t>>> cbs;
+    KeyedLaunches cbs;
     size_t off_bdesc = 0, off_btiles = 0, off_bsoff = 0, off_bsavail = 0, off_brmap = 0;
     // host mode's slab output: the results at 0, then row_bad and column, then the stored rows
     // (targets or decoded bytes), then the digests (dig_off)
@@ -318,7 +320,7 @@ struct SubPlan {
     // syndrome decodes (decode): phase 1 launches (bit-sliced syndromes) and phase 2 launches
     // (the Cauchy solve), one each per shape
     // (shape, (first, count)) in tiles; synf: the fused kernel (both phases in one wave)
-    std::vector<std::pair<int, std::pair<uint32_t, uint32_t>>> syn1, syn2, synf;
+    KeyedLaunches syn1, syn2, synf;
     size_t off_sdesc = 0, off_stiles = 0, off_ssoff = 0, off_ssavail = 0, off_vdesc = 0, off_vtiles = 0,
            off_masks = 0, off_ftiles = 0;
     uint64_t syn_bytes = 0;  // syndrome scratch of this unit
@@ -636,6 +638,30 @@ void flatten(const Bins &bins, std::vector<Group> &groups, std::vector<sec::Tile
             std::copy(g.begin(), g.end(), tiles.begin() + first);
         }
     }
+}
+
+// One chunk's tiles for a bit-sliced kernel that runs each row group as a tile of its own, in runs
+// of 8 positions per group: workgroup b runs on XCD b % 8, so one XCD's L2 serves a span's second
+// read.  `copy_first`: the first group's tiles carry ntail bit 0 (they copy the chunk's blocks).
+void add_group_run_tiles(std::vector<sec::Tile> &tiles, uint32_t desc_index, uint64_t B, uint64_t step,
+                         const std::vector<int> &groups, int rows_per_group, bool copy_first)
+{
+    for (uint64_t t0 = 0; t0 < B; t0 += 8 * step)
+        for (int g : groups)
+            for (uint64_t t = t0; t < std::min(B, t0 + 8 * step); t += step)
+                tiles.push_back(sec::Tile{desc_index, (uint32_t)t, (uint32_t)(g * rows_per_group),
+                                          copy_first && g == groups[0] ? 1u : 0u});
+}
+
+// The tiles of every key, in key order, as one array; `launches` gets (key, (first, count)) in it.
+std::vector<sec::Tile> flatten_keyed(const std::map<int, std::vector<sec::Tile>> &by_key, KeyedLaunches &launches)
+{
+    std::vector<sec::Tile> tiles;
+    for (auto &kv : by_key) {
+        launches.push_back({kv.first, {(uint32_t)tiles.size(), (uint32_t)kv.second.size()}});
+        tiles.insert(tiles.end(), kv.second.begin(), kv.second.end());
+    }
+    return tiles;
 }
 
 // A plan's launch units as chunk ranges: all chunks (device mode), or (host mode) contiguous
@@ -1630,12 +1656,7 @@ int build_decode_plan(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks
                     for (uint64_t t = 0; t < c.B; t += sec_bs_span())
                         st2.push_back(sec::Tile{si, (uint32_t)t, 0u, copies ? 1u : 0u});
                 } else {
-                    auto &st = stiles[sh];
-                    for (uint64_t t0 = 0; t0 < c.B; t0 += 8 * step)  // runs of 8 positions per group: one XCD
-                        for (int g : gs)
-                            for (uint64_t t = t0; t < std::min<uint64_t>(c.B, t0 + 8 * step); t += step)
-                                st.push_back(
-                                    sec::Tile{si, (uint32_t)t, (uint32_t)(g * NR), copies && g == gs[0] ? 1u : 0u});
+                    add_group_run_tiles(stiles[sh], si, c.B, step, gs, NR, copies);
                 }
                 // phase 2: the groups of lost rows, their tiles interleaved as phase 1's
                 sec::SolveDesc vd{};
@@ -1660,11 +1681,7 @@ int build_decode_plan(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks
                 for (int g = 0; g * NR2 < k; ++g)
                     if ((lost >> (g * NR2)) & ((NR2 >= 64 ? ~0ull : (1ull << NR2) - 1)))
                         gl.push_back(g);
-                auto &vt = vtiles[sh];
-                for (uint64_t t0 = 0; t0 < c.B; t0 += 8 * step)
-                    for (int g : gl)
-                        for (uint64_t t = t0; t < std::min<uint64_t>(c.B, t0 + 8 * step); t += step)
-                            vt.push_back(sec::Tile{vi, (uint32_t)t, (uint32_t)(g * NR2), 0u});
+                add_group_run_tiles(vtiles[sh], vi, c.B, step, gl, NR2, false);
             } else if (nout > 0 && !(nocopy && e_of[i] == 0)) {
                 add_work(bins, tail, (uint32_t)(i - c0), c.B, valid, (int)e_of[i], c.k, true, false,
                          recover || nocopy ? dec_small_kb(c.k) : 0);
@@ -1690,21 +1707,10 @@ int build_decode_plan(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks
                 if (kv.first >= kSolveLds && big(kv.second, vB))
                     xcd_order(kv.second);
         }
-        std::vector<sec::Tile> tiles, stl, vtl;
+        std::vector<sec::Tile> tiles;
         flatten(bins, sp.groups, tiles, true);
-        for (auto &kv : stiles) {
-            sp.syn1.push_back({kv.first, {(uint32_t)stl.size(), (uint32_t)kv.second.size()}});
-            stl.insert(stl.end(), kv.second.begin(), kv.second.end());
-        }
-        for (auto &kv : vtiles) {
-            sp.syn2.push_back({kv.first, {(uint32_t)vtl.size(), (uint32_t)kv.second.size()}});
-            vtl.insert(vtl.end(), kv.second.begin(), kv.second.end());
-        }
-        std::vector<sec::Tile> ftl;
-        for (auto &kv : ftiles) {
-            sp.synf.push_back({kv.first, {(uint32_t)ftl.size(), (uint32_t)kv.second.size()}});
-            ftl.insert(ftl.end(), kv.second.begin(), kv.second.end());
-        }
+        const std::vector<sec::Tile> stl = flatten_keyed(stiles, sp.syn1), vtl = flatten_keyed(vtiles, sp.syn2),
+                                     ftl = flatten_keyed(ftiles, sp.synf);
         sp.off_ftiles = img.put(ftl.data(), ftl.size() * sizeof(sec::Tile));
         sp.off_sdesc = img.put(sdescs.data(), sdescs.size() * sizeof(sec::SynDesc));
         sp.off_stiles = img.put(stl.data(), stl.size() * sizeof(sec::Tile));
@@ -2195,12 +2201,7 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
                 for (int g = 0; g < sec_bs_groups(sh); ++g)
                     if ((b.pmask >> (g * NR)) & ((1ull << NR) - 1ull))
                         held.push_back(g);
-                auto &bt = btiles[sh];
-                for (uint64_t t0 = 0; t0 < c.B; t0 += 8 * step)
-                    for (size_t gi = 0; gi < held.size(); ++gi)
-                        for (uint64_t t = t0; t < c.B && t < t0 + 8 * step; t += step)
-                            bt.push_back(sec::Tile{(uint32_t)bdescs.size(), (uint32_t)t, (uint32_t)(held[gi] * NR),
-                                                   gi == 0 && copies ? 1u : 0u});
+                add_group_run_tiles(btiles[sh], (uint32_t)bdescs.size(), c.B, step, held, NR, copies);
                 bdescs.push_back(b);
                 continue;
             }
@@ -2227,11 +2228,7 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             sp.off_mrow = img.put(mrow.data(), mrow.size() * 4);
         }
         if (!bdescs.empty()) {
-            std::vector<sec::Tile> bt;
-            for (auto &kv : btiles) {
-                sp.cbs.push_back({kv.first, {(uint32_t)bt.size(), (uint32_t)kv.second.size()}});
-                bt.insert(bt.end(), kv.second.begin(), kv.second.end());
-            }
+            const std::vector<sec::Tile> bt = flatten_keyed(btiles, sp.cbs);
             sp.off_bdesc = img.put(bdescs.data(), bdescs.size() * sizeof(sec::CbsDesc));
             sp.off_btiles = img.put(bt.data(), bt.size() * sizeof(sec::Tile));
             sp.off_bsoff = img.put(bsoff.data(), bsoff.size() * 8);

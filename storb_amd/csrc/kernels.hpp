@@ -300,8 +300,9 @@ int sec_launch_syndrome_bs_pair(int shape, const uint8_t *blocks, uint8_t *out, 
 int sec_launch_decode_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::SynDesc *descs,
                          const sec::Tile *t, uint32_t ntiles, sec::SynSlots sl, void *stream);
 // Bit-sliced check (and the copy half of a decode + check that lost nothing) of chunks whose basis
-// is their k data blocks: tiles as phase 1's (r0 = the row group's first parity row, one tile per
-// span and row group with a held row; ntail bit 0 = this tile also copies the data blocks to `out`)
+// is their k data blocks (phase 1's item pipeline with a comparing ending): tiles as phase 1's
+// (r0 = the row group's first parity row, one tile per span and row group with a held row; ntail
+// bit 0 = this tile also copies the data blocks to `out`)
 int sec_launch_check_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::CbsDesc *descs,
                         const sec::Tile *t, uint32_t ntiles, sec::CbsSlots sl, void *stream);
 // The shapes with the two-wave phase-1 kernel (zfec(64,96): both 16-row parity groups)

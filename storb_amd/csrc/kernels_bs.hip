@@ -105,10 +105,10 @@ __device__ __forceinline__ void transpose8(u32 (&x)[8])
     swap_bits<1, 0x55555555u>(x[6], x[7]);
 }
 
-// Block loads: nontemporal (streaming) in the one-group encode kernels, where every byte is read
-// once; cached elsewhere (the zfec(64,96) encode and the decode phases, whose blocks a second
-// wave or group reads again from L2; measured (64,96) +5-8 % cached, (16,24) -5 %, (32,48) even;
-// r02_bs_ab.jsonl run 4).
+// Block loads: nontemporal (streaming) in every kernel that loads through here today: the encodes,
+// the zfec(64,96) pair encode included (it reads each block once), and phase 1's register ring.
+// NT = false (cached) served the interleaved (64,96) encode, whose blocks a second group read again
+// from L2 (measured (64,96) +5-8 % cached, (16,24) -5 %, (32,48) even; r02_bs_ab.jsonl run 4).
 template <bool NT>
 __device__ __forceinline__ u32x4 ld16(const u8 *p)
 {
@@ -580,11 +580,54 @@ __device__ __forceinline__ void syn_rows(std::integer_sequence<int, Rs...>, u32 
     (coef_planes_skip<K, M, R0 + Rs, J, R0 + Rs>(&acc[Rs * 8], lo, hi, pmask), ...);
 }
 
+// The endings of phase 1: what becomes of present parity row R0 + r once it is loaded and
+// transposed in x, when acc[r * 8 ..] holds the present data blocks' contribution to that row.
+// One item pipeline (below) serves the two-kernel decode, the fused decode and the check; they
+// differ in this alone.  An ending is a type with one static member, row<NR, R0, r>(acc, x, c,
+// state...); its state (the arguments after c) travels through the pipeline as a pack of plain
+// values.  (Held in an object passed by reference instead, the same code compiled to other
+// instruction streams: scalar register allocation in the check, 1-12 instructions in phase 1.)
+
+// two kernels: the scaled syndrome to row *q of the chunk's syndrome scratch, for sec_solve_bs_kernel
+struct SynToScratch {
+    template <int NR, int R0, int r>
+    static __device__ __forceinline__ void row(u32 (&acc)[NR * 8], const u32 (&x)[8], const SynCtx &c, u8 *syn,
+                                               u32 *q)  // *q: the syndrome row of the next present parity row
+    {
+        u32 y[8];  // syndrome = the row's planes ^ the present blocks' contribution, * w
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            y[i] = acc[r * 8 + i] ^ x[i];
+        scale_planes(y, c.wmask[*q]);
+        u8 *o = syn + (u64)*q * c.stride;
+        st16(o + c.ua, y[0], y[1], y[2], y[3]);
+        st16(o + c.ub, y[4], y[5], y[6], y[7]);
+        ++*q;
+    }
+};
+
+// fused decode: the scaled syndrome stays in the row's accumulators for the solve in the same wave
+struct SynKept {
+    template <int NR, int R0, int r>
+    static __device__ __forceinline__ void row(u32 (&acc)[NR * 8], const u32 (&x)[8], const SynCtx &c, u32 *q)
+    {
+        u32 y[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            y[i] = acc[r * 8 + i] ^ x[i];
+        scale_planes(y, c.wmask[*q]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            acc[r * 8 + i] = y[i];
+        ++*q;
+    }
+};
+
 // Item J's processing once its 8 dwords are in x: a present data block (copy to its output
-// row, bit-sliced rows of the present parity rows) or a present parity row (its syndrome).
-template <int K, int M, int R0, int NR, bool FUSED, int J>
-__device__ __forceinline__ void syn_process(u32 (&acc)[NR * 8], u32 (&x)[8], const SynCtx &c, u8 *orow0, u32 B,
-                                            u32 last, bool copies, u8 *syn, u32 &q)
+// row, bit-sliced rows of the present parity rows) or a present parity row (the ending's).
+template <int K, int M, int R0, int NR, class End, int J, class... S>
+__device__ __forceinline__ void p1_process(u32 (&acc)[NR * 8], u32 (&x)[8], const SynCtx &c, u8 *orow0, u32 B,
+                                           u32 last, bool copies, S... st)
 {
     if constexpr (J < K) {
         if (copies) {  // the present primary's bytes to its output row (row K-1 clamps to `last`)
@@ -602,30 +645,15 @@ __device__ __forceinline__ void syn_process(u32 (&acc)[NR * 8], u32 (&x)[8], con
         subsets(x[0], x[1], x[2], x[3], lo);
         subsets(x[4], x[5], x[6], x[7], hi);
         syn_rows<K, M, R0, J>(std::make_integer_sequence<int, NR>{}, acc, lo, hi, c.pmask);  // present rows only
-    } else {  // parity row R0 + r: syndrome = its planes ^ the present blocks' contribution, * w
-        constexpr int r = J - K;
+    } else {
         transpose8(x);
-        u32 y[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            y[i] = acc[r * 8 + i] ^ x[i];
-        scale_planes(y, c.wmask[q]);
-        if constexpr (FUSED) {  // kept for the solve in the same wave
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                acc[r * 8 + i] = y[i];
-        } else {
-            u8 *o = syn + (u64)q * c.stride;
-            st16(o + c.ua, y[0], y[1], y[2], y[3]);
-            st16(o + c.ub, y[4], y[5], y[6], y[7]);
-        }
-        ++q;
+        End::template row<NR, R0, J - K>(acc, x, c, st...);
     }
 }
 
-template <int K, int M, int R0, int NR, int D, bool FUSED, int J>
-__device__ __forceinline__ void syn_item(u32 (&acc)[NR * 8], u32 (&ring)[D][8], const SynCtx &c, u8 *orow0, u32 B,
-                                         u32 last, bool copies, u8 *syn, u32 &q)
+template <int K, int M, int R0, int NR, int D, class End, int J, class... S>
+__device__ __forceinline__ void p1_item(u32 (&acc)[NR * 8], u32 (&ring)[D][8], const SynCtx &c, u8 *orow0, u32 B,
+                                        u32 last, bool copies, S... st)
 {
     constexpr int NI = K + NR;
     const bool here = item_present<K, NR, R0>(c, J);
@@ -638,14 +666,14 @@ __device__ __forceinline__ void syn_item(u32 (&acc)[NR * 8], u32 (&ring)[D][8], 
             load_syn_item<K, NR, R0, J + D>(ring[J % D], c);
     if (!here)
         return;
-    syn_process<K, M, R0, NR, FUSED, J>(acc, x, c, orow0, B, last, copies, syn, q);
+    p1_process<K, M, R0, NR, End, J>(acc, x, c, orow0, B, last, copies, st...);
 }
 
-template <int K, int M, int R0, int NR, int D, bool FUSED, int... Js>
-__device__ __forceinline__ void syn_items(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], u32 (&ring)[D][8],
-                                          const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies, u8 *syn, u32 &q)
+template <int K, int M, int R0, int NR, int D, class End, class... S, int... Js>
+__device__ __forceinline__ void p1_items(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], u32 (&ring)[D][8],
+                                         const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies, S... st)
 {
-    (syn_item<K, M, R0, NR, D, FUSED, Js>(acc, ring, c, orow0, B, last, copies, syn, q), ...);
+    (p1_item<K, M, R0, NR, D, End, Js>(acc, ring, c, orow0, B, last, copies, st...), ...);
 }
 
 // ---- phase 1's loads for k >= 32: an LDS ring filled by global_load_lds (no VGPRs) ----------
@@ -721,10 +749,10 @@ __device__ __forceinline__ void rank_issue(Ring &ring, u32 w, const RankRing &rr
                                      (__attribute__((address_space(3))) void *)&ring.v[w][slot][1][0], 16, 0, 0);
 }
 
-template <int K, int M, int R0, int NR, int D, bool FUSED, int J, class Ring>
-__device__ __forceinline__ void syn_item_rank(u32 (&acc)[NR * 8], Ring &ring, u32 w, u32 (&xs)[8], const SynCtx &c,
-                                              const RankRing &rr, u32 &p, u8 *orow0, u32 B, u32 last, bool copies,
-                                              u8 *syn, u32 &q)
+template <int K, int M, int R0, int NR, int D, class End, int J, class Ring, class... S>
+__device__ __forceinline__ void p1_item_rank(u32 (&acc)[NR * 8], Ring &ring, u32 w, u32 (&xs)[8], const SynCtx &c,
+                                             const RankRing &rr, u32 &p, u8 *orow0, u32 B, u32 last, bool copies,
+                                             S... st)
 {
     if (!item_present<K, NR, R0>(c, J))
         return;
@@ -750,16 +778,16 @@ __device__ __forceinline__ void syn_item_rank(u32 (&acc)[NR * 8], Ring &ring, u3
         rank_issue(ring, w, rr, c, p + D, slot);
         ++p;
     }
-    syn_process<K, M, R0, NR, FUSED, J>(acc, x, c, orow0, B, last, copies, syn, q);
+    p1_process<K, M, R0, NR, End, J>(acc, x, c, orow0, B, last, copies, st...);
 }
 
-template <int K, int M, int R0, int NR, int D, bool FUSED, class Ring, int... Js>
-__device__ __forceinline__ void syn_items_rank(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], Ring &ring,
-                                               u32 w, const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies,
-                                               u8 *syn, u32 &q)
+template <int K, int M, int R0, int NR, int D, class End, class Ring, class... S, int... Js>
+__device__ __forceinline__ void p1_items_rank(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], Ring &ring,
+                                              u32 w, const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies,
+                                              S... st)
 {
     u32 xs[8];
-    if (item_present<K, NR, R0>(c, K - 1))
+    if (item_present<K, NR, R0>(c, K - 1))  // (the check's dmask is a constant: no branch there)
         load_syn_item<K, NR, R0, K - 1>(xs, c);
     asm volatile("" ::: "memory");  // block K-1's loads are issued before (older than) every ring load
     const RankRing rr = rank_ring<K, NR, R0>(ring, w, c);
@@ -767,9 +795,16 @@ __device__ __forceinline__ void syn_items_rank(std::integer_sequence<int, Js...>
     for (u32 r = 0; r < (u32)D; ++r)
         rank_issue(ring, w, rr, c, r, r);
     u32 p = 0;
-    (syn_item_rank<K, M, R0, NR, D, FUSED, Js>(acc, ring, w, xs, c, rr, p, orow0, B, last, copies, syn, q), ...);
+    (p1_item_rank<K, M, R0, NR, D, End, Js>(acc, ring, w, xs, c, rr, p, orow0, B, last, copies, st...), ...);
 }
 
+// One wave's span of the two-kernel phase 1, rows [R0, R0 + NR): the context from the lane's
+// positions, zeroed accumulators, then the items through the LDS rank ring (k >= 32) or a register
+// ring of D.  chk_span and fused_span open the same way and keep their own copy of these lines, as
+// the three one-wave kernels keep their own row-group dispatch: moved into a shared helper (the
+// context, or the ring choice, or the dispatch as a lambda taking R0) the same code compiled to
+// other instruction streams, the ring choice taking sec_syndrome_bs_kernel<8,12,4,4> and <8,11,3,4>
+// from 95 / 85 to 228 VGPRs (profiles/bs_phase1_refactor_kres.txt).
 template <int K, int M, int R0, int NR, int D, class Ring>
 __device__ __forceinline__ void syn_span(const u8 *__restrict__ blocks, u8 *__restrict__ out, u8 *__restrict__ syn,
                                          const sec::SynDesc &d, const sec::SynSlots &sl, u32 s, bool copies,
@@ -788,13 +823,13 @@ __device__ __forceinline__ void syn_span(const u8 *__restrict__ blocks, u8 *__re
     if constexpr (K >= 32) {
         constexpr int DL = SEC_FUSED_LDS_RING;
         const u32 w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        syn_items_rank<K, M, R0, NR, DL, false>(std::make_integer_sequence<int, K + NR>{}, acc, lring, w, c,
-                                                out + d.out_off, B, d.last, copies, syn + d.syn_off, q);
+        p1_items_rank<K, M, R0, NR, DL, SynToScratch>(std::make_integer_sequence<int, K + NR>{}, acc, lring, w, c,
+                                                      out + d.out_off, B, d.last, copies, syn + d.syn_off, &q);
     } else {
         u32 ring[D][8];
         load_syn_first<K, NR, R0>(std::make_integer_sequence<int, D>{}, ring, c);
-        syn_items<K, M, R0, NR, D, false>(std::make_integer_sequence<int, K + NR>{}, acc, ring, c, out + d.out_off,
-                                          B, d.last, copies, syn + d.syn_off, q);
+        p1_items<K, M, R0, NR, D, SynToScratch>(std::make_integer_sequence<int, K + NR>{}, acc, ring, c,
+                                                out + d.out_off, B, d.last, copies, syn + d.syn_off, &q);
     }
 }
 
@@ -852,10 +887,10 @@ __global__ __launch_bounds__(128) void sec_syndrome_bs_pair_kernel(
 
 // ---- check: the held parity rows of a chunk against the encode of its k data blocks ----------
 // A check whose basis is the chunk's k data blocks predicts zfec's own parity rows, so it is phase 1
-// with nothing lost and another ending: the items, their loaders (register ring for k <= 16, the
-// global_load_lds rank ring for k >= 32, block k-1 alone honouring its avail) and the rows'
-// accumulation are phase 1's; a held parity row, once loaded and transposed, is XORed UNSCALED into
-// its accumulators, which then hold the planes of predicted ^ stored: a byte is nonzero exactly where
+// with nothing lost (dmask the constant "every block", so block k-1 is loaded without a branch) and
+// another ending, ChkCompare: p1_span runs it as it runs the decodes (the same items, loaders and
+// rows' accumulation), and a held parity row, once loaded and transposed, is XORed UNSCALED into its
+// accumulators, which then hold the planes of predicted ^ stored: a byte is nonzero exactly where
 // the two differ.  The ending is check_main's (kernels.hip): the planes ORed, and a lane whose
 // planes are all zero goes on without a store; otherwise the planes are transposed back, the first
 // nonzero byte of the lane's 32 found, its true position (the lane's clamped piece address + its
@@ -867,144 +902,44 @@ __global__ __launch_bounds__(128) void sec_syndrome_bs_pair_kernel(
 // output rows (a decode + check that lost nothing), row k-1 stopping at `last`.
 
 // parity row R0 + r, loaded and transposed in x: compare and report
-template <int NR, int R0, int r>
-__device__ __forceinline__ void chk_compare(const u32 (&acc)[NR * 8], const u32 (&x)[8], const SynCtx &c,
-                                            const u32 *rmap, u32 *flags)
-{
-    u32 y[8], any = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        y[i] = acc[r * 8 + i] ^ x[i];
-        any |= y[i];
-    }
-    if (any == 0)
-        return;
-    transpose8(y);
-    const u64 a0 = y[0] | (u64)y[1] << 32, a1 = y[2] | (u64)y[3] << 32;
-    const u64 b0 = y[4] | (u64)y[5] << 32, b1 = y[6] | (u64)y[7] << 32;
-    // the piece at pa lies at or before the one at pb, and where they overlap they hold the same
-    // bytes: the first nonzero byte of the first nonzero piece is the lane's first
-    u32 at;
-    if (a0 | a1)
-        at = c.pa + (a0 ? (u32)__builtin_ctzll(a0) >> 3 : 8u + ((u32)__builtin_ctzll(a1) >> 3));
-    else
-        at = c.pb + (b0 ? (u32)__builtin_ctzll(b0) >> 3 : 8u + ((u32)__builtin_ctzll(b1) >> 3));
-    atomicMin(flags, at);
-    flags[1 + rmap[R0 + r]] = 0u;
-}
-
-// Item J once its 8 dwords are in x: a data block (copy to its output row, bit-sliced rows of the
-// held parity rows) or a held parity row (compared)
-template <int K, int M, int R0, int NR, int J>
-__device__ __forceinline__ void chk_process(u32 (&acc)[NR * 8], u32 (&x)[8], const SynCtx &c, u8 *orow0, u32 B,
-                                            u32 last, bool copies, const u32 *rmap, u32 *flags)
-{
-    if constexpr (J < K) {
-        if (copies) {
-            u8 *o = orow0 + (u64)J * B;
-            if constexpr (J == K - 1) {
-                st16_clamped(o, c.pa, last, x[0], x[1], x[2], x[3]);
-                st16_clamped(o, c.pb, last, x[4], x[5], x[6], x[7]);
-            } else {
-                st16(o + c.pa, x[0], x[1], x[2], x[3]);
-                st16(o + c.pb, x[4], x[5], x[6], x[7]);
-            }
-        }
-        transpose8(x);
-        u32 lo[16], hi[16];
-        subsets(x[0], x[1], x[2], x[3], lo);
-        subsets(x[4], x[5], x[6], x[7], hi);
-        syn_rows<K, M, R0, J>(std::make_integer_sequence<int, NR>{}, acc, lo, hi, c.pmask);  // held rows only
-    } else {
-        transpose8(x);
-        chk_compare<NR, R0, J - K>(acc, x, c, rmap, flags);
-    }
-}
-
-template <int K, int M, int R0, int NR, int D, int J>
-__device__ __forceinline__ void chk_item(u32 (&acc)[NR * 8], u32 (&ring)[D][8], const SynCtx &c, u8 *orow0, u32 B,
-                                         u32 last, bool copies, const u32 *rmap, u32 *flags)
-{
-    constexpr int NI = K + NR;
-    const bool here = item_present<K, NR, R0>(c, J);
-    u32 x[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-        x[i] = ring[J % D][i];
-    if constexpr (J + D < NI)
-        if (item_present<K, NR, R0>(c, J + D))
-            load_syn_item<K, NR, R0, J + D>(ring[J % D], c);
-    if (!here)
-        return;
-    chk_process<K, M, R0, NR, J>(acc, x, c, orow0, B, last, copies, rmap, flags);
-}
-
-template <int K, int M, int R0, int NR, int D, int... Js>
-__device__ __forceinline__ void chk_items(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], u32 (&ring)[D][8],
-                                          const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies, const u32 *rmap,
-                                          u32 *flags)
-{
-    (chk_item<K, M, R0, NR, D, Js>(acc, ring, c, orow0, B, last, copies, rmap, flags), ...);
-}
-
-// k >= 32: the items through phase 1's rank ring (syn_item_rank)
-template <int K, int M, int R0, int NR, int D, int J, class Ring>
-__device__ __forceinline__ void chk_item_rank(u32 (&acc)[NR * 8], Ring &ring, u32 w, u32 (&xs)[8], const SynCtx &c,
-                                              const RankRing &rr, u32 &p, u8 *orow0, u32 B, u32 last, bool copies,
-                                              const u32 *rmap, u32 *flags)
-{
-    if (!item_present<K, NR, R0>(c, J))
-        return;
-    u32 x[8];
-    if constexpr (J == K - 1) {
-        wait_vm<2 * D>();  // the ring's 2 D loads in flight are all younger than block K-1's
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            x[i] = xs[i];
-    } else {
-        wait_vm<2 * (D - 1)>();  // rank p has landed
-        const u32 slot = p % D;
-        const u32x4 a = ring.v[w][slot][0][threadIdx.x & 63], b = ring.v[w][slot][1][threadIdx.x & 63];
-        x[0] = a.x;
-        x[1] = a.y;
-        x[2] = a.z;
-        x[3] = a.w;
-        x[4] = b.x;
-        x[5] = b.y;
-        x[6] = b.z;
-        x[7] = b.w;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot is read before it is refilled
-        rank_issue(ring, w, rr, c, p + D, slot);
-        ++p;
-    }
-    chk_process<K, M, R0, NR, J>(acc, x, c, orow0, B, last, copies, rmap, flags);
-}
-
-template <int K, int M, int R0, int NR, int D, class Ring, int... Js>
-__device__ __forceinline__ void chk_items_rank(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], Ring &ring,
-                                               u32 w, const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies,
+struct ChkCompare {
+    template <int NR, int R0, int r>
+    static __device__ __forceinline__ void row(const u32 (&acc)[NR * 8], const u32 (&x)[8], const SynCtx &c,
                                                const u32 *rmap, u32 *flags)
-{
-    u32 xs[8];
-    load_syn_item<K, NR, R0, K - 1>(xs, c);
-    asm volatile("" ::: "memory");  // block K-1's loads are issued before (older than) every ring load
-    const RankRing rr = rank_ring<K, NR, R0>(ring, w, c);
+    {
+        u32 y[8], any = 0;
 #pragma unroll
-    for (u32 r = 0; r < (u32)D; ++r)
-        rank_issue(ring, w, rr, c, r, r);
-    u32 p = 0;
-    (chk_item_rank<K, M, R0, NR, D, Js>(acc, ring, w, xs, c, rr, p, orow0, B, last, copies, rmap, flags), ...);
-}
+        for (int i = 0; i < 8; ++i) {
+            y[i] = acc[r * 8 + i] ^ x[i];
+            any |= y[i];
+        }
+        if (any == 0)
+            return;
+        transpose8(y);
+        const u64 a0 = y[0] | (u64)y[1] << 32, a1 = y[2] | (u64)y[3] << 32;
+        const u64 b0 = y[4] | (u64)y[5] << 32, b1 = y[6] | (u64)y[7] << 32;
+        // the piece at pa lies at or before the one at pb, and where they overlap they hold the same
+        // bytes: the first nonzero byte of the first nonzero piece is the lane's first
+        u32 at;
+        if (a0 | a1)
+            at = c.pa + (a0 ? (u32)__builtin_ctzll(a0) >> 3 : 8u + ((u32)__builtin_ctzll(a1) >> 3));
+        else
+            at = c.pb + (b0 ? (u32)__builtin_ctzll(b0) >> 3 : 8u + ((u32)__builtin_ctzll(b1) >> 3));
+        atomicMin(flags, at);
+        flags[1 + rmap[R0 + r]] = 0u;
+    }
+};
 
+// (the span as syn_span; dmask a constant, so p1_items_rank loads block K-1 without a branch)
 template <int K, int M, int R0, int NR, int D, class Ring>
 __device__ __forceinline__ void chk_span(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CbsDesc &d,
                                          const sec::CbsSlots &sl, u32 s, bool copies, Ring &lring)
 {
+    constexpr uint64_t all = K >= 64 ? ~0ull : (1ull << K) - 1ull;  // every data block is held
     const u32 B = d.B;
     const u32 lane = (threadIdx.x & 63) * 16;
-    const uint64_t all = K >= 64 ? ~0ull : (1ull << K) - 1ull;  // every data block is held
-    SynCtx c{blocks,  sl.off,   sl.avail, nullptr, d.slot0, min(s + lane, B - 16), min(s + 1024 + lane, B - 16),
-             s + lane, s + 1024 + lane, all, d.pmask, 0};
+    SynCtx c{blocks,   sl.off,          sl.avail, nullptr, d.slot0, min(s + lane, B - 16), min(s + 1024 + lane, B - 16),
+             s + lane, s + 1024 + lane, all,      d.pmask, 0};
     u32 acc[NR * 8];
 #pragma unroll
     for (int i = 0; i < NR * 8; ++i)
@@ -1014,13 +949,13 @@ __device__ __forceinline__ void chk_span(const u8 *__restrict__ blocks, u8 *__re
     if constexpr (K >= 32) {
         constexpr int DL = SEC_FUSED_LDS_RING;
         const u32 w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        chk_items_rank<K, M, R0, NR, DL>(std::make_integer_sequence<int, K + NR>{}, acc, lring, w, c, out + d.out_off,
-                                         B, d.last, copies, rmap, flags);
+        p1_items_rank<K, M, R0, NR, DL, ChkCompare>(std::make_integer_sequence<int, K + NR>{}, acc, lring, w, c,
+                                                    out + d.out_off, B, d.last, copies, rmap, flags);
     } else {
         u32 ring[D][8];
         load_syn_first<K, NR, R0>(std::make_integer_sequence<int, D>{}, ring, c);
-        chk_items<K, M, R0, NR, D>(std::make_integer_sequence<int, K + NR>{}, acc, ring, c, out + d.out_off, B,
-                                   d.last, copies, rmap, flags);
+        p1_items<K, M, R0, NR, D, ChkCompare>(std::make_integer_sequence<int, K + NR>{}, acc, ring, c,
+                                              out + d.out_off, B, d.last, copies, rmap, flags);
     }
 }
 
@@ -1334,13 +1269,13 @@ __device__ __forceinline__ void fused_span(const u8 *__restrict__ blocks, u8 *__
     if constexpr (K >= 32) {
         constexpr int DL = SEC_FUSED_LDS_RING;
         const u32 w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        syn_items_rank<K, M, RP0, NRP, DL, true>(std::make_integer_sequence<int, K + NRP>{}, acc, lring, w, c,
-                                                 out + d.out_off, B, d.last, copies, nullptr, q);
+        p1_items_rank<K, M, RP0, NRP, DL, SynKept>(std::make_integer_sequence<int, K + NRP>{}, acc, lring, w, c,
+                                                   out + d.out_off, B, d.last, copies, &q);
     } else {
         u32 ring[D][8];
         load_syn_first<K, NRP, RP0>(std::make_integer_sequence<int, D>{}, ring, c);
-        syn_items<K, M, RP0, NRP, D, true>(std::make_integer_sequence<int, K + NRP>{}, acc, ring, c,
-                                           out + d.out_off, B, d.last, copies, nullptr, q);
+        p1_items<K, M, RP0, NRP, D, SynKept>(std::make_integer_sequence<int, K + NRP>{}, acc, ring, c,
+                                             out + d.out_off, B, d.last, copies, &q);
     }
     const uint64_t lost = ~d.dmask & (K >= 64 ? ~0ull : (1ull << K) - 1ull);
     const OutCtx o{out + d.out_off, sl.masks + d.zq0, lost, B, d.last, d.flags & 2u ? 1u : 0u, c.pa, c.pb};
@@ -1371,33 +1306,72 @@ __global__ __launch_bounds__(256) void sec_decode_bs_kernel(const u8 *__restrict
     }
 }
 
-template <int K, int M, int R0, int NR, int D>
-hipError_t launch_bs(int lanes, const u8 *in, u8 *par, const sec::EncDesc *d, const sec::Tile *t, u32 nt,
-                     hipStream_t s)
+// ---- launches ----------------------------------------------------------------------------------
+// Build knobs (A/B: tools/sweep.py).
+#ifndef SEC_BS_PAIR_RING
+#define SEC_BS_PAIR_RING 2  // own blocks in flight per wave of the pair encode
+#endif
+#ifndef SEC_SYN_RING
+#define SEC_SYN_RING 4  // phase 1 and the check, the 16-row groups' ring
+#endif
+// phase 2: the syndromes' 8-dword items, D of them in flight (4 against 2: +2-7 % on the two-kernel
+// decodes, r03_syn_ab.jsonl)
+#ifndef SEC_SOLVE_RING
+#define SEC_SOLVE_RING 4
+#endif
+// fused kernel ring: 6 against 4 +0-4 % (r03_syn_ab.jsonl)
+#ifndef SEC_FUSED_RING
+#define SEC_FUSED_RING 6
+#endif
+
+// The shapes, and what every launcher below instantiates for them: (k, m, parity rows per launch or
+// tile group), the encode's ring depth and phase 1's (the check's too).  Encode depths from the
+// register budget (8 NR accumulators + 8 D ring dwords per lane) and A/Bs: zfec(16,24) keeps 10 of
+// its 16 blocks in flight (182 VGPRs; +2-8 % over 4 on 1 and 16 MiB chunks), C4 5 (10: -2 %), the
+// 16-row groups 2 (the two-group shape runs the pair kernel: SEC_BS_PAIR_RING).  Phase 1's as the
+// encode's (the kernels' register budgets are alike), the 16-row groups' SEC_SYN_RING.
+struct BsShape {
+    int k, m, nr, enc_ring, p1_ring;
+    constexpr int groups() const { return (m - k + nr - 1) / nr; }
+    // phase-2 rows per group: (10,14) 10, (8,*) 8, (16,24) 16; k >= 32 in groups of 8 rows (groups
+    // of 16, four waves per span: -9 % at 32 lost, +4-6 % on random 16-30 % losses,
+    // profiles/r06_syn_ab_rank_pipe_snr16.jsonl)
+    constexpr int solve_nr() const { return k <= 16 ? k : 8; }
+    constexpr int solve_ring() const { return SEC_SOLVE_RING < m - k ? SEC_SOLVE_RING : m - k; }  // at most every row
+    // solve rows per group in the one-wave kernel: 8 (16 cost 282 VGPRs = one wave per SIMD, and a
+    // lone wave leaves the memory pipe idle while it solves: 0.8x the two-kernel path; 8 rows: 224)
+    constexpr int fused_nr() const { return k <= 10 ? k : 8; }
+};
+constexpr BsShape kShapes[] = {{10, 14, 4, 5, 5},  {8, 12, 4, 4, 4}, {16, 24, 8, 10, 10}, {32, 48, 16, 2, SEC_SYN_RING},
+                               {64, 96, 16, SEC_BS_PAIR_RING, SEC_SYN_RING}, {8, 11, 3, 4, 4}};
+constexpr int kNShapes = (int)(sizeof(kShapes) / sizeof(kShapes[0]));
+
+// f(shape as a compile-time constant), or hipErrorInvalidValue for a shape the table lacks
+template <class F, int... Is>
+hipError_t dispatch_shape(int shape, F &&f, std::integer_sequence<int, Is...>)
+{
+    hipError_t e = hipErrorInvalidValue;
+    ((shape == Is ? (void)(e = f(std::integral_constant<int, Is>{})) : void()), ...);
+    return e;
+}
+template <class F>
+hipError_t dispatch_shape(int shape, F &&f)
+{
+    return dispatch_shape(shape, f, std::make_integer_sequence<int, kNShapes>{});
+}
+
+// one launch: kernel timing (sec_ctx_set_timing) rides on the dispatch
+template <class... P>
+hipError_t launch(void (*kern)(P...), u32 nt, int lanes, size_t lds, void *stream, std::common_type_t<P>... args)
 {
     void *a = nullptr, *b = nullptr;
-    sec_next_launch_events(&a, &b);  // kernel timing (sec_ctx_set_timing) rides on the dispatch
-    if constexpr (R0 == -2)
-        hipExtLaunchKernelGGL((sec_encode_bs_pair_kernel<K, M, NR, D>), dim3(nt), dim3(128), 0, s, (hipEvent_t)a,
-                              (hipEvent_t)b, 0, in, par, d, t);
-    else
-        hipExtLaunchKernelGGL((sec_encode_bs_kernel<K, M, R0, NR, D>), dim3(nt), dim3(lanes), 0, s, (hipEvent_t)a,
-                              (hipEvent_t)b, 0, in, par, d, t);
+    sec_next_launch_events(&a, &b);
+    hipExtLaunchKernelGGL(kern, dim3(nt), dim3(lanes), lds, (hipStream_t)stream, (hipEvent_t)a, (hipEvent_t)b, 0,
+                          args...);
     return hipGetLastError();
 }
 
-// Shapes: (k, m, rows per launch).  Ring depths from the register budget (8 NR accumulators
-// + 8 D ring dwords per lane) and A/Bs: zfec(16,24) keeps 10 of its 16 blocks in flight
-// (182 VGPRs; +2-8 % over 4 on 1 and 16 MiB chunks), C4 5 (10: -2 %), the 16-row groups 2;
-// own blocks in flight per wave of the pair kernel
-#ifndef SEC_BS_PAIR_RING
-#define SEC_BS_PAIR_RING 2
-#endif
-struct BsShape {
-    int k, m, nr;
-};
-constexpr BsShape kShapes[] = {{10, 14, 4}, {8, 12, 4}, {16, 24, 8}, {32, 48, 16}, {64, 96, 16}, {8, 11, 3}};
-constexpr int kNShapes = (int)(sizeof(kShapes) / sizeof(kShapes[0]));
+bool lanes_ok(int lanes) { return lanes >= 64 && lanes <= 256 && lanes % 64 == 0; }
 
 }  // namespace
 
@@ -1409,167 +1383,39 @@ int sec_bs_shape(int k, int m, int rows)
     return -1;
 }
 
-int sec_bs_groups(int shape) { return (kShapes[shape].m - kShapes[shape].k + kShapes[shape].nr - 1) / kShapes[shape].nr; }
+int sec_bs_groups(int shape) { return kShapes[shape].groups(); }
 
 int sec_bs_rows(int shape) { return kShapes[shape].nr; }
 
 uint32_t sec_bs_span() { return kSpan; }
 
+int sec_solve_rows(int shape) { return shape >= 0 && shape < kNShapes ? kShapes[shape].solve_nr() : 0; }
+
+int sec_solve_lds(int shape) { return shape == 3 || shape == 4; }  // zfec(32,48), (64,96)
+
+int sec_syn_pair(int shape) { return shape == 4; }  // zfec(64,96)
+
+int sec_syn_shape(int k, int m) { return sec_bs_shape(k, m); }
+
+// group -2: both groups of a span in one two-wave workgroup (sec_encode_bs_pair_kernel, the
+// two-group zfec(64,96), one tile per span); 0: the one-group shapes
 int sec_launch_encode_bs(int shape, int group, int lanes, const uint8_t *in, uint8_t *par, const sec::EncDesc *descs,
                          const sec::Tile *t, uint32_t ntiles, void *stream)
 {
     if (ntiles == 0)
         return hipSuccess;
-    if (lanes < 64 || lanes > 256 || lanes % 64 || shape < 0 || shape >= kNShapes || (group != 0 && group != -2))
+    if (!lanes_ok(lanes) || (group != 0 && group != -2))
         return hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    // group -2: both groups of a span in one two-wave workgroup (sec_encode_bs_pair_kernel, the
-    // two-group zfec(64,96), one tile per span); 0: the one-group shapes
-    if (group == -2)
-        return shape == 4 ? launch_bs<64, 96, -2, 16, SEC_BS_PAIR_RING>(128, in, par, descs, t, ntiles, s)
-                          : hipErrorInvalidValue;
-    switch (shape * 4 + group + 1) {
-    case 1: return launch_bs<10, 14, 0, 4, 5>(lanes, in, par, descs, t, ntiles, s);
-    case 5: return launch_bs<8, 12, 0, 4, 4>(lanes, in, par, descs, t, ntiles, s);
-    case 9: return launch_bs<16, 24, 0, 8, 10>(lanes, in, par, descs, t, ntiles, s);
-    case 13: return launch_bs<32, 48, 0, 16, 2>(lanes, in, par, descs, t, ntiles, s);
-    case 21: return launch_bs<8, 11, 0, 3, 4>(lanes, in, par, descs, t, ntiles, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-namespace {
-template <int K, int M, int NR, int D>
-hipError_t launch_syn(int lanes, const u8 *blocks, u8 *out, u8 *syn, const sec::SynDesc *d, const sec::Tile *t, u32 nt,
-                      sec::SynSlots sl, hipStream_t s)
-{
-    void *a = nullptr, *b = nullptr;
-    sec_next_launch_events(&a, &b);
-    hipExtLaunchKernelGGL((sec_syndrome_bs_kernel<K, M, NR, D>), dim3(nt), dim3(lanes), 0, s, (hipEvent_t)a,
-                          (hipEvent_t)b, 0, blocks, out, syn, d, t, sl);
-    return hipGetLastError();
-}
-
-// phase-2 rows per group: (10,14) 10, (8,*) 8, the rest 16
-// (k >= 32 in groups of 8 rows; groups of 16, four waves per span: -9 % at 32 lost, +4-6 % on
-// random 16-30 % losses, profiles/r06_syn_ab_rank_pipe_snr16.jsonl)
-constexpr int solve_nr(int k) { return k <= 16 ? k : 8; }
-
-template <int K, int M, int D>
-hipError_t launch_solve(int lanes, const u8 *syn, u8 *out, const sec::SolveDesc *d, const sec::Tile *t, u32 nt,
-                        const uint64_t *masks, hipStream_t s)
-{
-    void *a = nullptr, *b = nullptr;
-    sec_next_launch_events(&a, &b);
-    hipExtLaunchKernelGGL((sec_solve_bs_kernel<K, M, solve_nr(K), D>), dim3(nt), dim3(lanes), 0, s, (hipEvent_t)a,
-                          (hipEvent_t)b, 0, syn, out, d, t, masks);
-    return hipGetLastError();
-}
-}  // namespace
-
-int sec_solve_rows(int shape) { return shape >= 0 && shape < kNShapes ? solve_nr(kShapes[shape].k) : 0; }
-
-// Ring depths: the syndromes' 8-dword items, D of them in flight (SEC_SOLVE_RING, build knob;
-// 4 against 2: +2-7 % on the two-kernel decodes, r03_syn_ab.jsonl)
-#ifndef SEC_SOLVE_RING
-#define SEC_SOLVE_RING 4
-#endif
-int sec_launch_solve_bs(int shape, int lanes, const uint8_t *syn, uint8_t *out, const sec::SolveDesc *descs,
-                        const sec::Tile *t, uint32_t ntiles, const uint64_t *masks, void *stream)
-{
-    if (ntiles == 0)
-        return hipSuccess;
-    if (lanes < 64 || lanes > 256 || lanes % 64)
-        return hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    constexpr int R = SEC_SOLVE_RING;
-    switch (shape) {
-    case 0: return launch_solve<10, 14, R < 4 ? R : 4>(lanes, syn, out, descs, t, ntiles, masks, s);
-    case 1: return launch_solve<8, 12, R < 4 ? R : 4>(lanes, syn, out, descs, t, ntiles, masks, s);
-    case 2: return launch_solve<16, 24, R>(lanes, syn, out, descs, t, ntiles, masks, s);
-    case 3: return launch_solve<32, 48, R>(lanes, syn, out, descs, t, ntiles, masks, s);
-    case 4: return launch_solve<64, 96, R>(lanes, syn, out, descs, t, ntiles, masks, s);
-    case 5: return launch_solve<8, 11, R < 3 ? R : 3>(lanes, syn, out, descs, t, ntiles, masks, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-namespace {
-// solve rows per group in the one-wave kernel: 8 (16 cost 282 VGPRs = one wave per SIMD, and a
-// lone wave leaves the memory pipe idle while it solves: 0.8x the two-kernel path; 8 rows: 224)
-constexpr int fused_nr(int k) { return k <= 10 ? k : 8; }
-
-template <int K, int M, int NRP, int D>
-hipError_t launch_fused(int lanes, const u8 *blocks, u8 *out, const sec::SynDesc *d, const sec::Tile *t, u32 nt,
-                        sec::SynSlots sl, hipStream_t s)
-{
-    void *a = nullptr, *b = nullptr;
-    sec_next_launch_events(&a, &b);
-    hipExtLaunchKernelGGL((sec_decode_bs_kernel<K, M, NRP, fused_nr(K), D>), dim3(nt), dim3(lanes), 0, s,
-                          (hipEvent_t)a, (hipEvent_t)b, 0, blocks, out, d, t, sl);
-    return hipGetLastError();
-}
-}  // namespace
-
-// fused kernel ring (SEC_FUSED_RING, build knob): 6 against 4 +0-4 % (r03_syn_ab.jsonl)
-#ifndef SEC_FUSED_RING
-#define SEC_FUSED_RING 6
-#endif
-int sec_launch_decode_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::SynDesc *descs,
-                         const sec::Tile *t, uint32_t ntiles, sec::SynSlots sl, void *stream)
-{
-    if (ntiles == 0)
-        return hipSuccess;
-    if (lanes < 64 || lanes > 256 || lanes % 64)
-        return hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    constexpr int R = SEC_FUSED_RING;
-    switch (shape) {
-    case 0: return launch_fused<10, 14, 4, R>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 1: return launch_fused<8, 12, 4, R>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 2: return launch_fused<16, 24, 8, R>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 3: return launch_fused<32, 48, 16, R>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 4: return launch_fused<64, 96, 16, R>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 5: return launch_fused<8, 11, 3, R>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-int sec_solve_lds(int shape) { return shape == 3 || shape == 4; }  // zfec(32,48), (64,96)
-
-int sec_launch_solve_bs_lds(int shape, int slots, const uint8_t *syn, uint8_t *out, const sec::SolveDesc *descs,
-                            const sec::Tile *t, uint32_t ntiles, const uint64_t *masks, void *stream)
-{
-    if (ntiles == 0)
-        return hipSuccess;
-    if (slots < 1 || slots > 32)
-        return hipErrorInvalidValue;
-    const size_t lds = (size_t)slots * 2048;
-    void *a = nullptr, *b = nullptr;
-    sec_next_launch_events(&a, &b);
-    hipStream_t s = (hipStream_t)stream;
-    switch (shape) {
-    case 3:
-        if (slots > 16)
+    return dispatch_shape(shape, [&](auto i) {
+        constexpr BsShape S = kShapes[decltype(i)::value];
+        if (group != (S.groups() == 2 ? -2 : 0))
             return hipErrorInvalidValue;
-        hipExtLaunchKernelGGL((sec_solve_bs_lds_kernel<32, 48, solve_nr(32)>), dim3(ntiles), dim3(64 * (32 / solve_nr(32))),
-                              lds, s, (hipEvent_t)a, (hipEvent_t)b, 0, syn, out, descs, t, masks);
-        break;
-    case 4:
-        hipExtLaunchKernelGGL((sec_solve_bs_lds_kernel<64, 96, solve_nr(64)>), dim3(ntiles), dim3(64 * (64 / solve_nr(64))),
-                              lds, s, (hipEvent_t)a, (hipEvent_t)b, 0, syn, out, descs, t, masks);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+        if constexpr (S.groups() == 2)
+            return launch(sec_encode_bs_pair_kernel<S.k, S.m, S.nr, S.enc_ring>, ntiles, 128, 0, stream, in, par, descs, t);
+        else
+            return launch(sec_encode_bs_kernel<S.k, S.m, 0, S.nr, S.enc_ring>, ntiles, lanes, 0, stream, in, par, descs, t);
+    });
 }
-
-int sec_syn_pair(int shape) { return shape == 4; }  // zfec(64,96)
-
-#ifndef SEC_SYN_RING
-#define SEC_SYN_RING 4
-#endif
-int sec_syn_shape(int k, int m) { return sec_bs_shape(k, m); }
 
 int sec_launch_syndrome_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, uint8_t *syn,
                            const sec::SynDesc *descs, const sec::Tile *t, uint32_t ntiles, sec::SynSlots sl,
@@ -1577,51 +1423,13 @@ int sec_launch_syndrome_bs(int shape, int lanes, const uint8_t *blocks, uint8_t 
 {
     if (ntiles == 0)
         return hipSuccess;
-    if (lanes < 64 || lanes > 256 || lanes % 64)
+    if (!lanes_ok(lanes))
         return hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    switch (shape) {  // ring depths as the encode's (kernels' register budgets are alike); the
-                      // 16-row groups' SEC_SYN_RING (build knob, A/B)
-    case 0: return launch_syn<10, 14, 4, 5>(lanes, blocks, out, syn, descs, t, ntiles, sl, s);
-    case 1: return launch_syn<8, 12, 4, 4>(lanes, blocks, out, syn, descs, t, ntiles, sl, s);
-    case 2: return launch_syn<16, 24, 8, 10>(lanes, blocks, out, syn, descs, t, ntiles, sl, s);
-    case 3: return launch_syn<32, 48, 16, SEC_SYN_RING>(lanes, blocks, out, syn, descs, t, ntiles, sl, s);
-    case 4: return launch_syn<64, 96, 16, SEC_SYN_RING>(lanes, blocks, out, syn, descs, t, ntiles, sl, s);
-    case 5: return launch_syn<8, 11, 3, 4>(lanes, blocks, out, syn, descs, t, ntiles, sl, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-namespace {
-template <int K, int M, int NR, int D>
-hipError_t launch_chk(int lanes, const u8 *blocks, u8 *out, const sec::CbsDesc *d, const sec::Tile *t, u32 nt,
-                      sec::CbsSlots sl, hipStream_t s)
-{
-    void *a = nullptr, *b = nullptr;
-    sec_next_launch_events(&a, &b);
-    hipExtLaunchKernelGGL((sec_check_bs_kernel<K, M, NR, D>), dim3(nt), dim3(lanes), 0, s, (hipEvent_t)a,
-                          (hipEvent_t)b, 0, blocks, out, d, t, sl);
-    return hipGetLastError();
-}
-}  // namespace
-
-int sec_launch_check_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::CbsDesc *descs,
-                        const sec::Tile *t, uint32_t ntiles, sec::CbsSlots sl, void *stream)
-{
-    if (ntiles == 0)
-        return hipSuccess;
-    if (lanes < 64 || lanes > 256 || lanes % 64)
-        return hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
-    switch (shape) {  // ring depths as phase 1's (sec_launch_syndrome_bs)
-    case 0: return launch_chk<10, 14, 4, 5>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 1: return launch_chk<8, 12, 4, 4>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 2: return launch_chk<16, 24, 8, 10>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 3: return launch_chk<32, 48, 16, SEC_SYN_RING>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 4: return launch_chk<64, 96, 16, SEC_SYN_RING>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    case 5: return launch_chk<8, 11, 3, 4>(lanes, blocks, out, descs, t, ntiles, sl, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_shape(shape, [&](auto i) {
+        constexpr BsShape S = kShapes[decltype(i)::value];
+        constexpr auto kern = sec_syndrome_bs_kernel<S.k, S.m, S.nr, S.p1_ring>;
+        return launch(kern, ntiles, lanes, 0, stream, blocks, out, syn, descs, t, sl);
+    });
 }
 
 int sec_launch_syndrome_bs_pair(int shape, const uint8_t *blocks, uint8_t *out, uint8_t *syn, const sec::SynDesc *descs,
@@ -1629,12 +1437,72 @@ int sec_launch_syndrome_bs_pair(int shape, const uint8_t *blocks, uint8_t *out, 
 {
     if (ntiles == 0)
         return hipSuccess;
-    if (shape != 4)
-        return hipErrorInvalidValue;
-    void *a = nullptr, *b = nullptr;
-    sec_next_launch_events(&a, &b);
-    hipExtLaunchKernelGGL((sec_syndrome_bs_pair_kernel<64, 96, 16, SEC_SYN_RING>), dim3(ntiles), dim3(128), 0,
-                          (hipStream_t)stream, (hipEvent_t)a, (hipEvent_t)b, 0, blocks, out, syn, descs, t, sl);
-    return hipGetLastError();
+    return dispatch_shape(shape, [&](auto i) {
+        constexpr BsShape S = kShapes[decltype(i)::value];
+        if constexpr (S.groups() == 2)
+            return launch(sec_syndrome_bs_pair_kernel<S.k, S.m, S.nr, S.p1_ring>, ntiles, 128, 0, stream, blocks, out,
+                          syn, descs, t, sl);
+        else
+            return hipErrorInvalidValue;
+    });
 }
 
+int sec_launch_solve_bs(int shape, int lanes, const uint8_t *syn, uint8_t *out, const sec::SolveDesc *descs,
+                        const sec::Tile *t, uint32_t ntiles, const uint64_t *masks, void *stream)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    if (!lanes_ok(lanes))
+        return hipErrorInvalidValue;
+    return dispatch_shape(shape, [&](auto i) {
+        constexpr BsShape S = kShapes[decltype(i)::value];
+        return launch(sec_solve_bs_kernel<S.k, S.m, S.solve_nr(), S.solve_ring()>, ntiles, lanes, 0, stream, syn, out,
+                      descs, t, masks);
+    });
+}
+
+// `slots` syndrome rows of 2 KiB in LDS: e rounded up to 8, at most the shape's m - k
+int sec_launch_solve_bs_lds(int shape, int slots, const uint8_t *syn, uint8_t *out, const sec::SolveDesc *descs,
+                            const sec::Tile *t, uint32_t ntiles, const uint64_t *masks, void *stream)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    return dispatch_shape(shape, [&](auto i) {
+        constexpr BsShape S = kShapes[decltype(i)::value];
+        if constexpr (S.k >= 32)  // sec_solve_lds
+            return slots < 1 || slots > S.m - S.k
+                       ? hipErrorInvalidValue
+                       : launch(sec_solve_bs_lds_kernel<S.k, S.m, S.solve_nr()>, ntiles, 64 * (S.k / S.solve_nr()),
+                                (size_t)slots * 2048, stream, syn, out, descs, t, masks);
+        else
+            return hipErrorInvalidValue;
+    });
+}
+
+int sec_launch_decode_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::SynDesc *descs,
+                         const sec::Tile *t, uint32_t ntiles, sec::SynSlots sl, void *stream)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    if (!lanes_ok(lanes))
+        return hipErrorInvalidValue;
+    return dispatch_shape(shape, [&](auto i) {
+        constexpr BsShape S = kShapes[decltype(i)::value];
+        constexpr auto kern = sec_decode_bs_kernel<S.k, S.m, S.nr, S.fused_nr(), SEC_FUSED_RING>;
+        return launch(kern, ntiles, lanes, 0, stream, blocks, out, descs, t, sl);
+    });
+}
+
+int sec_launch_check_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::CbsDesc *descs,
+                        const sec::Tile *t, uint32_t ntiles, sec::CbsSlots sl, void *stream)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    if (!lanes_ok(lanes))
+        return hipErrorInvalidValue;
+    return dispatch_shape(shape, [&](auto i) {
+        constexpr BsShape S = kShapes[decltype(i)::value];
+        constexpr auto kern = sec_check_bs_kernel<S.k, S.m, S.nr, S.p1_ring>;
+        return launch(kern, ntiles, lanes, 0, stream, blocks, out, descs, t, sl);
+    });
+}
