@@ -249,7 +249,11 @@ typedef struct sec_rep_chunk {
  * digests (nullable): 20 bytes per target at digests + 20 (tgt0 + j), the SHA-1 of the repaired
  * piece (storb's piece id), computed by the SHA-1 kernel while the targets are device-resident;
  * digests live where the targets do (device memory, or host memory with SEC_F_HOST).
- * More than 8 targets of a chunk take ceil(ntargets / 8) passes over its sources.
+ * More than 8 targets of a chunk take ceil(ntargets / 8) passes over its sources on the direct
+ * (v_perm) kernels; a chunk whose k sources are its data blocks (every target is then a parity row)
+ * may take the bit-sliced repair kernel instead, one pass per 16-row group that holds a target,
+ * whatever ntargets (sec_repair_method, option "SEC_CHECK_BS"; one call may hold both kinds).  The
+ * bytes written are the same.
  * Aliasing: no target range may overlap a source block or another target of any chunk in the
  * call: workgroups read sources while others write targets, so an overlap gives unspecified
  * bytes.  The library does not check this (sec_decode_batch's rule).
@@ -386,7 +390,10 @@ int sec_decode_check_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t n
  * consistent; with both it launches nothing.  `blocks` or `out` may be NULL: the offsets are then
  * absolute addresses.  Nothing is ever written to the blocks; every call starts from clean state.
  * More than 8 rows (targets + check rows) of a chunk take ceil((ntargets + n - k) / 8) row groups
- * over its basis.
+ * over its basis on the direct (v_perm) kernels; a chunk with a target whose first k entries are
+ * its k data blocks may take the bit-sliced repair kernel instead, one pass per 16-row group with a
+ * target or a check row (sec_repair_method, option "SEC_CHECK_BS"; one call may hold both kinds).
+ * Targets and results are the same.  A chunk with no target always takes the direct kernels.
  * Aliasing: sec_repair_batch's rule (no target range may overlap a block or another target of the
  * call).
  * Flags: none or SEC_F_ASYNC (device pointers); SEC_F_HOST (host pointers) is ALWAYS staged through
@@ -434,7 +441,9 @@ int sec_check_locate(int k, int m, const int32_t *sharenums, int n, const uint8_
  * the data blocks 0 .. k-1 in any order, every entry but data block k-1 is readable to B
  * (block_avail: the chunk's n entries, nullable = all B) and padlen < B (0 for a check); else 0.
  * Eligibility alone: whether an eligible chunk takes that kernel is option "SEC_CHECK_BS" (-1 the
- * measured rule, 0 never, 1 always).
+ * measured rule, 0 never, 1 always).  The same option governs the bit-sliced repair kernel of
+ * sec_repair_batch / sec_repair_check_batch (sec_repair_method), whose measured rule is a rule of
+ * its own.
  * Errors: sec_check_batch's for the same arguments, in its order (SEC_EINVAL also for a NULL
  * method or padlen < 0). */
 int sec_check_method(int k, int m, const int32_t *sharenums, int n, uint64_t B,
@@ -444,6 +453,24 @@ int sec_check_method(int k, int m, const int32_t *sharenums, int n, uint64_t B,
  * the bit-sliced check kernel and to the direct kernels on this context (cumulative; either
  * pointer nullable). */
 int sec_ctx_check_methods(sec_ctx *ctx, int64_t *bitsliced, int64_t *direct);
+
+/* Whether a chunk of sec_repair_batch (n == k) / sec_repair_check_batch is eligible for the
+ * bit-sliced repair kernel (host logic, no device needed): *method = 1 when (k, m) is one of the
+ * bit-sliced shapes (sec_check_method's), B >= 16, the chunk has a target or a check row
+ * (ntargets + n - k >= 1), the first k sharenums are the data blocks 0 .. k-1 in any order (so every
+ * target is a parity row) and every entry but data block k-1 is readable to B (block_avail: the
+ * chunk's n entries, nullable = all B); else 0.
+ * Eligibility alone: whether an eligible chunk takes that kernel is option "SEC_CHECK_BS", and a
+ * chunk with no target never does.
+ * Errors: sec_repair_check_batch's for the same arguments, in its order (SEC_EINVAL also for a NULL
+ * method). */
+int sec_repair_method(int k, int m, const int32_t *sharenums, int n, const int32_t *targets,
+                      int ntargets, uint64_t B, const uint64_t *block_avail, int *method);
+
+/* Chunks with at least one target that sec_repair_batch and sec_repair_check_batch have sent to the
+ * bit-sliced repair kernel and to the direct kernels on this context (cumulative; either pointer
+ * nullable).  sec_ctx_check_methods does not count these calls. */
+int sec_ctx_repair_methods(sec_ctx *ctx, int64_t *bitsliced, int64_t *direct);
 
 /* ---- piece ids: SHA-1 (piece_hash, /root/reference/storb/util/piece.py:54-68) ----
  * A message is `len` bytes at `addr`, of which the first `avail` exist in

@@ -229,7 +229,8 @@ enum Opt {
     O_COPY_THREADS,      // 0 rule, or host copy-pool threads
     O_REGISTER_MIN,      // page-lock pageable host buffers for calls moving >= this many bytes (0: never)
     O_HOST_JOIN,         // 0: the GPU writes every byte of a host reassembly
-    O_CHECK_BS,          // bit-sliced check: -1 rule (check_bs_rule), 0 never, 1 every eligible chunk
+    O_CHECK_BS,          // bit-sliced check: -1 rule (check_bs_rule), 0 never, 1 every eligible chunk;
+                         // the bit-sliced repair too (its -1 rule: repair_bs_rule)
     O_COUNT
 };
 
@@ -309,9 +310,11 @@ struct SubPlan {
     uint32_t nentries = 0;                 // entries of the unit's chunks (operations with compared rows)
     size_t off_cdesc = 0;                  // the chunks' ChkDesc (sec_check_final)
     // bit-sliced checks (sec_check_bs_kernel): launches as (shape, (first, count)) in their tiles;
-    // their descriptors, tiles and per-block addresses, avails and parity-row -> check-row maps
+    // their descriptors, tiles and per-block addresses, avails and parity-row -> check-row maps.
+    // An operation with targets keeps its bit-sliced repairs (sec_repair_bs_kernel) here instead:
+    // RbsDesc at off_bdesc, and the parity-row -> target map
     KeyedLaunches cbs;
-    size_t off_bdesc = 0, off_btiles = 0, off_bsoff = 0, off_bsavail = 0, off_brmap = 0;
+    size_t off_bdesc = 0, off_btiles = 0, off_bsoff = 0, off_bsavail = 0, off_brmap = 0, off_btmap = 0;
     // host mode's slab output: the results at 0, then row_bad and column, then the stored rows
     // (targets or decoded bytes), then the digests (dig_off)
     uint64_t chk_rows = 0, chk_col = 0, pay_off = 0;
@@ -754,6 +757,7 @@ struct sec_ctx {
     int64_t zero_copy_calls = 0, registered_calls = 0, staged_calls = 0;
     int64_t syn_chunks = 0, direct_chunks = 0, fused_chunks = 0;  // decodes by method (sec_ctx_decode_paths)
     int64_t chk_bs_chunks = 0, chk_direct_chunks = 0;  // checked chunks by kernel (sec_ctx_check_methods)
+    int64_t rep_bs_chunks = 0, rep_direct_chunks = 0;  // repaired chunks by kernel (sec_ctx_repair_methods)
 
     hipStream_t stream() const { return ext ? ext : own; }
     hipEvent_t ev()
@@ -1406,6 +1410,63 @@ bool check_bs_rule(const Options &o, int shape, uint64_t B, bool copies)
     }
 }
 
+// Bit-sliced repair (kernels_bs.hip sec_repair_bs_kernel): the shape of its kernel for a chunk of a
+// repair (n == k) or a repair + check whose arguments passed the call's screen, or -1 (the direct
+// kernels).  Eligible when
+//   * (k, m) is one of the bit-sliced shapes, 16 <= B (below it the tail kernel), and the chunk has
+//     a row at all: a target or a check row (nt + n - k >= 1);
+//   * the first k entries are the data blocks 0 .. k-1 in any order.  No target is held, so every
+//     target is then a parity row, and so is every check row: rows of the matrix the kernel holds;
+//   * every entry's avail is one phase 1's loader honours, as check_bs_shape asks: block k-1 may
+//     have any avail, every other entry is readable to B.
+// avail: the chunk's n entries in the caller's order, or NULL (all B).
+int repair_bs_shape(int k, int m, const int32_t *sn, int n, int nt, uint64_t B, const uint64_t *avail)
+{
+    const int sh = sec_bs_shape(k, m);
+    if (sh < 0 || nt + (n - k) < 1 || B < 16 || B > 0xFFFFFFFFull - 8192)
+        return -1;
+    for (int j = 0; j < k; ++j)
+        if (sn[j] >= k)
+            return -1;
+    for (int e = 0; avail && e < n; ++e)
+        if (sn[e] != k - 1 && avail[e] < B)
+            return -1;
+    return sh;
+}
+
+// Whether an eligible chunk with nt >= 1 targets and nr compared rows takes the bit-sliced repair.
+// SEC_CHECK_BS = 0 never, 1 always; the default takes it only where it measured at least 5 % faster
+// than the direct kernels on the same build (rounds differ by up to 3 %, boxes by 1-3 %), by shape,
+// block size, targets and compared rows; every shape, block size (outside the least and greatest
+// measured of the shape) and target count not measured stays direct (tools/bench_repair_bs.py,
+// profiles/repair_bs_rate.json; DESIGN §5 "Repair, bit-sliced").
+bool repair_bs_rule(const Options &o, int shape, uint64_t B, int nt, int nr)
+{
+    if (o[O_CHECK_BS] >= 0)
+        return o[O_CHECK_BS] == 1;
+    // direct ms / bit-sliced ms at the shape's two block sizes (one where one is given); data pieces
+    // the basis, lost pieces parity; "+ check": every surviving piece held (nr = m - k - nt):
+    //   (16,24)  B 64 KiB | 512 KiB: 1 lost 0.84 | 0.91, 2 0.87 | 0.90, 4 0.89 | 0.91, 8 1.11 | 1.13;
+    //            + check 1 lost 1.20 | 1.19, 2 lost 1.15 | 1.14
+    //   (32,48)  B 32 KiB | 2 MiB: 1 lost 0.96 | 0.98, 4 0.89 | 1.05, 16 1.88 | 1.99;
+    //            + check 1 lost 2.00 | 2.17, 2 lost 2.00 | 2.15
+    //   (64,96)  B 16 KiB | 4 MiB: 1 lost 0.76 | 0.90, 8 in one group 1.28 | 1.39, 16 in one group
+    //            2.28 | 2.35, 16 as 8 + 8 1.49 | 1.53, 32 2.38 | 2.50; + check 1 lost 2.50 | 2.72,
+    //            2 lost 2.49 | 2.72.  8 lost stays direct: the rule does not see the groups, and 4 + 4
+    //            (two passes against the direct kernel's one) was not measured
+    //   (10,14)  B 6554: 1 lost 0.79, 2 0.82, 4 0.84; + check 1 lost 1.22, 2 lost 1.26
+    //   (8,12)   B 512 KiB: 4 lost 0.96; + check 1 lost 1.04, 2 lost 1.04: never;  (8,11) not measured
+    const int rows = nt + nr;
+    switch (shape) {
+    case 0: return B == 6554 && rows == 4 && nt <= 2;
+    case 2: return B >= (64u << 10) && B <= (512u << 10) && rows == 8 && (nt <= 2 || nt == 8);
+    case 3: return B >= (32u << 10) && B <= (2u << 20) && rows == 16 && (nt <= 2 || nt == 16);
+    case 4:
+        return B >= (16u << 10) && B <= (4u << 20) && ((rows == 32 && (nt <= 2 || nt == 32)) || (nt == 16 && nr == 0));
+    default: return false;
+    }
+}
+
 // The cache key of a table made from the k blocks idx[0..k) of a (k, m) code
 std::string slots_key(int k, int m, const int *idx)
 {
@@ -2042,7 +2103,23 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             ++plan.ndirect;
         }
     }
-    auto rows_of = [&](int64_t i) {  // -> rows; ns_of[i] = how many of them are stored
+    // repair and repair + check: the chunks with a target that the bit-sliced repair kernel takes,
+    // in the same list (an operation has one kind or the other).  A repair + check chunk with no
+    // target is a plain check and stays with the direct kernels, whatever the option.
+    for (int64_t i = 0; Op::kTargets && i < nchunks; ++i) {
+        const RowChunk c = Op::view(chunks[i]);
+        if (c.nt < 1)
+            continue;
+        const int sh = repair_bs_shape(c.k, c.m, a.sharenums + c.slot0, c.n, c.nt, c.B,
+                                       host || !a.block_avail ? nullptr : a.block_avail + c.slot0);
+        if (sh >= 0 && repair_bs_rule(ctx->opt, sh, c.B, c.nt, c.n - c.k)) {
+            bs_of[(size_t)i] = sh;
+            ++plan.nsyn;
+        } else {
+            ++plan.ndirect;
+        }
+    }
+    auto rows_of =[&](int64_t i) {  // -> rows; ns_of[i] = how many of them are stored
         const RowChunk c = Op::view(chunks[i]);
         const int *idx = &L.idx[L.first[i]];
         rows.clear();
@@ -2058,7 +2135,9 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         return idx;
     };
     auto want = [&](int64_t i, std::string &key) -> size_t {
-        if (bs_of[(size_t)i] >= 0)  // the matrix is in the kernel (and nothing is lost: ns_of stays 0)
+        // the matrix is in the kernel (ns_of stays 0: no row of the chunk goes through the direct
+        // kernels, whose descriptor then has nothing to store)
+        if (bs_of[(size_t)i] >= 0)
             return 0;
         const int *idx = rows_of(i);
         if (rows.empty())
@@ -2093,7 +2172,8 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         std::vector<sec::TailItem> tail;
         std::vector<sec::CbsDesc> bdescs;
         std::vector<uint64_t> bsoff;
-        std::vector<uint32_t> bsavail, brmap;
+        std::vector<uint32_t> bsavail, brmap, btmap;
+        std::vector<sec::RbsDesc> rdescs;              // the bit-sliced repair's, in bdescs' place
         std::map<int, std::vector<sec::Tile>> btiles;  // by shape
         uint64_t nent = 0;
         if (Op::kChecks) {
@@ -2170,6 +2250,43 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             }
             sp.in_bytes += (uint64_t)c.n * c.B;
             sp.out_bytes += nstore;
+            if (Op::kTargets && bs_of[(size_t)i] >= 0) {
+                // the bit-sliced repair: its blocks by number as below, the target rows' indices in
+                // tgt_off, the held parity rows' check-row indices, and one tile per span and row
+                // group with a target or a held row, in the check's runs of 8
+                const int sh = bs_of[(size_t)i], NR = sec_bs_rows(sh);
+                sec::RbsDesc b{};
+                b.B = r.B;
+                b.slot0 = (uint32_t)bsoff.size();
+                b.flag0 = r.flag0;
+                b.rmap0 = (uint32_t)brmap.size();
+                bsoff.resize(bsoff.size() + (size_t)c.m, 0);
+                bsavail.resize(bsavail.size() + (size_t)c.m, 0);
+                brmap.resize(brmap.size() + (size_t)(c.m - c.k), 0);
+                btmap.resize(btmap.size() + (size_t)(c.m - c.k), 0);
+                for (int e = 0; e < c.n; ++e) {
+                    const int sn = a.sharenums[c.slot0 + entry_from(L, i, c.k, e)];
+                    bsoff[b.slot0 + (size_t)sn] = soff[r.slot0 + (size_t)e];
+                    bsavail[b.slot0 + (size_t)sn] = savail[r.slot0 + (size_t)e];
+                    if (e >= c.k) {
+                        b.pmask |= 1ull << (sn - c.k);
+                        brmap[b.rmap0 + (size_t)(sn - c.k)] = (uint32_t)(e - c.k);
+                    }
+                }
+                for (int t = 0; t < c.nt; ++t) {
+                    const int row = a.target_nums[c.tgt0 + t] - c.k;
+                    b.tmask |= 1ull << row;
+                    btmap[b.rmap0 + (size_t)row] = r.tgt0 + (uint32_t)t;
+                }
+                const uint64_t step = (uint64_t)sec_bs_span() * (bs_lanes / 64);
+                std::vector<int> busy;  // row groups with a target or a held row
+                for (int g = 0; g < sec_bs_groups(sh); ++g)
+                    if (((b.pmask | b.tmask) >> (g * NR)) & ((1ull << NR) - 1ull))
+                        busy.push_back(g);
+                add_group_run_tiles(btiles[sh], (uint32_t)rdescs.size(), c.B, step, busy, NR, false);
+                rdescs.push_back(b);
+                continue;
+            }
             if (bs_of[(size_t)i] >= 0) {
                 // its blocks by number (data j at j, parity row p at k + p), the held parity rows'
                 // check-row indices, and one tile per span and row group with a held row, in runs of
@@ -2227,9 +2344,11 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             sp.off_srow = img.put(srow.data(), srow.size() * 4);
             sp.off_mrow = img.put(mrow.data(), mrow.size() * 4);
         }
-        if (!bdescs.empty()) {
+        if (!bdescs.empty() || !rdescs.empty()) {
             const std::vector<sec::Tile> bt = flatten_keyed(btiles, sp.cbs);
-            sp.off_bdesc = img.put(bdescs.data(), bdescs.size() * sizeof(sec::CbsDesc));
+            sp.off_bdesc = rdescs.empty() ? img.put(bdescs.data(), bdescs.size() * sizeof(sec::CbsDesc))
+                                          : img.put(rdescs.data(), rdescs.size() * sizeof(sec::RbsDesc));
+            sp.off_btmap = img.put(btmap.data(), btmap.size() * 4);
             sp.off_btiles = img.put(bt.data(), bt.size() * sizeof(sec::Tile));
             sp.off_bsoff = img.put(bsoff.data(), bsoff.size() * 8);
             sp.off_bsavail = img.put(bsavail.data(), bsavail.size() * 4);
@@ -2277,7 +2396,20 @@ int launch_row_sub(sec_ctx *ctx, const SubPlan &sp, bool host, const uint8_t *bl
     if (timed)
         RC(timing_begin(ctx, &t0, s));
     // the chunks of the bit-sliced check, one launch per shape, into the same flag words
+    // (an operation with targets: the chunks of the bit-sliced repair, stored rows and flag words)
     for (const auto &b : sp.cbs) {
+        if (Op::kTargets) {
+            const sec::RbsSlots rsl{plan.meta.as<uint64_t>(sp.off_bsoff), plan.meta.as<uint32_t>(sp.off_bsavail),
+                                    plan.meta.as<uint32_t>(sp.off_brmap), plan.meta.as<uint32_t>(sp.off_btmap),
+                                    plan.meta.as<uint64_t>(sp.off_toff), flags};
+            int e = sec_launch_repair_bs(b.first, ctx->opt.lanes(O_BS_LANES), blocks, out,
+                                         plan.meta.as<sec::RbsDesc>(sp.off_bdesc),
+                                         plan.meta.as<sec::Tile>(sp.off_btiles) + b.second.first, b.second.second, rsl,
+                                         s);
+            if (e)
+                return hip_fail((hipError_t)e, "sec_repair_bs_kernel");
+            continue;
+        }
         const sec::CbsSlots bsl{plan.meta.as<uint64_t>(sp.off_bsoff), plan.meta.as<uint32_t>(sp.off_bsavail),
                                 plan.meta.as<uint32_t>(sp.off_brmap), flags};
         int e = sec_launch_check_bs(b.first, ctx->opt.lanes(O_BS_LANES), blocks, out,
@@ -2502,6 +2634,10 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
     if (Op::kChecks && !Op::kTargets) {  // sec_ctx_check_methods
         ctx->chk_bs_chunks += plan.nsyn;
         ctx->chk_direct_chunks += plan.ndirect;
+    }
+    if (Op::kTargets) {  // sec_ctx_repair_methods: the chunks with a target
+        ctx->rep_bs_chunks += plan.nsyn;
+        ctx->rep_direct_chunks += plan.ndirect;
     }
     if (Op::kChecks) {
         // every call starts from clean flag words (0xFFFFFFFF: no position yet, row agrees), whatever
@@ -4346,6 +4482,18 @@ int sec_check_method(int k, int m, const int32_t *sharenums, int n, uint64_t B, 
     return SEC_OK;
 }
 
+int sec_repair_method(int k, int m, const int32_t *sharenums, int n, const int32_t *targets, int ntargets, uint64_t B,
+                      const uint64_t *block_avail, int *method)
+{
+    if (!method || n < 0 || ntargets < 0 || (ntargets > 0 && !targets))
+        return SEC_EINVAL;
+    RC(check_blocks(k, m, sharenums, n, targets, ntargets, false));
+    if (B >= (1ull << 31))
+        return SEC_ESIZE;
+    *method = repair_bs_shape(k, m, sharenums, n, ntargets, B, block_avail) >= 0 ? 1 : 0;
+    return SEC_OK;
+}
+
 int sec_check_locate(int k, int m, const int32_t *sharenums, int n, const uint8_t *column, int32_t *culprit)
 {
     RC(check_blocks(k, m, sharenums, k, sharenums ? sharenums + k : nullptr, n - k, true));
@@ -4447,6 +4595,17 @@ int sec_ctx_check_methods(sec_ctx *ctx, int64_t *bitsliced, int64_t *direct)
         *bitsliced = ctx->chk_bs_chunks;
     if (direct)
         *direct = ctx->chk_direct_chunks;
+    return SEC_OK;
+}
+
+int sec_ctx_repair_methods(sec_ctx *ctx, int64_t *bitsliced, int64_t *direct)
+{
+    if (!ctx)
+        return SEC_EINVAL;
+    if (bitsliced)
+        *bitsliced = ctx->rep_bs_chunks;
+    if (direct)
+        *direct = ctx->rep_direct_chunks;
     return SEC_OK;
 }
 

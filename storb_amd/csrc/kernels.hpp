@@ -227,6 +227,30 @@ struct CbsSlots {
     uint32_t *flags;
 };
 
+// One chunk of a bit-sliced repair or repair + check (kernels_bs.hip sec_repair_bs_kernel; 32 B): all
+// k data blocks are held and are the basis, so every target and every check row is zfec's own parity
+// row.  Blocks as CbsDesc's (off / avail from slot0; a target row's entry is unused).  Parity row r,
+// when its bit in tmask is set, is stored whole at out + tgt_off[tmap[rmap0 + r]] (tmap: the row's
+// index in the launch's tgt_off, the caller's target order); when its bit in pmask is set it is
+// compared, rmap[rmap0 + r] its check-row index as in CbsDesc.  No row is in both masks.
+struct RbsDesc {
+    uint64_t pmask;  // bit r: parity row r held (compared)
+    uint64_t tmask;  // bit r: parity row r is a target (stored)
+    uint32_t B;
+    uint32_t slot0;
+    uint32_t flag0;  // as ChkDesc::flag0 (unused when pmask is 0)
+    uint32_t rmap0;  // first of the chunk's m - k entries in RbsSlots::rmap and ::tmap
+};
+
+struct RbsSlots {
+    const uint64_t *off;
+    const uint32_t *avail;
+    const uint32_t *rmap;
+    const uint32_t *tmap;
+    const uint64_t *tgt_off;  // target address: out + tgt_off[target], any byte alignment
+    uint32_t *flags;
+};
+
 // Syndromes are stored bit-sliced (a lane's 8 planes where its 32 bytes would be), at the
 // lanes' unclamped positions: rows of whole 2048-position wave spans.
 constexpr uint64_t kSynSpan = 2048;
@@ -305,6 +329,12 @@ int sec_launch_decode_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *o
 // bit 0 = this tile also copies the data blocks to `out`)
 int sec_launch_check_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::CbsDesc *descs,
                         const sec::Tile *t, uint32_t ntiles, sec::CbsSlots sl, void *stream);
+// Bit-sliced repair and repair + check of chunks whose basis is their k data blocks (phase 1's item
+// pipeline; target rows stored at their own addresses, held rows compared): tiles as the check's
+// (r0 = the row group's first parity row, one tile per span and row group with a target or a held
+// row; ntail unused)
+int sec_launch_repair_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::RbsDesc *descs,
+                         const sec::Tile *t, uint32_t ntiles, sec::RbsSlots sl, void *stream);
 // The shapes with the two-wave phase-1 kernel (zfec(64,96): both 16-row parity groups)
 int sec_syn_pair(int shape);
 // Phase 2: the lost data rows of row group r0 / sec_solve_rows(shape) of each tile's chunk

@@ -493,6 +493,16 @@ struct SynCtx {
     uint64_t dmask, pmask, stride;
 };
 
+// Repair (sec_repair_bs_kernel) accumulates rows it never loads: pmask there is held | target (what
+// syn_rows sees), lmask the held rows alone (what the item pipeline loads).  The pipeline's helpers
+// take the context as a template parameter for this alone; with SynCtx they are what they were.
+struct RbsCtx : SynCtx {
+    uint64_t lmask;
+};
+
+__device__ __forceinline__ uint64_t load_mask(const SynCtx &c) { return c.pmask; }
+__device__ __forceinline__ uint64_t load_mask(const RbsCtx &c) { return c.lmask; }
+
 // a ^ (b & m), m wave-uniform (an SGPR holding 0 or ~0)
 __device__ __forceinline__ u32 xor_and(u32 a, u32 b, u32 m)
 {
@@ -523,22 +533,22 @@ __device__ __forceinline__ void scale_planes(u32 (&y)[8], uint64_t m)
         y[t] = o[t];
 }
 
-template <int K, int NR, int R0>
-__device__ __forceinline__ bool item_present(const SynCtx &c, int J)
+template <int K, int NR, int R0, class C>
+__device__ __forceinline__ bool item_present(const C &c, int J)
 {
-    return J < K ? ((c.dmask >> J) & 1) : ((c.pmask >> (R0 + J - K)) & 1);
+    return J < K ? ((c.dmask >> J) & 1) : ((load_mask(c) >> (R0 + J - K)) & 1);
 }
 
-template <int K, int NR, int R0, int J>
-__device__ __forceinline__ void load_syn_item(u32 (&x)[8], const SynCtx &c)
+template <int K, int NR, int R0, int J, class C>
+__device__ __forceinline__ void load_syn_item(u32 (&x)[8], const C &c)
 {
     constexpr u32 slot = J < K ? (u32)J : (u32)(K + R0 + J - K);
     load_item<J == K - 1>(x, c.blocks + c.off[c.slot0 + slot], c.pa, c.pb, J == K - 1 ? c.avail[c.slot0 + slot] : 0u);
 }
 
-template <int K, int NR, int R0, int... Js>
+template <int K, int NR, int R0, class C, int... Js>
 __device__ __forceinline__ void load_syn_first(std::integer_sequence<int, Js...>, u32 (&ring)[sizeof...(Js)][8],
-                                               const SynCtx &c)
+                                               const C &c)
 {
     ((item_present<K, NR, R0>(c, Js) ? load_syn_item<K, NR, R0, Js>(ring[Js], c) : void()), ...);
 }
@@ -625,8 +635,8 @@ struct SynKept {
 
 // Item J's processing once its 8 dwords are in x: a present data block (copy to its output
 // row, bit-sliced rows of the present parity rows) or a present parity row (the ending's).
-template <int K, int M, int R0, int NR, class End, int J, class... S>
-__device__ __forceinline__ void p1_process(u32 (&acc)[NR * 8], u32 (&x)[8], const SynCtx &c, u8 *orow0, u32 B,
+template <int K, int M, int R0, int NR, class End, int J, class C, class... S>
+__device__ __forceinline__ void p1_process(u32 (&acc)[NR * 8], u32 (&x)[8], const C &c, u8 *orow0, u32 B,
                                            u32 last, bool copies, S... st)
 {
     if constexpr (J < K) {
@@ -651,8 +661,8 @@ __device__ __forceinline__ void p1_process(u32 (&acc)[NR * 8], u32 (&x)[8], cons
     }
 }
 
-template <int K, int M, int R0, int NR, int D, class End, int J, class... S>
-__device__ __forceinline__ void p1_item(u32 (&acc)[NR * 8], u32 (&ring)[D][8], const SynCtx &c, u8 *orow0, u32 B,
+template <int K, int M, int R0, int NR, int D, class End, int J, class C, class... S>
+__device__ __forceinline__ void p1_item(u32 (&acc)[NR * 8], u32 (&ring)[D][8], const C &c, u8 *orow0, u32 B,
                                         u32 last, bool copies, S... st)
 {
     constexpr int NI = K + NR;
@@ -669,9 +679,9 @@ __device__ __forceinline__ void p1_item(u32 (&acc)[NR * 8], u32 (&ring)[D][8], c
     p1_process<K, M, R0, NR, End, J>(acc, x, c, orow0, B, last, copies, st...);
 }
 
-template <int K, int M, int R0, int NR, int D, class End, class... S, int... Js>
+template <int K, int M, int R0, int NR, int D, class End, class C, class... S, int... Js>
 __device__ __forceinline__ void p1_items(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], u32 (&ring)[D][8],
-                                         const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies, S... st)
+                                         const C &c, u8 *orow0, u32 B, u32 last, bool copies, S... st)
 {
     (p1_item<K, M, R0, NR, D, End, Js>(acc, ring, c, orow0, B, last, copies, st...), ...);
 }
@@ -703,17 +713,17 @@ struct RankRing {
     u32 n;     // ranks
 };
 
-template <int K, int NR, int R0>
-__device__ __forceinline__ bool ring_item(const SynCtx &c, u32 it)
+template <int K, int NR, int R0, class C>
+__device__ __forceinline__ bool ring_item(const C &c, u32 it)
 {
     constexpr u32 NI = K + NR;
     if (it >= NI || it == (u32)K - 1)
         return false;
-    return it < (u32)K ? ((c.dmask >> it) & 1) : ((c.pmask >> (R0 + it - K)) & 1);
+    return it < (u32)K ? ((c.dmask >> it) & 1) : ((load_mask(c) >> (R0 + it - K)) & 1);
 }
 
-template <int K, int NR, int R0, class Ring>
-__device__ __forceinline__ RankRing rank_ring(Ring &ring, u32 w, const SynCtx &c)
+template <int K, int NR, int R0, class Ring, class C>
+__device__ __forceinline__ RankRing rank_ring(Ring &ring, u32 w, const C &c)
 {
     const u32 t = threadIdx.x & 63;
     const bool h0 = ring_item<K, NR, R0>(c, t), h1 = ring_item<K, NR, R0>(c, 64 + t);
@@ -749,8 +759,8 @@ __device__ __forceinline__ void rank_issue(Ring &ring, u32 w, const RankRing &rr
                                      (__attribute__((address_space(3))) void *)&ring.v[w][slot][1][0], 16, 0, 0);
 }
 
-template <int K, int M, int R0, int NR, int D, class End, int J, class Ring, class... S>
-__device__ __forceinline__ void p1_item_rank(u32 (&acc)[NR * 8], Ring &ring, u32 w, u32 (&xs)[8], const SynCtx &c,
+template <int K, int M, int R0, int NR, int D, class End, int J, class Ring, class C, class... S>
+__device__ __forceinline__ void p1_item_rank(u32 (&acc)[NR * 8], Ring &ring, u32 w, u32 (&xs)[8], const C &c,
                                              const RankRing &rr, u32 &p, u8 *orow0, u32 B, u32 last, bool copies,
                                              S... st)
 {
@@ -781,9 +791,9 @@ __device__ __forceinline__ void p1_item_rank(u32 (&acc)[NR * 8], Ring &ring, u32
     p1_process<K, M, R0, NR, End, J>(acc, x, c, orow0, B, last, copies, st...);
 }
 
-template <int K, int M, int R0, int NR, int D, class End, class Ring, class... S, int... Js>
+template <int K, int M, int R0, int NR, int D, class End, class Ring, class C, class... S, int... Js>
 __device__ __forceinline__ void p1_items_rank(std::integer_sequence<int, Js...>, u32 (&acc)[NR * 8], Ring &ring,
-                                              u32 w, const SynCtx &c, u8 *orow0, u32 B, u32 last, bool copies,
+                                              u32 w, const C &c, u8 *orow0, u32 B, u32 last, bool copies,
                                               S... st)
 {
     u32 xs[8];
@@ -986,6 +996,97 @@ __global__ __launch_bounds__(256) void sec_check_bs_kernel(const u8 *__restrict_
 // (The two-wave pair form of sec_syndrome_bs_pair_kernel, both groups of a zfec(64,96) span in one
 // workgroup, measured slower here on three cases of four and is archived:
 // tools/archive/kernels_bs_check_pair.diff.)
+
+// ---- repair: lost parity rows of a chunk that holds its k data blocks, optionally with a check ----
+// A repair (or repair + check) whose basis is the chunk's k data blocks regenerates zfec's own
+// parity rows, so it is the check with a fourth ending.  A TARGET row (tmask) is accumulated like a
+// held row (the context's pmask is held | target, which is what syn_rows sees) but is never an item:
+// the pipeline's loads go by the context's lmask, the held rows alone.  After the last item each
+// target row's planes are transposed back and stored whole, as two unaligned 16-byte pieces at the
+// target's own address out + tgt_off[tmap[row]] (any byte alignment, as sec_repair_kernel's; a piece
+// past B moved back to end at B, so nothing outside [0, B) is written and every byte of it is).  A
+// held row (repair + check only) is compared by ChkCompare into ChkDesc::flag0's layout, so
+// sec_check_final runs unchanged behind it.  Targets are stored whether or not the chunk is
+// consistent.  Nothing is copied (`copies` is a constant false: the copy half compiles away).
+// zfec(64,96) runs each 16-row group with a target or a held row as a tile of its own, as the check.
+
+template <int R0, int NR, int r>
+__device__ __forceinline__ void rbs_out(const u32 (&acc)[NR * 8], u8 *out, const sec::RbsSlots &sl, u32 rmap0,
+                                        uint64_t tmask, u32 pa, u32 pb)
+{
+    if (!((tmask >> (R0 + r)) & 1))  // wave-uniform: the descriptor's
+        return;
+    u32 y[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        y[i] = acc[r * 8 + i];
+    transpose8(y);
+    u8 *o = out + sl.tgt_off[sl.tmap[rmap0 + R0 + r]];
+    st16(o + pa, y[0], y[1], y[2], y[3]);
+    st16(o + pb, y[4], y[5], y[6], y[7]);
+}
+
+template <int R0, int NR, int... Rs>
+__device__ __forceinline__ void rbs_outs(std::integer_sequence<int, Rs...>, const u32 (&acc)[NR * 8], u8 *out,
+                                         const sec::RbsSlots &sl, u32 rmap0, uint64_t tmask, u32 pa, u32 pb)
+{
+    (rbs_out<R0, NR, Rs>(acc, out, sl, rmap0, tmask, pa, pb), ...);
+}
+
+// (the span as chk_span)
+template <int K, int M, int R0, int NR, int D, class Ring>
+__device__ __forceinline__ void rbs_span(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::RbsDesc &d,
+                                         const sec::RbsSlots &sl, u32 s, Ring &lring)
+{
+    constexpr uint64_t all = K >= 64 ? ~0ull : (1ull << K) - 1ull;  // every data block is held
+    const u32 B = d.B;
+    const u32 lane = (threadIdx.x & 63) * 16;
+    RbsCtx c{{blocks, sl.off, sl.avail, nullptr, d.slot0, min(s + lane, B - 16), min(s + 1024 + lane, B - 16),
+              s + lane, s + 1024 + lane, all, d.pmask | d.tmask, 0},
+             d.pmask};
+    u32 acc[NR * 8];
+#pragma unroll
+    for (int i = 0; i < NR * 8; ++i)
+        acc[i] = 0;
+    const u32 *rmap = sl.rmap + d.rmap0;
+    u32 *flags = sl.flags + d.flag0;
+    if constexpr (K >= 32) {
+        constexpr int DL = SEC_FUSED_LDS_RING;
+        const u32 w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        p1_items_rank<K, M, R0, NR, DL, ChkCompare>(std::make_integer_sequence<int, K + NR>{}, acc, lring, w, c,
+                                                    (u8 *)nullptr, B, B, false, rmap, flags);
+    } else {
+        u32 ring[D][8];
+        load_syn_first<K, NR, R0>(std::make_integer_sequence<int, D>{}, ring, c);
+        p1_items<K, M, R0, NR, D, ChkCompare>(std::make_integer_sequence<int, K + NR>{}, acc, ring, c, (u8 *)nullptr,
+                                              B, B, false, rmap, flags);
+    }
+    rbs_outs<R0, NR>(std::make_integer_sequence<int, NR>{}, acc, out, sl, d.rmap0, d.tmask, c.pa, c.pb);
+}
+
+// Tiles as the check's: r0 = the row group's first parity row.
+template <int K, int M, int NR, int D>
+__global__ __launch_bounds__(256) void sec_repair_bs_kernel(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                            const sec::RbsDesc *__restrict__ descs,
+                                                            const sec::Tile *__restrict__ tiles,
+                                                            const sec::RbsSlots sl)
+{
+    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::RbsDesc d = descs[tl.chunk];
+    const u32 s = tl.t0 + (threadIdx.x >> 6) * kSpan;
+    if (s >= d.B)
+        return;
+    __shared__ Phase1Lds<K> lring;  // one ring for both row-group variants
+    if constexpr (M - K <= NR) {
+        rbs_span<K, M, 0, NR, D>(blocks, out, d, sl, s, lring);
+    } else {
+        static_assert(M - K == 2 * NR, "two row groups");
+        if (tl.r0 == 0)
+            rbs_span<K, M, 0, NR, D>(blocks, out, d, sl, s, lring);
+        else
+            rbs_span<K, M, NR, NR, D>(blocks, out, d, sl, s, lring);
+    }
+}
 
 // ---- decode, phase 2: lost row l = z_l * XOR_{r in S} c[r][l] * (w_r s_r) ----------------------
 struct SolveCtx {
@@ -1503,6 +1604,20 @@ int sec_launch_check_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *ou
     return dispatch_shape(shape, [&](auto i) {
         constexpr BsShape S = kShapes[decltype(i)::value];
         constexpr auto kern = sec_check_bs_kernel<S.k, S.m, S.nr, S.p1_ring>;
+        return launch(kern, ntiles, lanes, 0, stream, blocks, out, descs, t, sl);
+    });
+}
+
+int sec_launch_repair_bs(int shape, int lanes, const uint8_t *blocks, uint8_t *out, const sec::RbsDesc *descs,
+                         const sec::Tile *t, uint32_t ntiles, sec::RbsSlots sl, void *stream)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    if (!lanes_ok(lanes))
+        return hipErrorInvalidValue;
+    return dispatch_shape(shape, [&](auto i) {
+        constexpr BsShape S = kShapes[decltype(i)::value];
+        constexpr auto kern = sec_repair_bs_kernel<S.k, S.m, S.nr, S.p1_ring>;
         return launch(kern, ntiles, lanes, 0, stream, blocks, out, descs, t, sl);
     });
 }

@@ -550,6 +550,14 @@ class Engine:
         self._check(self.lib.sec_ctx_check_methods(self._ctx, ctypes.byref(b), ctypes.byref(d)))
         return b.value, d.value
 
+    def repair_methods(self) -> tuple[int, int]:
+        """(bit-sliced, direct): chunks with at least one target that repair and repair + check
+        calls have repaired so far, by kernel (option ``SEC_CHECK_BS``; ``repair_method`` says
+        which chunks are eligible)."""
+        b, d = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.lib.sec_ctx_repair_methods(self._ctx, ctypes.byref(b), ctypes.byref(d)))
+        return b.value, d.value
+
     _SCRATCH_CAP = 256 << 20  # largest result staged in the reusable pinned scratch
 
     def _out_buffer(self, nbytes: int) -> np.ndarray:
@@ -992,6 +1000,24 @@ def check_locate(k: int, m: int, sharenums, column) -> int:
     who = ctypes.c_int32(0)
     check(lib.sec_check_locate(int(k), int(m), _ptr(sn) or None, sn.size, _ptr(col) or None, ctypes.byref(who)), lib)
     return who.value
+
+
+def repair_method(k: int, m: int, sharenums, targets, B: int, avail=None) -> bool:
+    """Whether a chunk of a repair (len(sharenums) == k) or a repair + check is eligible for the
+    bit-sliced repair kernel (sec_repair_method): a bit-sliced shape, B >= 16, a target or a check
+    row, the first k sharenums the data blocks 0 .. k-1 in any order, and every entry but data
+    block k-1 readable to B (avail: one length per sharenum, or None = all B).  Eligibility alone:
+    option ``SEC_CHECK_BS`` decides whether an eligible chunk takes that kernel."""
+    lib = _lib.load()
+    sn = np.ascontiguousarray([int(x) for x in sharenums], dtype=np.int32)
+    tg = np.ascontiguousarray([int(x) for x in targets], dtype=np.int32)
+    av = None if avail is None else np.ascontiguousarray([int(x) for x in avail], dtype=np.uint64)
+    if av is not None and av.size != sn.size:
+        raise ValueError("repair_method: one avail per sharenum")
+    out = ctypes.c_int(0)
+    check(lib.sec_repair_method(int(k), int(m), _ptr(sn) or None, sn.size, _ptr(tg) or None, tg.size, int(B),
+                                None if av is None else (_ptr(av) or None), ctypes.byref(out)), lib)
+    return bool(out.value)
 
 
 def repair_matrix(k: int, m: int, sharenums, targets) -> bytes:
