@@ -20,7 +20,8 @@ LIB = os.path.join(LIBDIR, "libstorbec.so")
 VARIANT_DIR = os.path.join(ROOT, "build", "variants")
 INCLUDE = os.path.join(ROOT, "include")
 SOURCES = ["kernels.hip", "kernels_bs.hip", "bignum.hip", "api.cpp"]
-HEADERS = ["kernels.hpp", "bignum.hpp", "bn_host.hpp", "gf_host.hpp", "gf_const.hpp", "task_pool.hpp"]
+HEADERS = ["kernels.hpp", "bignum.hpp", "bn_host.hpp", "bs_plan.hpp", "gf_host.hpp", "gf_const.hpp",
+           "task_pool.hpp"]
 # gfx950 (MI355X) only: the kernels use gfx950 instructions (16-byte global_load_lds, v_bitop3)
 # and up to 160 KiB of LDS per workgroup; kernels_bs.hip stops any other target with #error
 ARCH = "gfx950"

@@ -33,6 +33,7 @@
 #include "task_pool.hpp"
 #include "bignum.hpp"
 #include "bn_host.hpp"
+#include "bs_plan.hpp"
 #include "gf_host.hpp"
 #include "kernels.hpp"
 #include "storb_ec.h"
@@ -309,12 +310,10 @@ struct SubPlan {
     size_t off_cpos = 0, off_echunk = 0;   // the entries' caller positions and chunks (ChkSlots)
     uint32_t nentries = 0;                 // entries of the unit's chunks (operations with compared rows)
     size_t off_cdesc = 0;                  // the chunks' ChkDesc (sec_check_final)
-    // bit-sliced checks (sec_check_bs_kernel): launches as (shape, (first, count)) in their tiles;
-    // their descriptors, tiles and per-block addresses, avails and parity-row -> check-row maps.
-    // An operation with targets keeps its bit-sliced repairs (sec_repair_bs_kernel) here instead:
-    // RbsDesc at off_bdesc, and the parity-row -> target map
-    KeyedLaunches cbs;
-    size_t off_bdesc = 0, off_btiles = 0, off_bsoff = 0, off_bsavail = 0, off_brmap = 0, off_btmap = 0;
+    // bit-sliced row launches (add_bs_row_chunk; Op::kBsLaunch) as (shape, (first, count)) in their tiles;
+    // their Op::BsDesc, tiles, blocks by number and parity-row -> check-row and -> target maps
+    KeyedLaunches bs_rows;
+    size_t off_bs_desc = 0, off_bs_tiles = 0, off_bs_soff = 0, off_bs_avail = 0, off_bs_rmap = 0, off_bs_tmap = 0;
     // host mode's slab output: the results at 0, then row_bad and column, then the stored rows
     // (targets or decoded bytes), then the digests (dig_off)
     uint64_t chk_rows = 0, chk_col = 0, pay_off = 0;
@@ -337,8 +336,7 @@ struct Plan {
     DevBuf meta;  // device copy of the metadata image of every sub-plan
     bool valid = false;
     int64_t nsyn = 0, ndirect = 0, nfused = 0;  // decode: chunks with a lost primary, by method
-                                                // (check, decode + check: chunks with a check row,
-                                                // bit-sliced in nsyn, direct in ndirect)
+    int64_t nrow_bs = 0, nrow_direct = 0;  // row operations: the chunks Op::bs_judged, by the kernels they took
     uint64_t nflags = 0;                        // check: flag words of the whole call
 };
 
@@ -449,7 +447,7 @@ int syn_choice(const Options &o, const sec_dec_chunk &c, const int *idx, int e, 
     const int sh = sec_syn_shape(c.k, c.m);
     // e < k - 1: the LDS-ring kernels point an absent item's loads at the first present data block
     // other than the (possibly short) block k-1 (kernels_bs.hip item_addrs)
-    if (sh < 0 || e < 1 || e >= c.k - 1 || c.B < 16 || c.B > 0xFFFFFFFFull - 8192 || c.padlen >= c.B)
+    if (sh < 0 || e < 1 || e >= c.k - 1 || c.B < 16 || c.B > sec::kBsMaxB || c.padlen >= c.B)
         return -1;
     // g16: 16-row data groups with a lost row, the grouping the two-kernel estimate was fitted on
     // (r03); phase 2 now runs 8-row groups (SEC_SOLVE_NR), which measured faster, not slower, so
@@ -561,7 +559,7 @@ int bs_shape(const Options &o, int k, int m, uint64_t B)
 {
     if (o[O_BS] == 0)
         return -1;
-    if (B < 16 || B > 0xFFFFFFFFull - 8192)
+    if (B < 16 || B > sec::kBsMaxB)
         return -1;
     // Default: the shapes with >= 8 parity rows, where the v_perm rows are VALU-bound (1.3-1.7x
     // here), and C4's RS(10,4) (+0-4 %, whole 65536-chunk job +2 %); the other p <= 4 shapes
@@ -641,19 +639,6 @@ void flatten(const Bins &bins, std::vector<Group> &groups, std::vector<sec::Tile
             std::copy(g.begin(), g.end(), tiles.begin() + first);
         }
     }
-}
-
-// One chunk's tiles for a bit-sliced kernel that runs each row group as a tile of its own, in runs
-// of 8 positions per group: workgroup b runs on XCD b % 8, so one XCD's L2 serves a span's second
-// read.  `copy_first`: the first group's tiles carry ntail bit 0 (they copy the chunk's blocks).
-void add_group_run_tiles(std::vector<sec::Tile> &tiles, uint32_t desc_index, uint64_t B, uint64_t step,
-                         const std::vector<int> &groups, int rows_per_group, bool copy_first)
-{
-    for (uint64_t t0 = 0; t0 < B; t0 += 8 * step)
-        for (int g : groups)
-            for (uint64_t t = t0; t < std::min(B, t0 + 8 * step); t += step)
-                tiles.push_back(sec::Tile{desc_index, (uint32_t)t, (uint32_t)(g * rows_per_group),
-                                          copy_first && g == groups[0] ? 1u : 0u});
 }
 
 // The tiles of every key, in key order, as one array; `launches` gets (key, (first, count)) in it.
@@ -1357,34 +1342,6 @@ uint64_t slot_avail(const Chunk &c, const uint64_t *block_avail, int j)
     return block_avail ? std::min<uint64_t>(block_avail[c.slot0 + j], c.B) : c.B;
 }
 
-// Bit-sliced check (kernels_bs.hip sec_check_bs_kernel): the shape of its kernel for a chunk of a
-// check or a decode + check whose arguments passed the call's screen, or -1 (the direct kernels).
-// Eligible when
-//   * (k, m) is one of the bit-sliced shapes, 16 <= B (below it the tail kernel) and at least one
-//     check row is held (n > k);
-//   * the first k entries are the data blocks 0 .. k-1 in any order, so the check rows are zfec's
-//     own parity rows and nothing is recovered (a decode + check with a missing primary holds a
-//     parity row in its basis);
-//   * every entry's avail is one phase 1's loader honours: that loader clamps its addresses to
-//     B - 16 and reads whole 16-byte pieces, taking the zero-filling byte path for data block k-1
-//     alone (zfec's padded last block read in place), so every other entry, data or parity, must
-//     be readable to B; block k-1 may have any avail;
-//   * padlen < B (only output row k-1 is short), as the syndrome decode asks.
-// avail: the chunk's n entries in the caller's order, or NULL (all B).
-int check_bs_shape(int k, int m, const int32_t *sn, int n, uint64_t B, const uint64_t *avail, uint64_t padlen)
-{
-    const int sh = sec_bs_shape(k, m);
-    if (sh < 0 || n <= k || B < 16 || B > 0xFFFFFFFFull - 8192 || padlen >= B)
-        return -1;
-    for (int j = 0; j < k; ++j)
-        if (sn[j] >= k)
-            return -1;
-    for (int e = 0; avail && e < n; ++e)
-        if (sn[e] != k - 1 && avail[e] < B)
-            return -1;
-    return sh;
-}
-
 // Whether an eligible chunk takes the bit-sliced check.  SEC_CHECK_BS = 0 never, 1 always; the
 // default takes it only where it measured at least 5 % faster than the direct kernels (rounds differ
 // by up to 3 %, boxes by 1-3 %), by shape, block size and whether the kernel also copies the data
@@ -1408,30 +1365,6 @@ bool check_bs_rule(const Options &o, int shape, uint64_t B, bool copies)
     case 4: return B >= (4u << 10);
     default: return false;
     }
-}
-
-// Bit-sliced repair (kernels_bs.hip sec_repair_bs_kernel): the shape of its kernel for a chunk of a
-// repair (n == k) or a repair + check whose arguments passed the call's screen, or -1 (the direct
-// kernels).  Eligible when
-//   * (k, m) is one of the bit-sliced shapes, 16 <= B (below it the tail kernel), and the chunk has
-//     a row at all: a target or a check row (nt + n - k >= 1);
-//   * the first k entries are the data blocks 0 .. k-1 in any order.  No target is held, so every
-//     target is then a parity row, and so is every check row: rows of the matrix the kernel holds;
-//   * every entry's avail is one phase 1's loader honours, as check_bs_shape asks: block k-1 may
-//     have any avail, every other entry is readable to B.
-// avail: the chunk's n entries in the caller's order, or NULL (all B).
-int repair_bs_shape(int k, int m, const int32_t *sn, int n, int nt, uint64_t B, const uint64_t *avail)
-{
-    const int sh = sec_bs_shape(k, m);
-    if (sh < 0 || nt + (n - k) < 1 || B < 16 || B > 0xFFFFFFFFull - 8192)
-        return -1;
-    for (int j = 0; j < k; ++j)
-        if (sn[j] >= k)
-            return -1;
-    for (int e = 0; avail && e < n; ++e)
-        if (sn[e] != k - 1 && avail[e] < B)
-            return -1;
-    return sh;
 }
 
 // Whether an eligible chunk with nt >= 1 targets and nr compared rows takes the bit-sliced repair.
@@ -1653,35 +1586,26 @@ int build_decode_plan(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks
                 // phase 1: every present block in place, syndromes to the scratch
                 const int k = c.k, p = c.m - c.k, e = (int)e_of[i], NR = sec_bs_rows(sh);
                 const bool copies = !recover && !nocopy;
+                const uint32_t last = recover ? (uint32_t)c.B : (uint32_t)(nout - (uint64_t)(k - 1) * c.B);
+                const auto lay = sec::bs_layout(k, c.m, idx, &soff[slot0], &savail[slot0], k, k, ssoff, ssavail);
                 sec::SynDesc sd{};
                 sd.out_off = d.out_off;
                 sd.syn_off = sp.syn_bytes;
+                sd.dmask = lay.dmask;
+                sd.pmask = lay.pmask;
                 sd.B = (uint32_t)c.B;
-                sd.last = recover ? (uint32_t)c.B : (uint32_t)(nout - (uint64_t)(k - 1) * c.B);
-                sd.slot0 = (uint32_t)ssoff.size();
-                ssoff.resize(ssoff.size() + (size_t)(k + p), 0);
-                ssavail.resize(ssavail.size() + (size_t)(k + p), 0);
-                for (int s = 0; s < k; ++s) {
-                    const size_t j = sd.slot0 + (idx[s] < k ? (size_t)s : (size_t)idx[s]);
-                    (idx[s] < k ? sd.dmask : sd.pmask) |= 1ull << (idx[s] < k ? s : idx[s] - k);
-                    ssoff[j] = soff[slot0 + s];
-                    ssavail[j] = savail[slot0 + s];
-                }
-                std::vector<int> gs;  // touched row groups, ascending
-                for (int g = 0; g * NR < p; ++g)
-                    if ((sd.pmask >> (g * NR)) & ((NR >= 64 ? ~0ull : (1ull << NR) - 1)))
-                        gs.push_back(g);
+                sd.last = last;
+                sd.slot0 = lay.slot0;
+                const std::vector<int> gs = sec::touched_groups(sd.pmask, p, NR);  // parity row groups
                 const int method = fuse_of[i];  // syn_choice: both phases in one kernel unless kSynTwo
                 if (method == kSynTwo)
                     sp.syn_bytes += (uint64_t)e * sec::syn_stride(c.B);
                 // the scalings of this erasure pattern (shared by the chunks that have it)
                 uint64_t lost = 0;
-                std::string key = std::to_string(k) + "/" + std::to_string(c.m) + ":";
-                for (int s = 0; s < k; ++s) {
-                    key += std::to_string(idx[s]) + ",";
+                for (int s = 0; s < k; ++s)
                     if (idx[s] >= k)
                         lost |= 1ull << s;
-                }
+                const std::string key = slots_key(k, c.m, idx);
                 auto mk = mask_of.find(key);
                 if (mk == mask_of.end()) {
                     std::vector<int> S, Lost;
@@ -1717,7 +1641,7 @@ int build_decode_plan(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks
                     for (uint64_t t = 0; t < c.B; t += sec_bs_span())
                         st2.push_back(sec::Tile{si, (uint32_t)t, 0u, copies ? 1u : 0u});
                 } else {
-                    add_group_run_tiles(stiles[sh], si, c.B, step, gs, NR, copies);
+                    sec::add_group_run_tiles(stiles[sh], si, c.B, step, gs, NR, copies);
                 }
                 // phase 2: the groups of lost rows, their tiles interleaved as phase 1's
                 sec::SolveDesc vd{};
@@ -1726,7 +1650,7 @@ int build_decode_plan(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks
                 vd.lost = lost;
                 vd.pmask = sd.pmask;
                 vd.B = (uint32_t)c.B;
-                vd.last = recover ? (uint32_t)c.B : (uint32_t)(nout - (uint64_t)(k - 1) * c.B);
+                vd.last = last;
                 vd.zq0 = mk->second.second;
                 vd.recover = recover ? 1u : 0u;
                 const uint32_t vi = (uint32_t)vdescs.size();
@@ -1738,11 +1662,7 @@ int build_decode_plan(sec_ctx *ctx, const sec_dec_chunk *chunks, int64_t nchunks
                     continue;
                 }
                 const int NR2 = sec_solve_rows(sh);
-                std::vector<int> gl;
-                for (int g = 0; g * NR2 < k; ++g)
-                    if ((lost >> (g * NR2)) & ((NR2 >= 64 ? ~0ull : (1ull << NR2) - 1)))
-                        gl.push_back(g);
-                add_group_run_tiles(vtiles[sh], vi, c.B, step, gl, NR2, false);
+                sec::add_group_run_tiles(vtiles[sh], vi, c.B, step, sec::touched_groups(lost, k, NR2), NR2, false);
             } else if (nout > 0 && !(nocopy && e_of[i] == 0)) {
                 add_work(bins, tail, (uint32_t)(i - c0), c.B, valid, (int)e_of[i], c.k, true, false,
                          recover || nocopy ? dec_small_kb(c.k) : 0);
@@ -1867,8 +1787,8 @@ int launch_decode_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
 //   repair + check   n              targets, at caller addresses        entries k..n-1   optional
 // What differs is held in a traits struct per operation (RepairOp .. RepairCheckOp): the ABI chunk
 // and its RowChunk view, the device descriptor and slots the tile kernels take, the order of its
-// precondition errors (screen_first over the whole batch, then screen chunk by chunk), and its timing
-// kind.
+// precondition errors (screen_first over the whole batch, then screen chunk by chunk), its timing
+// kind, and, in a base struct per family (CheckBsFamily, RepairBsFamily), its bit-sliced kernel.
 
 // A chunk of any of the four, in common terms (fields an operation lacks are 0)
 struct RowChunk {
@@ -1908,7 +1828,43 @@ int check_held(const RowChunk &c, const RowArgs &a, const int32_t *targets = nul
     return check_blocks(c.k, c.m, a.sharenums + c.slot0, c.n, targets, c.nt, false);
 }
 
-struct RepairOp {
+// The bit-sliced kernel of an operation's family: its descriptor, the chunks its rule judges (bs_judged)
+// and of those the ones it takes (bs_shape, else -1), its launcher and slots.  Check and decode + check:
+struct CheckBsFamily {
+    using BsDesc = sec::CbsDesc;
+    static constexpr const char *kBsKernel = "sec_check_bs_kernel";
+    static bool bs_judged(const RowChunk &c) { return c.n > c.k; }
+    static int bs_shape(const Options &o, const RowChunk &c, const int32_t *sn, const uint64_t *avail, bool copies)
+    {
+        const int sh = sec::check_bs_shape(sec_bs_shape(c.k, c.m), c.k, sn, c.n, c.B, avail, c.padlen);
+        return sh >= 0 && check_bs_rule(o, sh, c.B, copies) ? sh : -1;
+    }
+    static constexpr auto kBsLaunch = sec_launch_check_bs;
+    static sec::CbsSlots bs_slots(const DevBuf &m, const SubPlan &sp, uint32_t *flags)
+    {
+        return {m.as<uint64_t>(sp.off_bs_soff), m.as<uint32_t>(sp.off_bs_avail), m.as<uint32_t>(sp.off_bs_rmap), flags};
+    }
+};
+
+// Repair and repair + check.  A repair + check chunk with no target is a plain check and stays direct.
+struct RepairBsFamily {
+    using BsDesc = sec::RbsDesc;
+    static constexpr const char *kBsKernel = "sec_repair_bs_kernel";
+    static bool bs_judged(const RowChunk &c) { return c.nt >= 1; }
+    static int bs_shape(const Options &o, const RowChunk &c, const int32_t *sn, const uint64_t *avail, bool)
+    {
+        const int sh = sec::repair_bs_shape(sec_bs_shape(c.k, c.m), c.k, sn, c.n, c.nt, c.B, avail);
+        return sh >= 0 && repair_bs_rule(o, sh, c.B, c.nt, c.n - c.k) ? sh : -1;
+    }
+    static constexpr auto kBsLaunch = sec_launch_repair_bs;
+    static sec::RbsSlots bs_slots(const DevBuf &m, const SubPlan &sp, uint32_t *flags)
+    {
+        return {m.as<uint64_t>(sp.off_bs_soff), m.as<uint32_t>(sp.off_bs_avail), m.as<uint32_t>(sp.off_bs_rmap),
+                m.as<uint32_t>(sp.off_bs_tmap), m.as<uint64_t>(sp.off_toff), flags};
+    }
+};
+
+struct RepairOp : RepairBsFamily {
     using Chunk = sec_rep_chunk;
     using Desc = sec::RepDesc;
     using Slots = sec::RepSlots;
@@ -1935,7 +1891,7 @@ struct RepairOp {
     }
 };
 
-struct CheckOp {
+struct CheckOp : CheckBsFamily {
     using Chunk = sec_chk_chunk;
     using Desc = sec::ChkDesc;
     using Slots = sec::ChkSlots;
@@ -1957,7 +1913,7 @@ struct CheckOp {
     }
 };
 
-struct DecodeCheckOp {
+struct DecodeCheckOp : CheckBsFamily {
     using Chunk = sec_dchk_chunk;
     using Desc = sec::DChkDesc;
     using Slots = sec::DChkSlots;
@@ -2002,7 +1958,7 @@ struct DecodeCheckOp {
     }
 };
 
-struct RepairCheckOp {
+struct RepairCheckOp : RepairBsFamily {
     using Chunk = sec_rchk_chunk;
     using Desc = sec::RChkDesc;
     using Slots = sec::RChkSlots;
@@ -2063,6 +2019,50 @@ int rows_coef(int k, int m, const int *idx, const std::vector<int> &rows, std::v
 // The caller position of entry e of a chunk: the basis in normalised order, then the caller's
 int entry_from(const SlotLayout &L, int64_t i, int k, int e) { return e < k ? L.perm[L.first[i] + e] : e; }
 
+template <class Op> struct BsRowUnit {  // a launch unit's SubPlan::bs_rows while its plan is built
+    std::vector<typename Op::BsDesc> descs;
+    std::vector<uint64_t> soff;
+    std::vector<uint32_t> savail, rmap, tmap;
+    std::map<int, std::vector<sec::Tile>> tiles;  // by shape
+};
+
+// One chunk of the operation's bit-sliced kernel of shape sh: its n entries (the direct kernels':
+// blocks sn at eoff, eavail) by block number, the held parity rows' check-row indices, the target
+// rows' indices in tgt_off, and one tile per span and row group with a held row or a target, in runs
+// of 8.  A decode + check that reassembles: the first such group's tiles copy the data blocks.
+template <class Op>
+void add_bs_row_chunk(BsRowUnit<Op> &u, int sh, int lanes, const RowChunk &c, const RowInfo &r, const int *sn,
+                      const uint64_t *eoff, const uint32_t *eavail, const int32_t *targets, bool recover)
+{
+    const int p = c.m - c.k, NR = sec_bs_rows(sh);
+    const auto lay = sec::bs_layout(c.k, c.m, sn, eoff, eavail, c.n, c.k, u.soff, u.savail, &u.rmap);
+    typename Op::BsDesc b{};
+    b.pmask = lay.pmask;
+    b.B = r.B;
+    b.slot0 = lay.slot0;
+    b.flag0 = r.flag0;
+    b.rmap0 = lay.rmap0;
+    uint64_t rows = b.pmask;
+    bool copies = false;
+    if constexpr (Op::kTargets) {
+        u.tmap.resize(u.tmap.size() + (size_t)p, 0);
+        for (int t = 0; t < c.nt; ++t) {
+            const int row = targets[t] - c.k;
+            b.tmask |= 1ull << row;
+            u.tmap[b.rmap0 + (size_t)row] = r.tgt0 + (uint32_t)t;
+        }
+        rows |= b.tmask;
+    } else {
+        b.out_off = r.out_off;
+        b.last = (uint32_t)(Op::kDecodes && !recover ? c.B - c.padlen : c.B);
+        copies = Op::kDecodes && !recover && r.nout > 0;
+    }
+    const uint64_t step = (uint64_t)sec_bs_span() * (lanes / 64);
+    const std::vector<int> groups = sec::touched_groups(rows, p, NR);
+    sec::add_group_run_tiles(u.tiles[sh], (uint32_t)u.descs.size(), c.B, step, groups, NR, copies);
+    u.descs.push_back(b);
+}
+
 // Per chunk: the table of its stored rows, then its compared rows, over its basis (layout
 // [slot][row][5]); its held entries (the basis in normalised order, then the compared rows in the
 // caller's); tiles as a copy-free decode's (add_work) over all its rows and [0, valid), valid = the
@@ -2083,41 +2083,19 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
     const bool recover = a.flags & SEC_F_RECOVER, digest = a.digests != nullptr;
     std::vector<PendingExpand> pending;
     std::vector<uint32_t> tab_of, ns_of((size_t)nchunks, 0);
-    std::vector<int> rows;
-    // check and decode + check: the chunks the bit-sliced check kernel takes (its shape, else -1);
-    // they need no table and get no tile of the direct kernels.  Staged entries are all B long.
-    constexpr bool bs_op = Op::kChecks && !Op::kTargets;
+    std::vector<int> rows, sn;  // scratch: a chunk's table rows (rows_of), its entries' block numbers
+    // the chunks the operation's bit-sliced kernel takes (its shape, else -1); they need no table and
+    // get no tile of the direct kernels.  Staged entries are all B long.
     std::vector<int> bs_of((size_t)nchunks, -1);
-    plan.nsyn = plan.ndirect = 0;
-    for (int64_t i = 0; bs_op && i < nchunks; ++i) {
+    plan.nrow_bs = plan.nrow_direct = 0;
+    for (int64_t i = 0; i < nchunks; ++i) {
         const RowChunk c = Op::view(chunks[i]);
-        if (c.n <= c.k)
+        if (!Op::bs_judged(c))
             continue;
-        const int sh = check_bs_shape(c.k, c.m, a.sharenums + c.slot0, c.n, c.B,
-                                      host || !a.block_avail ? nullptr : a.block_avail + c.slot0, c.padlen);
         const bool copies = Op::kDecodes && !recover && (uint64_t)c.k * c.B > c.padlen;
-        if (sh >= 0 && check_bs_rule(ctx->opt, sh, c.B, copies)) {
-            bs_of[(size_t)i] = sh;
-            ++plan.nsyn;
-        } else {
-            ++plan.ndirect;
-        }
-    }
-    // repair and repair + check: the chunks with a target that the bit-sliced repair kernel takes,
-    // in the same list (an operation has one kind or the other).  A repair + check chunk with no
-    // target is a plain check and stays with the direct kernels, whatever the option.
-    for (int64_t i = 0; Op::kTargets && i < nchunks; ++i) {
-        const RowChunk c = Op::view(chunks[i]);
-        if (c.nt < 1)
-            continue;
-        const int sh = repair_bs_shape(c.k, c.m, a.sharenums + c.slot0, c.n, c.nt, c.B,
-                                       host || !a.block_avail ? nullptr : a.block_avail + c.slot0);
-        if (sh >= 0 && repair_bs_rule(ctx->opt, sh, c.B, c.nt, c.n - c.k)) {
-            bs_of[(size_t)i] = sh;
-            ++plan.nsyn;
-        } else {
-            ++plan.ndirect;
-        }
+        bs_of[(size_t)i] = Op::bs_shape(ctx->opt, c, a.sharenums + c.slot0,
+                                        host || !a.block_avail ? nullptr : a.block_avail + c.slot0, copies);
+        ++(bs_of[(size_t)i] >= 0 ? plan.nrow_bs : plan.nrow_direct);
     }
     auto rows_of =[&](int64_t i) {  // -> rows; ns_of[i] = how many of them are stored
         const RowChunk c = Op::view(chunks[i]);
@@ -2170,11 +2148,7 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         std::vector<sec::MsgDesc> msgs;
         Bins bins;
         std::vector<sec::TailItem> tail;
-        std::vector<sec::CbsDesc> bdescs;
-        std::vector<uint64_t> bsoff;
-        std::vector<uint32_t> bsavail, brmap, btmap;
-        std::vector<sec::RbsDesc> rdescs;              // the bit-sliced repair's, in bdescs' place
-        std::map<int, std::vector<sec::Tile>> btiles;  // by shape
+        BsRowUnit<Op> bsr;
         uint64_t nent = 0;
         if (Op::kChecks) {
             for (int64_t i = c0; i < c1; ++i)
@@ -2250,76 +2224,11 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             }
             sp.in_bytes += (uint64_t)c.n * c.B;
             sp.out_bytes += nstore;
-            if (Op::kTargets && bs_of[(size_t)i] >= 0) {
-                // the bit-sliced repair: its blocks by number as below, the target rows' indices in
-                // tgt_off, the held parity rows' check-row indices, and one tile per span and row
-                // group with a target or a held row, in the check's runs of 8
-                const int sh = bs_of[(size_t)i], NR = sec_bs_rows(sh);
-                sec::RbsDesc b{};
-                b.B = r.B;
-                b.slot0 = (uint32_t)bsoff.size();
-                b.flag0 = r.flag0;
-                b.rmap0 = (uint32_t)brmap.size();
-                bsoff.resize(bsoff.size() + (size_t)c.m, 0);
-                bsavail.resize(bsavail.size() + (size_t)c.m, 0);
-                brmap.resize(brmap.size() + (size_t)(c.m - c.k), 0);
-                btmap.resize(btmap.size() + (size_t)(c.m - c.k), 0);
-                for (int e = 0; e < c.n; ++e) {
-                    const int sn = a.sharenums[c.slot0 + entry_from(L, i, c.k, e)];
-                    bsoff[b.slot0 + (size_t)sn] = soff[r.slot0 + (size_t)e];
-                    bsavail[b.slot0 + (size_t)sn] = savail[r.slot0 + (size_t)e];
-                    if (e >= c.k) {
-                        b.pmask |= 1ull << (sn - c.k);
-                        brmap[b.rmap0 + (size_t)(sn - c.k)] = (uint32_t)(e - c.k);
-                    }
-                }
-                for (int t = 0; t < c.nt; ++t) {
-                    const int row = a.target_nums[c.tgt0 + t] - c.k;
-                    b.tmask |= 1ull << row;
-                    btmap[b.rmap0 + (size_t)row] = r.tgt0 + (uint32_t)t;
-                }
-                const uint64_t step = (uint64_t)sec_bs_span() * (bs_lanes / 64);
-                std::vector<int> busy;  // row groups with a target or a held row
-                for (int g = 0; g < sec_bs_groups(sh); ++g)
-                    if (((b.pmask | b.tmask) >> (g * NR)) & ((1ull << NR) - 1ull))
-                        busy.push_back(g);
-                add_group_run_tiles(btiles[sh], (uint32_t)rdescs.size(), c.B, step, busy, NR, false);
-                rdescs.push_back(b);
-                continue;
-            }
             if (bs_of[(size_t)i] >= 0) {
-                // its blocks by number (data j at j, parity row p at k + p), the held parity rows'
-                // check-row indices, and one tile per span and row group with a held row, in runs of
-                // 8 tiles of each group: workgroup b runs on XCD b % 8, so the tiles reading the
-                // same data blocks share an L2.  The first such group copies the data blocks.
-                const int sh = bs_of[(size_t)i], NR = sec_bs_rows(sh);
-                sec::CbsDesc b{};
-                b.out_off = r.out_off;
-                b.B = r.B;
-                b.last = (uint32_t)(Op::kDecodes && !recover ? c.B - c.padlen : c.B);
-                b.slot0 = (uint32_t)bsoff.size();
-                b.flag0 = r.flag0;
-                b.rmap0 = (uint32_t)brmap.size();
-                bsoff.resize(bsoff.size() + (size_t)c.m, 0);
-                bsavail.resize(bsavail.size() + (size_t)c.m, 0);
-                brmap.resize(brmap.size() + (size_t)(c.m - c.k), 0);
-                for (int e = 0; e < c.n; ++e) {
-                    const int sn = a.sharenums[c.slot0 + entry_from(L, i, c.k, e)];
-                    bsoff[b.slot0 + (size_t)sn] = soff[r.slot0 + (size_t)e];
-                    bsavail[b.slot0 + (size_t)sn] = savail[r.slot0 + (size_t)e];
-                    if (e >= c.k) {
-                        b.pmask |= 1ull << (sn - c.k);
-                        brmap[b.rmap0 + (size_t)(sn - c.k)] = (uint32_t)(e - c.k);
-                    }
-                }
-                const bool copies = Op::kDecodes && !recover && r.nout > 0;
-                const uint64_t step = (uint64_t)sec_bs_span() * (bs_lanes / 64);
-                std::vector<int> held;  // row groups with a held row
-                for (int g = 0; g < sec_bs_groups(sh); ++g)
-                    if ((b.pmask >> (g * NR)) & ((1ull << NR) - 1ull))
-                        held.push_back(g);
-                add_group_run_tiles(btiles[sh], (uint32_t)bdescs.size(), c.B, step, held, NR, copies);
-                bdescs.push_back(b);
+                sn.assign(idx, idx + c.k);  // the entries' blocks: the basis, normalised, then the caller's
+                sn.insert(sn.end(), a.sharenums + c.slot0 + c.k, a.sharenums + c.slot0 + c.n);
+                add_bs_row_chunk<Op>(bsr, bs_of[(size_t)i], bs_lanes, c, r, sn.data(), &soff[r.slot0], &savail[r.slot0],
+                                     c.nt ? a.target_nums + c.tgt0 : nullptr, recover);
                 continue;
             }
             // (a chunk with no row and nothing to copy has no work)
@@ -2344,15 +2253,14 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             sp.off_srow = img.put(srow.data(), srow.size() * 4);
             sp.off_mrow = img.put(mrow.data(), mrow.size() * 4);
         }
-        if (!bdescs.empty() || !rdescs.empty()) {
-            const std::vector<sec::Tile> bt = flatten_keyed(btiles, sp.cbs);
-            sp.off_bdesc = rdescs.empty() ? img.put(bdescs.data(), bdescs.size() * sizeof(sec::CbsDesc))
-                                          : img.put(rdescs.data(), rdescs.size() * sizeof(sec::RbsDesc));
-            sp.off_btmap = img.put(btmap.data(), btmap.size() * 4);
-            sp.off_btiles = img.put(bt.data(), bt.size() * sizeof(sec::Tile));
-            sp.off_bsoff = img.put(bsoff.data(), bsoff.size() * 8);
-            sp.off_bsavail = img.put(bsavail.data(), bsavail.size() * 4);
-            sp.off_brmap = img.put(brmap.data(), brmap.size() * 4);
+        if (!bsr.descs.empty()) {
+            const std::vector<sec::Tile> bt = flatten_keyed(bsr.tiles, sp.bs_rows);
+            sp.off_bs_desc = img.put(bsr.descs.data(), bsr.descs.size() * sizeof(typename Op::BsDesc));
+            sp.off_bs_tmap = img.put(bsr.tmap.data(), bsr.tmap.size() * 4);
+            sp.off_bs_tiles = img.put(bt.data(), bt.size() * sizeof(sec::Tile));
+            sp.off_bs_soff = img.put(bsr.soff.data(), bsr.soff.size() * 8);
+            sp.off_bs_avail = img.put(bsr.savail.data(), bsr.savail.size() * 4);
+            sp.off_bs_rmap = img.put(bsr.rmap.data(), bsr.rmap.size() * 4);
         }
         if (Op::kTargets) {
             sp.nmsgs = (uint32_t)msgs.size();
@@ -2390,33 +2298,19 @@ int launch_row_sub(sec_ctx *ctx, const SubPlan &sp, bool host, const uint8_t *bl
     const uint32_t *tabs = st.tabs.buf.as<uint32_t>();
     uint32_t *flags = st.flags.as<uint32_t>();
     const typename Op::Slots sl = Op::slots(plan.meta, sp, flags);
-    const bool work = !sp.groups.empty() || sp.ntail || !sp.sha_runs.empty() || !sp.cbs.empty();
+    const bool work = !sp.groups.empty() || sp.ntail || !sp.sha_runs.empty() || !sp.bs_rows.empty();
     const bool timed = Op::kChecks ? work : !host;
     hipEvent_t t0 = nullptr;
     if (timed)
         RC(timing_begin(ctx, &t0, s));
-    // the chunks of the bit-sliced check, one launch per shape, into the same flag words
-    // (an operation with targets: the chunks of the bit-sliced repair, stored rows and flag words)
-    for (const auto &b : sp.cbs) {
-        if (Op::kTargets) {
-            const sec::RbsSlots rsl{plan.meta.as<uint64_t>(sp.off_bsoff), plan.meta.as<uint32_t>(sp.off_bsavail),
-                                    plan.meta.as<uint32_t>(sp.off_brmap), plan.meta.as<uint32_t>(sp.off_btmap),
-                                    plan.meta.as<uint64_t>(sp.off_toff), flags};
-            int e = sec_launch_repair_bs(b.first, ctx->opt.lanes(O_BS_LANES), blocks, out,
-                                         plan.meta.as<sec::RbsDesc>(sp.off_bdesc),
-                                         plan.meta.as<sec::Tile>(sp.off_btiles) + b.second.first, b.second.second, rsl,
-                                         s);
-            if (e)
-                return hip_fail((hipError_t)e, "sec_repair_bs_kernel");
-            continue;
-        }
-        const sec::CbsSlots bsl{plan.meta.as<uint64_t>(sp.off_bsoff), plan.meta.as<uint32_t>(sp.off_bsavail),
-                                plan.meta.as<uint32_t>(sp.off_brmap), flags};
-        int e = sec_launch_check_bs(b.first, ctx->opt.lanes(O_BS_LANES), blocks, out,
-                                    plan.meta.as<sec::CbsDesc>(sp.off_bdesc),
-                                    plan.meta.as<sec::Tile>(sp.off_btiles) + b.second.first, b.second.second, bsl, s);
+    // the chunks of the operation's bit-sliced kernel, one launch per shape, into the same flag words
+    const auto *bd = plan.meta.as<typename Op::BsDesc>(sp.off_bs_desc);
+    const sec::Tile *bt = plan.meta.as<sec::Tile>(sp.off_bs_tiles);
+    for (const auto &b : sp.bs_rows) {
+        int e = Op::kBsLaunch(b.first, ctx->opt.lanes(O_BS_LANES), blocks, out, bd, bt + b.second.first, b.second.second,
+                              Op::bs_slots(plan.meta, sp, flags), s);
         if (e)
-            return hip_fail((hipError_t)e, "sec_check_bs_kernel");
+            return hip_fail((hipError_t)e, Op::kBsKernel);
     }
     for (const Group &g : sp.groups) {
         int e = sec_launch_rows(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
@@ -2632,12 +2526,12 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
         plan.valid = true;
     }
     if (Op::kChecks && !Op::kTargets) {  // sec_ctx_check_methods
-        ctx->chk_bs_chunks += plan.nsyn;
-        ctx->chk_direct_chunks += plan.ndirect;
+        ctx->chk_bs_chunks += plan.nrow_bs;
+        ctx->chk_direct_chunks += plan.nrow_direct;
     }
     if (Op::kTargets) {  // sec_ctx_repair_methods: the chunks with a target
-        ctx->rep_bs_chunks += plan.nsyn;
-        ctx->rep_direct_chunks += plan.ndirect;
+        ctx->rep_bs_chunks += plan.nrow_bs;
+        ctx->rep_direct_chunks += plan.nrow_direct;
     }
     if (Op::kChecks) {
         // every call starts from clean flag words (0xFFFFFFFF: no position yet, row agrees), whatever
@@ -4478,7 +4372,7 @@ int sec_check_method(int k, int m, const int32_t *sharenums, int n, uint64_t B, 
     RC(check_blocks(k, m, sharenums, n, nullptr, 0, false));
     if (B >= (1ull << 31))
         return SEC_ESIZE;
-    *method = check_bs_shape(k, m, sharenums, n, B, block_avail, (uint64_t)padlen) >= 0 ? 1 : 0;
+    *method = sec::check_bs_shape(sec_bs_shape(k, m), k, sharenums, n, B, block_avail, (uint64_t)padlen) >= 0 ? 1 : 0;
     return SEC_OK;
 }
 
@@ -4490,7 +4384,7 @@ int sec_repair_method(int k, int m, const int32_t *sharenums, int n, const int32
     RC(check_blocks(k, m, sharenums, n, targets, ntargets, false));
     if (B >= (1ull << 31))
         return SEC_ESIZE;
-    *method = repair_bs_shape(k, m, sharenums, n, ntargets, B, block_avail) >= 0 ? 1 : 0;
+    *method = sec::repair_bs_shape(sec_bs_shape(k, m), k, sharenums, n, ntargets, B, block_avail) >= 0 ? 1 : 0;
     return SEC_OK;
 }
 

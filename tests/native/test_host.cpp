@@ -1,6 +1,7 @@
 // Host-side unit test of libstorbec's C++ helpers (no HIP): GF matrices, the staging copy
-// pool, and the task pool + SHA-1 of sec_encode_pieces.  Built by tests/test_native_host.py
-// with g++ under AddressSanitizer + UBSan and, separately, ThreadSanitizer (the pools' threads).
+// pool, the task pool + SHA-1 of sec_encode_pieces, and the bit-sliced kernels' host planning
+// (bs_plan.hpp).  Built by tests/test_native_host.py with g++ under AddressSanitizer + UBSan and,
+// separately, ThreadSanitizer (the pools' threads).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -11,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "bs_plan.hpp"
 #include "gf_host.hpp"
 #include "task_pool.hpp"
 
@@ -151,12 +153,104 @@ static void test_task_pool_sha1()
     EXPECT(ran.load() == 20);
 }
 
+// bs_plan.hpp: the host planning of the bit-sliced check, repair and syndrome decode
+static void test_bs_plan()
+{
+    // layout: k = 4, m = 7; the basis holds blocks {2, 0, 3, 1}, check rows {6, 4}; block 3 is short
+    {
+        const int k = 4, m = 7, sn[6] = {2, 0, 3, 1, 6, 4};
+        const uint64_t eoff[6] = {1200, 1000, 1300, 1100, 1600, 1400};  // block b at 1000 + 100 b
+        const uint32_t eavail[6] = {64, 64, 17, 64, 64, 64};
+        std::vector<uint64_t> off;
+        std::vector<uint32_t> avail, rmap;
+        for (uint32_t chunk = 0; chunk < 2; ++chunk) {  // the second appended after the first
+            const sec::BsLayout l = sec::bs_layout(k, m, sn, eoff, eavail, 6, k, off, avail, &rmap);
+            EXPECT(l.slot0 == chunk * 7 && l.rmap0 == chunk * 3);
+            EXPECT(off.size() == (chunk + 1) * 7 && avail.size() == off.size() && rmap.size() == (chunk + 1) * 3);
+            EXPECT(l.dmask == 0xF && l.pmask == 0b101);
+            for (int e = 0; e < 6; ++e) {
+                EXPECT(off[l.slot0 + sn[e]] == 1000 + 100 * (uint64_t)sn[e]);
+                EXPECT(avail[l.slot0 + sn[e]] == (sn[e] == 3 ? 17u : 64u));
+            }
+            EXPECT(off[l.slot0 + 5] == 0 && avail[l.slot0 + 5] == 0);  // parity row 1 is not held
+            EXPECT(rmap[l.rmap0 + 2] == 0 && rmap[l.rmap0 + 0] == 1 && rmap[l.rmap0 + 1] == 0);
+        }
+        // a decode's basis that holds parity (normalised): no check rows, no rmap
+        const int idx[4] = {0, 5, 2, 4};
+        const sec::BsLayout l = sec::bs_layout(k, m, idx, eoff, eavail, k, k, off, avail);
+        EXPECT(l.slot0 == 14 && off.size() == 21 && rmap.size() == 6);
+        EXPECT(l.dmask == 0b0101 && l.pmask == 0b011);
+        EXPECT(off[14 + 0] == 1200 && off[14 + 5] == 1000 && off[14 + 2] == 1300 && off[14 + 4] == 1100);
+        EXPECT(avail[14 + 2] == 17 && avail[14 + 4] == 64);
+        for (int j : {1, 3, 6})  // neither held: untouched
+            EXPECT(off[14 + j] == 0 && avail[14 + j] == 0);
+    }
+    // touched_groups (no shape has 64-row groups: that shift is pinned here, under UBSan)
+    using G = std::vector<int>;
+    EXPECT(sec::touched_groups(1, 32, 16) == G({0}));
+    EXPECT(sec::touched_groups(1ull << 16, 32, 16) == G({1}));
+    EXPECT(sec::touched_groups(1 | 1ull << 31, 32, 16) == G({0, 1}));
+    EXPECT(sec::touched_groups(0, 32, 16) == G());
+    EXPECT(sec::touched_groups(0b1000, 4, 4) == G({0}));
+    EXPECT(sec::touched_groups(~0ull, 64, 64) == G({0}));
+    // add_group_run_tiles: runs of 8 tiles of each group, then the ragged last span of each
+    for (bool copy_first : {true, false}) {
+        std::vector<sec::Tile> t;
+        sec::add_group_run_tiles(t, 5, 8 * 2048 + 1, 2048, {0, 1}, 16, copy_first);
+        EXPECT(t.size() == 18);
+        for (size_t i = 0; i < t.size(); ++i) {
+            const uint32_t g = i < 16 ? (uint32_t)i / 8 : (uint32_t)i - 16;
+            EXPECT(t[i].chunk == 5 && t[i].r0 == 16 * g);
+            EXPECT(t[i].t0 == (i < 16 ? (i % 8) * 2048 : 16384));
+            EXPECT(t[i].ntail == (copy_first && g == 0 ? 1u : 0u));
+        }
+    }
+    // eligibility: the basis is the chunk's k data blocks
+    {
+        const int k = 4;
+        const int32_t sn[6] = {2, 0, 3, 1, 6, 4}, par[6] = {2, 0, 4, 1, 6, 3};
+        const uint64_t B = 16, full[6] = {16, 16, 16, 16, 16, 16}, last_short[6] = {16, 16, 5, 16, 16, 16},
+                       data_short[6] = {16, 15, 16, 16, 16, 16}, parity_short[6] = {16, 16, 16, 16, 15, 16};
+        EXPECT(sec::bs_data_basis_shape(0, k, sn, 6, B, nullptr) == 0);
+        EXPECT(sec::bs_data_basis_shape(0, k, sn, 6, B, full) == 0);
+        EXPECT(sec::bs_data_basis_shape(0, k, sn, 6, B, last_short) == 0);  // only block k-1 short
+        EXPECT(sec::bs_data_basis_shape(-1, k, sn, 6, B, full) == -1);
+        EXPECT(sec::bs_data_basis_shape(0, k, sn, 6, 15, nullptr) == -1);
+        EXPECT(sec::bs_data_basis_shape(0, k, sn, 6, sec::kBsMaxB, nullptr) == 0);
+        EXPECT(sec::bs_data_basis_shape(0, k, sn, 6, sec::kBsMaxB + 1, nullptr) == -1);
+        EXPECT(sec::bs_data_basis_shape(0, k, par, 6, B, full) == -1);  // a basis entry >= k
+        EXPECT(sec::bs_data_basis_shape(0, k, sn, 6, B, data_short) == -1);
+        EXPECT(sec::bs_data_basis_shape(0, k, sn, 6, B, parity_short) == -1);
+        // the check's own conditions: a check row, padlen < B
+        EXPECT(sec::check_bs_shape(0, k, sn, 6, B, last_short, 3) == 0);
+        EXPECT(sec::check_bs_shape(-1, k, sn, 6, B, full, 3) == -1);
+        EXPECT(sec::check_bs_shape(0, k, sn, 6, 15, nullptr, 3) == -1);
+        EXPECT(sec::check_bs_shape(0, k, par, 6, B, full, 3) == -1);
+        EXPECT(sec::check_bs_shape(0, k, sn, 6, B, data_short, 3) == -1);
+        EXPECT(sec::check_bs_shape(0, k, sn, 6, B, parity_short, 3) == -1);
+        EXPECT(sec::check_bs_shape(0, k, sn, k, B, full, 3) == -1);
+        EXPECT(sec::check_bs_shape(0, k, sn, 6, B, full, B) == -1);
+        EXPECT(sec::check_bs_shape(0, k, sn, 6, B, full, B - 1) == 0);
+        // the repair's: a target or a check row
+        EXPECT(sec::repair_bs_shape(0, k, sn, k, 0, B, full) == -1);
+        EXPECT(sec::repair_bs_shape(0, k, sn, k, 1, B, full) == 0);
+        EXPECT(sec::repair_bs_shape(0, k, sn, k + 1, 0, B, full) == 0);
+        EXPECT(sec::repair_bs_shape(0, k, sn, k, 1, B, last_short) == 0);
+        EXPECT(sec::repair_bs_shape(-1, k, sn, k, 1, B, full) == -1);
+        EXPECT(sec::repair_bs_shape(0, k, sn, k, 1, 15, nullptr) == -1);
+        EXPECT(sec::repair_bs_shape(0, k, par, k, 1, B, full) == -1);
+        EXPECT(sec::repair_bs_shape(0, k, sn, 6, 1, B, data_short) == -1);
+        EXPECT(sec::repair_bs_shape(0, k, sn, 6, 1, B, parity_short) == -1);
+    }
+}
+
 int main()
 {
     test_matrices();
     test_copy_pool();
     test_shared_pool_concurrent();
     test_task_pool_sha1();
+    test_bs_plan();
     if (fails)
         return 1;
     printf("native host tests ok\n");
