@@ -965,6 +965,16 @@ def check_decode_check_item(k: int, m: int, blocks, sharenums, padlen: int) -> N
         raise Error(_lib.strerror(_lib.SEC_EPADLEN))
 
 
+def check_decode_ids_item(k: int, m: int, blocks, sharenums, padlen: int, ids) -> None:
+    """The id-checked decode's preconditions for one chunk (``piece.decode_chunks_id_checked``):
+    check_decode_check_item's, in its order (Error), then one 20-byte id per block (ValueError)."""
+    check_decode_check_item(k, m, blocks, sharenums, padlen)
+    if len(ids) != len(blocks):
+        raise ValueError("one recorded id per block")
+    if any(len(x) != 20 for x in ids):
+        raise ValueError("a piece id is 20 bytes")
+
+
 def check_repair_check_item(k: int, m: int, blocks, sharenums, targets) -> None:
     """The repair + check preconditions for one chunk (the library's own checks, raised before any
     GPU work): n equal-length blocks and n sharenums, 1 <= k <= m <= 256, k <= n <= m, sharenums

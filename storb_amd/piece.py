@@ -66,8 +66,8 @@ from pydantic import BaseModel, ConfigDict, Field
 
 from .constants import MAX_PIECE_SIZE, MIN_PIECE_SIZE, PIECE_LENGTH_OFFSET, PIECE_LENGTH_SCALING
 from .easyfec import Decoder, Encoder, Error
-from .engine import (EngineGroup, check_decode_check_item, check_decode_item, check_locate, check_repair_check_item,
-                     choose_blocks, device_count, get_engine, spread_threads)
+from .engine import (EngineGroup, check_decode_check_item, check_decode_ids_item, check_decode_item, check_locate,
+                     check_repair_check_item, choose_blocks, device_count, get_engine, spread_threads)
 
 logger = logging.getLogger(__name__)
 
@@ -78,7 +78,8 @@ __all__ = [
     "encode_chunks_stream", "Encoder",
     "Decoder", "Error", "use_devices", "repair_chunks", "repair_pieces", "ChunkCheck", "check_chunks", "check_pieces",
     "decode_chunks_checked", "reconstruct_data_checked", "PieceCheckError", "repair_chunks_checked",
-    "repair_pieces_checked",
+    "repair_pieces_checked", "ChunkIdCheck", "PieceIdError",
+    "decode_chunks_id_checked", "reconstruct_data_id_checked", "reconstruct_data_stream_id_checked",
 ]
 
 PREFETCH_PIECE_IDS = True  # encode_chunk hashes its pieces on a thread pool (see module doc)
@@ -1211,6 +1212,197 @@ def reconstruct_data_stream_checked(pieces: list[Piece], chunks: list[EncodedChu
             if not (ck.consistent or ck.located):
                 raise PieceCheckError(
                     f"Held pieces disagree and no corrupt piece could be named in chunk {ck.chunk_idx}", list(seen))
+            yield data, ck
+        if err is not None:
+            raise err
+
+
+class ChunkIdCheck(BaseModel):
+    """What ``decode_chunks_id_checked`` found for one chunk."""
+
+    chunk_idx: int
+    checked: int  # pieces hashed (the distinct pieces held)
+    ok: bool  # every held piece matches its recorded id
+    bad_piece_idx: list[int] = Field(default_factory=list)  # the pieces whose SHA-1 is not their id
+    decodable: bool = True  # at least k held pieces match: the chunk's bytes come from such pieces only
+
+
+class PieceIdError(ValueError):
+    """``reconstruct_data_id_checked``: fewer than k of some chunk's held pieces match their recorded
+    ids, so its bytes cannot be trusted.  ``checks``: every chunk's ``ChunkIdCheck``."""
+
+    def __init__(self, message: str, checks: list[ChunkIdCheck]):
+        super().__init__(message)
+        self.checks = checks
+
+
+# Who hashes the held pieces of an id-checked download: the library's SHA-1 kernel in one staged call
+# (``Engine.sha1_host``: one lane per piece, so a call costs about one piece's chain, 7-9 ms for a
+# 512 KiB piece, whatever the number of pieces), or ``hashlib`` on the hashing thread pool.  The
+# kernel is taken for calls (stream windows) of at least ID_CHECK_GPU_MIN_PIECES pieces of at most
+# ID_CHECK_GPU_MAX_PIECE_BYTES each.  Not measured on the download; the upload's measurements
+# (GPU_PIECE_IDS, GPU_PARITY_IDS above) ended on the host for every id, so the default is the
+# thread pool everywhere, and the kernel stays behind _ids_on_gpu, tested.
+ID_CHECK_GPU_MIN_PIECES: int | None = None  # None: never
+ID_CHECK_GPU_MAX_PIECE_BYTES = 1 << 62
+
+
+def _ids_on_gpu(npieces: int, piece_bytes: int) -> bool:
+    """Whether an id-checked call over `npieces` pieces, the largest of `piece_bytes`, hashes them
+    with the SHA-1 kernel (else on the hashing thread pool)."""
+    return (ID_CHECK_GPU_MIN_PIECES is not None and npieces >= ID_CHECK_GPU_MIN_PIECES
+            and piece_bytes <= ID_CHECK_GPU_MAX_PIECE_BYTES)
+
+
+def _recorded_id(ids, ch: EncodedChunk, piece_idx: int) -> bytes:
+    """The id recorded for piece `piece_idx` of chunk ch, 20 bytes, from its 40-hex or 20-byte form."""
+    try:
+        v = ids[piece_idx]
+    except (IndexError, KeyError, TypeError):
+        v = None
+    if v is None:
+        raise ValueError(f"No recorded id for piece {piece_idx} of chunk {ch.chunk_idx}")
+    v = bytes.fromhex(v) if isinstance(v, str) else bytes(v)
+    if len(v) != 20:
+        raise ValueError(f"The id of piece {piece_idx} of chunk {ch.chunk_idx} is not a SHA-1 digest")
+    return v
+
+
+def decode_chunks_id_checked(encoded_chunks: typing.Sequence[EncodedChunk],
+                             piece_ids: typing.Sequence) -> tuple[bytes, list[ChunkIdCheck]]:
+    """``decode_chunks`` with the reference's own integrity step before it: every held piece is
+    hashed and compared with the id recorded for it at upload (validator.py:1556-1604 hashes each
+    piece it receives and drops one whose SHA-1 is not its id, piece.py:54-68), and each chunk is
+    reassembled from pieces that passed.
+
+    ``piece_ids[c]`` holds the ids recorded for ``encoded_chunks[c]``, indexed by ``piece_idx``
+    (what ``ChunkDHTValue.piece_hashes`` holds: 40-hex strings, or 20-byte values); only the held
+    pieces' entries are read, and a held piece without one is a ``ValueError``.  Every distinct
+    piece held of a chunk is hashed, all chunks' pieces in ONE batch (``_ids_on_gpu`` picks who
+    hashes: the SHA-1 kernel in one ``sha1_host`` call, or ``hashlib`` on the hashing thread
+    pool); then every chunk is decoded in ONE ``decode_host`` call from k of its good pieces
+    (``choose_blocks``' pick among them), or, where fewer than k are good, from the first k held.
+
+    A chunk's bytes are trustworthy exactly when its ``ChunkIdCheck`` is ``decodable``: then they
+    come from pieces whose SHA-1 is the recorded id, whatever the other pieces hold and however
+    many miners act together (which the code-word check of ``decode_chunks_checked`` cannot say,
+    and it cannot check a chunk with exactly k pieces at all).  Otherwise they are what its first
+    k pieces decode to.  The pieces are read twice (hashed, then decoded from); a fused native
+    call is not built.  One device; the streaming form is ``reconstruct_data_stream_id_checked``."""
+    chunks = list(encoded_chunks)
+    if len(piece_ids) != len(chunks):
+        raise ValueError("decode_chunks_id_checked: one list of recorded ids per chunk")
+    held, want = [], []
+    for ch, ids in zip(chunks, piece_ids):
+        use = _held_pieces(ch, "reconstruct")
+        held.append(use)
+        want.append([_recorded_id(ids, ch, p.piece_idx) for p in use])
+    if not chunks:
+        return b"", []
+    for ch, use, ids in zip(chunks, held, want):  # every chunk's preconditions before any hashing
+        check_decode_ids_item(ch.k, ch.m, [p.data for p in use], [p.piece_idx for p in use], ch.padlen, ids)
+    flat = [p.data for use in held for p in use]
+    if _ids_on_gpu(len(flat), max(len(d) for d in flat)):
+        got = iter(get_engine().sha1_host(flat))
+    else:
+        got = iter(_pool("hash").map(lambda d: hashlib.sha1(d).digest(), flat))
+    out, items = [], []
+    for ch, use, ids in zip(chunks, held, want):
+        bad = [p.piece_idx for p, w in zip(use, ids) if next(got) != w]
+        good = [p for p in use if p.piece_idx not in bad]
+        ck = ChunkIdCheck(chunk_idx=ch.chunk_idx, checked=len(use), ok=not bad, bad_piece_idx=bad,
+                          decodable=len(good) >= ch.k)
+        out.append(ck)
+        k, m, blocks, sharenums = _check_item(ch, good if ck.decodable else use)
+        items.append((k, m, blocks[:k], sharenums[:k], ch.padlen))
+    return get_engine().decode_host(items), out
+
+
+def _group_pieces(pieces: list[Piece], chunks: list[EncodedChunk]) -> None:
+    """``reconstruct_data``'s grouping: each chunk gets its pieces in ascending piece_idx, or the
+    reference's ValueError."""
+    by_chunk: dict[int, list[Piece]] = {}
+    for p in pieces:
+        by_chunk.setdefault(p.chunk_idx, []).append(p)
+    for chunk in chunks:
+        relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
+        if len(relevant) < chunk.k:
+            raise ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
+        chunk.pieces = relevant
+
+
+def reconstruct_data_id_checked(pieces: list[Piece], chunks: list[EncodedChunk],
+                                piece_ids: typing.Sequence) -> tuple[bytes, list[ChunkIdCheck]]:
+    """``reconstruct_data`` with every piece handed over checked against its recorded id in the same
+    pass (``decode_chunks_id_checked``, grouped as ``reconstruct_data`` groups them; ``piece_ids[c]``
+    belongs to ``chunks[c]``).  Raises ``ValueError("Not enough pieces to reconstruct chunk N")`` as
+    ``reconstruct_data`` does, before any decode, and ``PieceIdError`` (carrying ``.checks``) when
+    some chunk is not ``decodable``; otherwise returns the bytes, all from pieces that match their
+    ids, and the checks."""
+    _group_pieces(pieces, chunks)
+    data, checks = decode_chunks_id_checked(chunks, piece_ids)
+    bad = [ck.chunk_idx for ck in checks if not ck.decodable]
+    if bad:
+        raise PieceIdError(f"Fewer than k held pieces match their recorded ids in chunk(s) {bad}", checks)
+    return data, checks
+
+
+def _decode_id_checked_window(window: list, by_chunk: dict):
+    """Worker side of reconstruct_data_stream_id_checked: (per-chunk ``(bytes, ChunkIdCheck)``, error)
+    for one window of ``(chunk, ids)`` pairs.  The window's chunks up to the first one without
+    enough pieces go through one ``decode_chunks_id_checked``; that chunk's error is returned, to be
+    raised in order."""
+    good, ids, err = [], [], None
+    for chunk, cid in window:
+        relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
+        if len(relevant) < chunk.k:
+            err = ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
+            break
+        chunk.pieces = relevant
+        good.append(chunk)
+        ids.append(cid)
+    if not good:
+        return [], err
+    try:
+        data, checks = decode_chunks_id_checked(good, ids)
+    except Exception as e:  # noqa: BLE001 - a precondition or device failure: nothing of the window is trusted
+        return [], e
+    view, at, pairs = memoryview(data), 0, []
+    for chunk, ck in zip(good, checks):
+        n = chunk.k * len(chunk.pieces[0].data) - chunk.padlen
+        pairs.append((bytes(view[at:at + n]), ck))
+        at += n
+    return pairs, err
+
+
+def reconstruct_data_stream_id_checked(pieces: list[Piece], chunks: list[EncodedChunk], piece_ids: typing.Sequence, *,
+                                       window_bytes: int | None = None) -> Iterator[tuple[bytes, ChunkIdCheck]]:
+    """``reconstruct_data_id_checked``'s contract, delivered as ``reconstruct_data_stream`` delivers:
+    yield ``(bytes, ChunkIdCheck)`` chunk by chunk, in order.
+
+    Chunks go in windows of about `window_bytes` (default STREAM_WINDOW_BYTES) of output.  Each
+    window is one ``decode_chunks_id_checked`` on the stream worker (every piece handed over hashed
+    in one batch, then one decode from good pieces; ``_ids_on_gpu`` picks who hashes, per window),
+    and window w+1 runs while the caller consumes window w.  A yielded chunk is ``decodable``.  Errors are raised when the stream
+    reaches the chunk, after every earlier chunk has been yielded: ``ValueError("Not enough pieces
+    to reconstruct chunk N")``, a ``ValueError`` for a held piece without a recorded id, and
+    ``PieceIdError`` (``.checks``: the checks of the chunks seen so far, that chunk's last).
+    Closing the generator early cancels the windows not yet started.  One device: ``devices=`` is
+    not provided, as for the whole check family."""
+    if len(piece_ids) != len(chunks):
+        raise ValueError("reconstruct_data_stream_id_checked: one list of recorded ids per chunk")
+    by_chunk: dict[int, list[Piece]] = {}
+    for p in pieces:
+        by_chunk.setdefault(p.chunk_idx, []).append(p)
+    wb = STREAM_WINDOW_BYTES if window_bytes is None else window_bytes
+    wins = _windows(list(zip(chunks, piece_ids)), wb, lambda pr: max(pr[0].original_chunk_size, 1))
+    seen: list[ChunkIdCheck] = []
+    for pairs, err in _pipeline(wins, _decode_id_checked_window, (by_chunk,), None):
+        for data, ck in pairs:
+            seen.append(ck)
+            if not ck.decodable:
+                raise PieceIdError(f"Fewer than k held pieces match their recorded ids in chunk {ck.chunk_idx}",
+                                   list(seen))
             yield data, ck
         if err is not None:
             raise err
