@@ -609,18 +609,7 @@ void add_bs_work(const Options &o, Bins &bins, uint32_t chunk, uint64_t B, int s
 
 bool use_xcd_order(bool, const Group &g) { return g.mfma < 3 && SEC_XCD_ORDER == 1; }
 
-void xcd_order(std::vector<sec::Tile> &t)
-{
-    const size_t n = t.size(), q = n / 8, r = n % 8;
-    if (n < 16)
-        return;
-    std::vector<sec::Tile> o(n);
-    for (size_t b = 0; b < n; ++b) {
-        const size_t x = b % 8;
-        o[b] = t[x * q + std::min(x, r) + b / 8];
-    }
-    t.swap(o);
-}
+using sec::xcd_order;  // bs_plan.hpp
 
 void flatten(const Bins &bins, std::vector<Group> &groups, std::vector<sec::Tile> &tiles, bool decode)
 {

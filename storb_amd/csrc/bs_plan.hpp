@@ -67,6 +67,23 @@ inline void add_group_run_tiles(std::vector<Tile> &tiles, uint32_t desc_index, u
                                      copy_first && g == groups[0] ? 1u : 0u});
 }
 
+// XCD order of one launch's tiles (api.cpp says where it applies and what it measured): workgroup b
+// runs on XCD b % 8, so entry b becomes the next tile of the contiguous eighth that belongs to
+// XCD b % 8, eighth x starting at x * (n / 8) + min(x, n % 8): the first n % 8 eighths hold one
+// tile more.  A permutation for any n; lists of fewer than 16 tiles keep their order.
+inline void xcd_order(std::vector<Tile> &t)
+{
+    const size_t n = t.size(), q = n / 8, r = n % 8;
+    if (n < 16)
+        return;
+    std::vector<Tile> o(n);
+    for (size_t b = 0; b < n; ++b) {
+        const size_t x = b % 8;
+        o[b] = t[x * q + std::min(x, r) + b / 8];
+    }
+    t.swap(o);
+}
+
 // Chunks whose basis is their k data blocks, so that every other row, held or wanted, is one of
 // zfec's own parity rows, which the bit-sliced kernels hold: `shape` (the (k, m)'s, sec_bs_shape) when
 //   * it is one and 16 <= B (below it the tail kernel) <= kBsMaxB;

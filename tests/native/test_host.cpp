@@ -244,8 +244,57 @@ static void test_bs_plan()
     }
 }
 
+// bs_plan.hpp xcd_order: a permutation for every count (n % 8 != 0 included), the identity below 16
+// tiles; entry b is a tile of the contiguous eighth of XCD b % 8 (the first n % 8 eighths one tile
+// longer, their bounds summed up here, not taken from the function's formula), and each eighth is
+// walked upwards without a gap.
+static void test_xcd_order()
+{
+    std::vector<size_t> counts;
+    for (size_t n = 0; n <= 4200; ++n)
+        counts.push_back(n);
+    for (size_t n : {2048, 2022, 1540, 65536 + 5})
+        counts.push_back(n);
+    for (size_t n : counts) {
+        std::vector<sec::Tile> t(n);
+        for (size_t i = 0; i < n; ++i)
+            t[i] = sec::Tile{(uint32_t)(i * 7 + 3), (uint32_t)i, (uint32_t)(i % 5), (uint32_t)(i % 3)};
+        const std::vector<sec::Tile> in = t;
+        sec::xcd_order(t);
+        bool ok = t.size() == n;
+        size_t lo[9] = {0};
+        for (size_t x = 0; x < 8; ++x)
+            lo[x + 1] = lo[x] + n / 8 + (x < n % 8 ? 1 : 0);
+        ok = ok && lo[8] == n;
+        std::vector<uint8_t> seen(n, 0);
+        size_t next[8];
+        for (size_t x = 0; x < 8; ++x)
+            next[x] = lo[x];
+        for (size_t b = 0; ok && b < n; ++b) {
+            const size_t i = t[b].t0, x = b % 8;
+            ok = i < n && !seen[i] && memcmp(&t[b], &in[i], sizeof(sec::Tile)) == 0;  // a whole input tile, once
+            if (!ok)
+                break;
+            seen[i] = 1;
+            if (n < 16) {
+                ok = i == b;
+            } else {
+                ok = lo[x] <= i && i < lo[x + 1] && i == next[x];  // its XCD's eighth, ascending
+                ++next[x];
+            }
+        }
+        for (size_t x = 0; ok && n >= 16 && x < 8; ++x)
+            ok = next[x] == lo[x + 1];
+        if (!ok) {
+            fprintf(stderr, "FAIL xcd_order: n = %zu\n", n);
+            ++fails;
+        }
+    }
+}
+
 int main()
 {
+    test_xcd_order();
     test_matrices();
     test_copy_pool();
     test_shared_pool_concurrent();
