@@ -611,6 +611,13 @@ bool use_xcd_order(bool, const Group &g) { return g.mfma < 3 && SEC_XCD_ORDER ==
 
 using sec::xcd_order;  // bs_plan.hpp
 
+// Placement.  Whatever tile workgroup b runs, its 16-byte map entry is stored XCD-major inside the
+// launch's own sub-array, at sec::tile_slot(b, count) (kernels.hpp; sec::append_placed), where
+// sec::own_tile reads it: the entries of the workgroups b % 8 == x are one contiguous run.  In
+// launch order the 8 entries of a 128-byte line went to 8 XCDs and every XCD's L2 fetched the whole
+// map to use an eighth of it (C2 encode: 8 x 4 MiB read per launch, profiles/pmc_c2_parent.json).
+// Order and placement compose: xcd_order decides which tile workgroup b runs, placement where that
+// entry lies.  Results depend on tile_slot being a bijection only, not on where workgroups run.
 void flatten(const Bins &bins, std::vector<Group> &groups, std::vector<sec::Tile> &tiles, bool decode)
 {
     groups.clear();
@@ -618,25 +625,27 @@ void flatten(const Bins &bins, std::vector<Group> &groups, std::vector<sec::Tile
         if (kv.second.empty())
             continue;
         const size_t first = tiles.size();
-        tiles.insert(tiles.end(), kv.second.begin(), kv.second.end());
         groups.push_back(Group{std::get<1>(kv.first), std::get<2>(kv.first), std::get<3>(kv.first),
-                               std::get<4>(kv.first), (uint32_t)first, (uint32_t)(tiles.size() - first),
+                               std::get<4>(kv.first), (uint32_t)first, (uint32_t)kv.second.size(),
                                std::get<0>(kv.first)});
         if (use_xcd_order(decode, groups.back()) || (std::get<2>(kv.first) == kBsPair && std::get<4>(kv.first))) {
-            std::vector<sec::Tile> g(tiles.begin() + first, tiles.end());
+            std::vector<sec::Tile> g(kv.second);
             xcd_order(g);
-            std::copy(g.begin(), g.end(), tiles.begin() + first);
+            sec::append_placed(tiles, g);
+        } else {
+            sec::append_placed(tiles, kv.second);
         }
     }
 }
 
-// The tiles of every key, in key order, as one array; `launches` gets (key, (first, count)) in it.
+// The tiles of every key, in key order, as one array, each key's launch placed on its own (see
+// flatten); `launches` gets (key, (first, count)) in it.
 std::vector<sec::Tile> flatten_keyed(const std::map<int, std::vector<sec::Tile>> &by_key, KeyedLaunches &launches)
 {
     std::vector<sec::Tile> tiles;
     for (auto &kv : by_key) {
         launches.push_back({kv.first, {(uint32_t)tiles.size(), (uint32_t)kv.second.size()}});
-        tiles.insert(tiles.end(), kv.second.begin(), kv.second.end());
+        sec::append_placed(tiles, kv.second);
     }
     return tiles;
 }

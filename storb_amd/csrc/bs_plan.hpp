@@ -73,15 +73,26 @@ inline void add_group_run_tiles(std::vector<Tile> &tiles, uint32_t desc_index, u
 // tile more.  A permutation for any n; lists of fewer than 16 tiles keep their order.
 inline void xcd_order(std::vector<Tile> &t)
 {
-    const size_t n = t.size(), q = n / 8, r = n % 8;
+    const uint32_t n = (uint32_t)t.size();
     if (n < 16)
         return;
     std::vector<Tile> o(n);
-    for (size_t b = 0; b < n; ++b) {
-        const size_t x = b % 8;
-        o[b] = t[x * q + std::min(x, r) + b / 8];
-    }
+    for (uint32_t b = 0; b < n; ++b)
+        o[b] = t[tile_slot(b, n)];  // kernels.hpp: the same formula places the map's entries
     t.swap(o);
+}
+
+// Appends one launch's tiles, t[b] the tile workgroup b runs (in chunk order or after xcd_order),
+// where its kernel reads them: entry b at tile_slot(b, t.size()) of the launch's own sub-array
+// (kernels.hpp).  Placement is the inverse view of xcd_order's formula, so an XCD-ordered launch's
+// sub-array comes out in chunk order.
+inline void append_placed(std::vector<Tile> &tiles, const std::vector<Tile> &t)
+{
+    const size_t first = tiles.size();
+    const uint32_t n = (uint32_t)t.size();
+    tiles.resize(first + n);
+    for (uint32_t b = 0; b < n; ++b)
+        tiles[first + tile_slot(b, n)] = t[b];
 }
 
 // Chunks whose basis is their k data blocks, so that every other row, held or wanted, is one of

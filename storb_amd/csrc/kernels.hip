@@ -395,7 +395,7 @@ __global__ __launch_bounds__(sec::max_lanes(R, U)) void sec_encode_kernel(const 
                                                          const sec::Tile *__restrict__ tiles,
                                                          const u32 *__restrict__ tabs)
 {
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::EncDesc d = descs[tl.chunk];
     const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
     if (t < d.valid)
@@ -579,7 +579,7 @@ __global__ __launch_bounds__(sec::max_lanes(R, U)) void sec_decode_kernel(const 
                                                          const u32 *__restrict__ tabs,
                                                          const sec::DecSlots sl)
 {
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::DecDesc d = descs[tl.chunk];
     const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
     if (t < d.valid)
@@ -865,7 +865,7 @@ __global__ __launch_bounds__(sec::max_lanes(R, U)) void sec_repair_kernel(const 
                                                          const sec::RepSlots sl)
 {
     static_assert(R >= 1, "a repair tile has target rows: nothing is copied");
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::RepDesc d = descs[tl.chunk];
     const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
     if (t < d.valid)
@@ -1099,7 +1099,7 @@ __global__ __launch_bounds__(sec::max_lanes(R, U)) void sec_check_kernel(const u
                                                         const sec::ChkSlots sl)
 {
     static_assert(R >= 1, "a check tile has check rows");
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::ChkDesc d = descs[tl.chunk];
     const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
     if (t < d.valid)
@@ -1369,7 +1369,7 @@ __global__ __launch_bounds__(sec::max_lanes(R, U)) void sec_decode_check_kernel(
                                                                const u32 *__restrict__ tabs,
                                                                const sec::DChkSlots sl)
 {
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::DChkDesc d = descs[tl.chunk];
     const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
     if (t < d.valid)
@@ -1607,7 +1607,7 @@ __global__ __launch_bounds__(sec::max_lanes(R, U)) void sec_repair_check_kernel(
                                                                const sec::RChkSlots sl)
 {
     static_assert(R >= 1, "a repair + check tile has target or check rows: nothing is copied");
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::RChkDesc d = descs[tl.chunk];
     const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
     if (t < d.valid)

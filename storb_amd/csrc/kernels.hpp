@@ -264,6 +264,34 @@ struct Tile {
                      // positions [valid, B) it also computes byte by byte; else 0
 };
 
+// Where a launch of nt tiles keeps the map entry of workgroup b inside its own sub-array:
+// XCD-major.  Workgroups are dealt round-robin over the 8 XCDs, so in launch order the 8 entries
+// of a 128-byte line went to 8 XCDs and each XCD's L2 fetched every line of the map for one entry;
+// here the entries of the workgroups b % 8 == x form one contiguous run, run x starting at
+// x * (nt / 8) + min(x, nt % 8) (the first nt % 8 runs hold one entry more).  A bijection of
+// [0, nt) for every nt, the identity below 16; the planner (bs_plan.hpp append_placed) and the
+// kernels (own_tile) share it, so results do not depend on where a workgroup runs.
+#ifdef __HIP__
+#define SEC_HOST_DEVICE __host__ __device__
+#else
+#define SEC_HOST_DEVICE
+#endif
+SEC_HOST_DEVICE inline uint32_t tile_slot(uint32_t b, uint32_t nt)
+{
+    if (nt < 16)
+        return b;
+    const uint32_t x = b % 8, r = nt % 8;
+    return x * (nt / 8) + (x < r ? x : r) + b / 8;
+}
+
+#ifdef __HIP__
+// This workgroup's tile, of a launch of one workgroup per tile (gridDim.x tiles); scalar arithmetic
+__device__ __forceinline__ Tile own_tile(const Tile *__restrict__ tiles)
+{
+    return tiles[tile_slot(blockIdx.x, gridDim.x)];
+}
+#endif
+
 // One byte position handled by the tail kernels.
 struct TailItem {
     uint32_t chunk;

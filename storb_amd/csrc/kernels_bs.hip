@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256) void sec_encode_bs_kernel(const u8 *__restrict
                                                             const sec::EncDesc *__restrict__ descs,
                                                             const sec::Tile *__restrict__ tiles)
 {
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::EncDesc d = descs[tl.chunk];
     const u32 s = tl.t0 + (threadIdx.x >> 6) * kSpan;
     if (s >= d.B)
@@ -413,7 +413,7 @@ __global__ __launch_bounds__(128) void sec_encode_bs_pair_kernel(const u8 *__res
                                                                  const sec::Tile *__restrict__ tiles)
 {
     static_assert(M - K == 2 * NR, "two row groups");
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::EncDesc d = descs[tl.chunk];
     if (tl.t0 >= d.B)  // the whole workgroup: both waves leave before any barrier
         return;
@@ -852,7 +852,7 @@ __global__ __launch_bounds__(256) void sec_syndrome_bs_kernel(const u8 *__restri
                                                               const sec::Tile *__restrict__ tiles,
                                                               const sec::SynSlots sl)
 {
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::SynDesc d = descs[tl.chunk];
     const u32 s = tl.t0 + (threadIdx.x >> 6) * kSpan;
     if (s >= d.B)
@@ -881,7 +881,7 @@ __global__ __launch_bounds__(128) void sec_syndrome_bs_pair_kernel(
     const sec::Tile *__restrict__ tiles, const sec::SynSlots sl)
 {
     static_assert(K >= 32 && M - K == 2 * NR, "two row groups on the LDS ring");
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::SynDesc d = descs[tl.chunk];
     if (tl.t0 >= d.B)
         return;
@@ -975,7 +975,7 @@ __global__ __launch_bounds__(256) void sec_check_bs_kernel(const u8 *__restrict_
                                                            const sec::Tile *__restrict__ tiles,
                                                            const sec::CbsSlots sl)
 {
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::CbsDesc d = descs[tl.chunk];
     const u32 s = tl.t0 + (threadIdx.x >> 6) * kSpan;
     if (s >= d.B)
@@ -1071,7 +1071,7 @@ __global__ __launch_bounds__(256) void sec_repair_bs_kernel(const u8 *__restrict
                                                             const sec::Tile *__restrict__ tiles,
                                                             const sec::RbsSlots sl)
 {
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::RbsDesc d = descs[tl.chunk];
     const u32 s = tl.t0 + (threadIdx.x >> 6) * kSpan;
     if (s >= d.B)
@@ -1226,7 +1226,7 @@ __global__ __launch_bounds__(256) void sec_solve_bs_kernel(const u8 *__restrict_
                                                            const sec::Tile *__restrict__ tiles,
                                                            const uint64_t *__restrict__ masks)
 {
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::SolveDesc d = descs[tl.chunk];
     const u32 s = tl.t0 + (threadIdx.x >> 6) * kSpan;
     if (s >= d.B)
@@ -1299,7 +1299,7 @@ __global__ __launch_bounds__(64 * (K / NR)) void sec_solve_bs_lds_kernel(const u
     static_assert(K % NR == 0 && NR <= 16, "row groups");
     extern __shared__ u32x4 sy_dyn[];
     auto sy = reinterpret_cast<u32x4 (*)[2][64]>(sy_dyn);
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::SolveDesc d = descs[tl.chunk];
     const u32 s = tl.t0;
     if (s >= d.B)  // the whole workgroup (one span)
@@ -1389,7 +1389,7 @@ __global__ __launch_bounds__(256) void sec_decode_bs_kernel(const u8 *__restrict
                                                             const sec::SynDesc *__restrict__ descs,
                                                             const sec::Tile *__restrict__ tiles, const sec::SynSlots sl)
 {
-    const sec::Tile tl = tiles[blockIdx.x];
+    const sec::Tile tl = sec::own_tile(tiles);
     const sec::SynDesc d = descs[tl.chunk];
     const u32 s = tl.t0 + (threadIdx.x >> 6) * kSpan;
     if (s >= d.B)
