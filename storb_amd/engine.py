@@ -63,6 +63,36 @@ def _ptr(a: np.ndarray) -> int:
     return int(a.ctypes.data) if a.size else 0
 
 
+def _flags(host: bool = False, asynchronous: bool = False, staged: bool = False, recover_only: bool = False) -> int:
+    """The flag word of a batch call."""
+    return ((SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0) |
+            (SEC_F_STAGED if staged else 0) | (SEC_F_RECOVER if recover_only else 0))
+
+
+def _rows(flat, width: int, counts, conv=bytes) -> list[list]:
+    """A flat array of `width`-byte records cut into rows, counts[c] records for chunk c, each
+    record through `conv`."""
+    mv = memoryview(flat)
+    out, f = [], 0
+    for n in counts:
+        out.append([conv(mv[width * (f + j):width * (f + j + 1)]) for j in range(n)])
+        f += n
+    return out
+
+
+def _decoded_len(item) -> int:
+    """The k*B - padlen bytes a decode item (k, m, blocks, sharenums, padlen) reassembles to."""
+    return item[0] * len(item[2][0]) - item[4]
+
+
+def _decoded_starts(items) -> list[int]:
+    """Where each decode item's bytes start in the concatenation of them all; last, its length."""
+    starts = [0]
+    for it in items:
+        starts.append(starts[-1] + _decoded_len(it))
+    return starts
+
+
 def default_device() -> int:
     for var in ("STORB_EC_DEVICE", "LOCAL_RANK"):
         v = os.environ.get(var)
@@ -167,8 +197,8 @@ class Engine:
         descs = np.ascontiguousarray(descs, dtype=ENC_DTYPE)
         s, _ks = addr(src)
         p, _kp = addr(parity)
-        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0) | (SEC_F_STAGED if staged else 0)
-        self._check(self.lib.sec_encode_batch(self._ctx, _ptr(descs), len(descs), s or None, p or None, flags))
+        self._check(self.lib.sec_encode_batch(self._ctx, _ptr(descs), len(descs), s or None, p or None,
+                                              _flags(host, asynchronous, staged)))
 
     def decode_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks, out, *,
                      block_avail: np.ndarray | None = None, recover_only: bool = False, host: bool = False,
@@ -185,10 +215,9 @@ class Engine:
             raise ValueError("block_avail needs one entry per slot")
         b, _kb = addr(blocks)
         o, _ko = addr(out)
-        flags = ((SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0) |
-                 (SEC_F_RECOVER if recover_only else 0) | (SEC_F_STAGED if staged else 0))
         self._check(self.lib.sec_decode_batch_ex(self._ctx, _ptr(descs), len(descs), _ptr(sn), _ptr(bo),
-                                                 None if av is None else _ptr(av), b or None, o or None, flags))
+                                                 None if av is None else _ptr(av), b or None, o or None,
+                                                 _flags(host, asynchronous, staged, recover_only)))
 
     # -- the repair / check family: shared plumbing ---------------------------
     def _row_call(self, fn, dtype, descs, sharenums, block_offs, block_avail, targets, bufs, *, host, asynchronous,
@@ -213,9 +242,8 @@ class Engine:
         if tn is not None:
             args += [_ptr(tn) or None, _ptr(to) or None]
         args += [a or None for a, _ in held[1:]]
-        flags = ((SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0) |
-                 (SEC_F_RECOVER if recover_only else 0))
-        self._check(fn(self._ctx, _ptr(descs), len(descs), *args, flags))
+        self._check(fn(self._ctx, _ptr(descs), len(descs), *args,
+                       _flags(host, asynchronous, recover_only=recover_only)))
 
     @staticmethod
     def _lay_out_blocks(items):
@@ -235,6 +263,34 @@ class Engine:
                 sn[slot + q] = int(it[3][q])
             slot += len(it[2])
         return sn, bo, keep, first
+
+    @staticmethod
+    def _recovered_bytes(item) -> int:
+        """What a recover-only call writes for a chunk: B bytes per primary missing from its
+        first k blocks."""
+        k = item[0]
+        return sum(1 for x in item[3][:k] if int(x) >= k) * len(item[2][0])
+
+    @staticmethod
+    def _join_views(item, rows, o) -> list:
+        """A chunk's k*B - padlen bytes as views, in order: its present primaries (among its first
+        k blocks) from the caller's blocks, the others from the recovered rows at rows[o:]."""
+        k, _m, blocks, sharenums, padlen = item
+        B = len(blocks[0])
+        prim = {int(x): q for q, x in enumerate(sharenums[:k]) if int(x) < k}  # primary -> its block
+        left = k * B - padlen
+        views = []
+        for row in range(k):
+            if left <= 0:
+                break
+            if row in prim:
+                v = memoryview(blocks[prim[row]]).cast("B")
+            else:  # the next recovered row (rows come in primary order)
+                v = rows[o:o + B]
+                o += B
+            views.append(v[:left] if left < B else v)
+            left -= B
+        return views
 
     @staticmethod
     def _lay_out_targets(items, digests: bool):
@@ -269,13 +325,7 @@ class Engine:
         from ._hostbytes import _finalize
 
         out = [[_finalize(b) for b in row] for row in objs]
-        if dig is None:
-            return out, None
-        dv, digs, f = memoryview(dig), [], 0
-        for row in out:
-            digs.append([bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(len(row))])
-            f += len(row)
-        return out, digs
+        return out, (None if dig is None else _rows(dig, 20, [len(row) for row in out]))
 
     @staticmethod
     def _check_results(items, first, res, rb, col):
@@ -387,30 +437,16 @@ class Engine:
         descs = np.zeros(len(items), dtype=DCHK_DTYPE)
         rec = []
         total = 0
-        for j, (k, m, blocks, sharenums, padlen) in enumerate(items):
-            B = len(blocks[0])
-            descs[j] = (total, B, padlen, slot0[j], len(blocks), k, m, 0)
+        for j, it in enumerate(items):
+            k, m, blocks, _sharenums, padlen = it
+            descs[j] = (total, len(blocks[0]), padlen, slot0[j], len(blocks), k, m, 0)
             rec.append(total)
-            total += sum(1 for x in sharenums[:k] if int(x) >= k) * B
+            total += self._recovered_bytes(it)
         buf = self._out_buffer(max(total, 1))
         res, rb, col = self._result_arrays(len(items), sn.size)
         self.decode_check_batch(descs, sn, bo, 0, buf, res, row_bad=rb, column=col, host=True, recover_only=True)
         mv = memoryview(buf)
-        views = []
-        for j, (k, m, blocks, sharenums, padlen) in enumerate(items):
-            B = len(blocks[0])
-            prim = {int(x): q for q, x in enumerate(sharenums[:k]) if int(x) < k}  # primary -> its block
-            o, left = rec[j], k * B - padlen
-            for row in range(k):
-                if left <= 0:
-                    break
-                if row in prim:
-                    v = memoryview(blocks[prim[row]]).cast("B")
-                else:  # the next recovered row (rows come in primary order)
-                    v = mv[o:o + B]
-                    o += B
-                views.append(v[:left] if left < B else v)
-                left -= B
+        views = [v for it, o in zip(items, rec) for v in self._join_views(it, mv, o)]
         return self._joined(views), self._check_results(items, slot0, res, rb, col)
 
     def repair_check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
@@ -456,9 +492,8 @@ class Engine:
         s, _ks = addr(src)
         p, _kp = addr(parity)
         g, _kg = addr(digests)
-        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
         self._check(self.lib.sec_encode_digest_batch(self._ctx, _ptr(descs), len(descs), s or None, p or None,
-                                                     g or None, flags))
+                                                     g or None, _flags(host, asynchronous)))
 
     @staticmethod
     def _key_handle(key):
@@ -479,26 +514,20 @@ class Engine:
         p, _kp = addr(parity)
         t, _kt = addr(tags)
         g, _kg = addr(digests) if digests is not None else (0, None)
-        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
         self._check(self.lib.sec_encode_tag_batch(self._ctx, self._key_handle(key), _ptr(descs), len(descs),
-                                                  s or None, p or None, g or None, t or None, flags))
+                                                  s or None, p or None, g or None, t or None,
+                                                  _flags(host, asynchronous)))
 
     @staticmethod
     def _tag_ints(tags: np.ndarray, ms) -> list[list[int]]:
         """Per chunk, its m tags as Python ints (tags: 256 bytes per slot, chunk-major)."""
-        tv = memoryview(tags)
-        out, f = [], 0
-        for m in ms:
-            out.append([int.from_bytes(tv[256 * (f + j):256 * (f + j + 1)], "big") for j in range(m)])
-            f += m
-        return out
+        return _rows(tags, 256, ms, lambda v: int.from_bytes(v, "big"))
 
     def sha1_batch(self, msgs: np.ndarray, digests, *, host: bool = False, asynchronous: bool = False) -> None:
         """SHA-1 of each (addr, len, avail) message into 20-byte digests — sec_sha1_batch."""
         msgs = np.ascontiguousarray(msgs, dtype=MSG_DTYPE)
         g, _kg = addr(digests)
-        flags = (SEC_F_HOST if host else 0) | (SEC_F_ASYNC if asynchronous else 0)
-        self._check(self.lib.sec_sha1_batch(self._ctx, _ptr(msgs), len(msgs), g or None, flags))
+        self._check(self.lib.sec_sha1_batch(self._ctx, _ptr(msgs), len(msgs), g or None, _flags(host, asynchronous)))
 
     # -- pinned host memory: the zero-copy host path ----------------------------
     def host_empty(self, nbytes: int) -> np.ndarray:
@@ -587,6 +616,23 @@ class Engine:
         mv = memoryview(out)
         return [bytes(mv[20 * i:20 * (i + 1)]) for i in range(len(datas))]
 
+    @staticmethod
+    def _encode_descs(chunks, shapes):
+        """ENC_DTYPE descriptors of host chunks (shapes: [(k, m)] per chunk), their parity back
+        to back: (descs, layout, total, keep), layout[i] = (offset, B, m - k) of chunk i's parity
+        blocks, total = the parity bytes, keep = what must outlive the call."""
+        descs = np.zeros(len(chunks), dtype=ENC_DTYPE)
+        keep, layout, total = [], [], 0
+        for i, (c, (k, m)) in enumerate(zip(chunks, shapes)):
+            a, kp = addr(c)
+            keep.append(kp)
+            ln = len(kp) if isinstance(kp, np.ndarray) else len(c)
+            B = -(-ln // k) if ln else 0
+            descs[i] = (a, ln, total, max(B, 1), k, m)
+            layout.append((total, B, m - k))
+            total += (m - k) * B
+        return descs, layout, total, keep
+
     def encode_host_raw(self, chunks, shapes, digests: bool = False, staged: bool = False, tag_key=None):
         """``encode_host`` without the per-block ``bytes``: returns (buf, layout) where buf is
         this engine's pinned result scratch and layout[i] = (offset, B, m - k) of chunk i's
@@ -597,18 +643,7 @@ class Engine:
         last element: per chunk, the APDP tags of its m blocks as Python ints, from the same pass
         (sec_encode_tag_batch)."""
         n = len(chunks)
-        descs = np.zeros(n, dtype=ENC_DTYPE)
-        keep = []
-        layout = []
-        total = 0
-        for i, (c, (k, m)) in enumerate(zip(chunks, shapes)):
-            a, kp = addr(c)
-            keep.append(kp)
-            ln = len(kp) if isinstance(kp, np.ndarray) else len(c)
-            B = -(-ln // k) if ln else 0
-            descs[i] = (a, ln, total, max(B, 1), k, m)
-            layout.append((total, B, m - k))
-            total += (m - k) * B
+        descs, layout, total, _keep = self._encode_descs(chunks, shapes)
         out = self._out_buffer(total)
         if tag_key is not None:
             ms = [m for (_, m) in shapes]
@@ -639,14 +674,8 @@ class Engine:
         of 256 bytes per piece) with tag_key (a ``bn.ModKey`` with ``set_tag`` done): each
         piece's APDP tag, big-endian, from the GPU call that encodes it (sec_encode_pieces_tags)."""
         n = len(chunks)
-        descs = np.zeros(n, dtype=ENC_DTYPE)
-        keep = []
-        for i, (c, (k, m)) in enumerate(zip(chunks, shapes)):
-            a, kp = addr(c)
-            keep.append(kp)
-            ln = len(kp) if isinstance(kp, np.ndarray) else len(c)
-            B = -(-ln // k) if ln else 0
-            descs[i] = (a, ln, 0, max(B, 1), k, m)
+        descs, _layout, _total, _keep = self._encode_descs(chunks, shapes)
+        descs["parity_off"] = 0  # ignored by sec_encode_pieces: the parity goes through the library's scratch
         pa = np.ascontiguousarray(piece_addrs, dtype=np.uint64)
         if pa.size != sum(m for (_, m) in shapes):
             raise ValueError("encode_pieces_into: one piece address per piece")
@@ -656,7 +685,7 @@ class Engine:
             raise ValueError("encode_pieces_into: tags and tag_key go together")
         if tags is not None and tags.size < 256 * pa.size:
             raise ValueError("encode_pieces_into: tags needs 256 bytes per piece")
-        flags = SEC_F_HOST | (SEC_F_STAGED if staged else 0) | (SEC_F_GPU_PARITY_IDS if gpu_parity_ids else 0)
+        flags = _flags(host=True, staged=staged) | (SEC_F_GPU_PARITY_IDS if gpu_parity_ids else 0)
         if n and tags is not None:
             self._check(self.lib.sec_encode_pieces_tags(self._ctx, self._key_handle(tag_key), _ptr(descs), n, None,
                                                         _ptr(pa), None if digests is None else _ptr(digests),
@@ -673,48 +702,14 @@ class Engine:
         ``tag_key`` (a ``bn.ModKey`` with ``set_tag`` done) also, last, per chunk the APDP tags of
         all m blocks as Python ints, from the same pass over the chunk.
         """
-        n = len(chunks)
-        descs = np.zeros(n, dtype=ENC_DTYPE)
-        keep = []
-        blocks = []
-        total = 0
-        for i, (c, (k, m)) in enumerate(zip(chunks, shapes)):
-            a, kp = addr(c)
-            keep.append(kp)
-            ln = len(kp) if isinstance(kp, np.ndarray) else len(c)
-            B = -(-ln // k) if ln else 0
-            descs[i] = (a, ln, total, max(B, 1), k, m)
-            blocks.append((total, B, m - k))
-            total += (m - k) * B
-        out = self._out_buffer(total)
+        res = self.encode_host_raw(chunks, shapes, digests=digests, tag_key=tag_key)
+        mv = memoryview(res[0])
+        out = [[[bytes(mv[o + r * B:o + (r + 1) * B]) for r in range(p)] for (o, B, p) in res[1]]]
+        if digests:
+            out.append(_rows(res[2], 20, [m for (_, m) in shapes]))
         if tag_key is not None:
-            ms = [m for (_, m) in shapes]
-            dig = np.empty(max(20 * sum(ms), 1), dtype=np.uint8) if digests else None
-            tags = np.empty(max(256 * sum(ms), 1), dtype=np.uint8)
-            if n:
-                self.encode_tag_batch(descs, 0, out, tags, tag_key, digests=dig, host=True)
-            mv = memoryview(out)
-            par = [[bytes(mv[o + r * B:o + (r + 1) * B]) for r in range(p)] for (o, B, p) in blocks]
-            ints = self._tag_ints(tags, ms)
-            if not digests:
-                return par, ints
-            dv, f, digs = memoryview(dig), 0, []
-            for m in ms:
-                digs.append([bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(m)])
-                f += m
-            return par, digs, ints
-        if not digests:
-            self.encode_batch(descs, 0, out, host=True)
-            mv = memoryview(out)
-            return [[bytes(mv[o + r * B:o + (r + 1) * B]) for r in range(p)] for (o, B, p) in blocks]
-        ms = [m for (_, m) in shapes]
-        dig = np.empty(max(20 * sum(ms), 1), dtype=np.uint8)
-        self.encode_digest_batch(descs, 0, out, dig, host=True)
-        mv, dv = memoryview(out), memoryview(dig)
-        par = [[bytes(mv[o + r * B:o + (r + 1) * B]) for r in range(p)] for (o, B, p) in blocks]
-        first = np.concatenate([[0], np.cumsum(ms)[:-1]]).astype(int) if ms else []
-        digs = [[bytes(dv[20 * (f + j):20 * (f + j + 1)]) for j in range(m)] for f, m in zip(first, ms)]
-        return par, digs
+            out.append(res[-1])
+        return out[0] if len(out) == 1 else tuple(out)
 
     # joins of at least this many bytes go to the library's copy threads (sec_host_copy) instead
     # of a single-threaded b"".join under the GIL
@@ -757,23 +752,11 @@ class Engine:
         """Every chunk's k*B - padlen bytes written to the host address outs[i], one call."""
         for it in items:
             check_decode_item(*it)
-        n = len(items)
-        descs = np.zeros(n, dtype=DEC_DTYPE)
-        nslots = sum(it[0] for it in items)
-        sn = np.zeros(max(nslots, 1), dtype=np.int32)
-        bo = np.zeros(max(nslots, 1), dtype=np.uint64)
-        keep = []
-        slot = 0
-        for j, (k, m, blocks, sharenums, padlen) in enumerate(items):
-            B = len(blocks[0])
-            for q, b in enumerate(blocks):
-                a, kp = addr(b)
-                keep.append(kp)
-                bo[slot + q] = a
-                sn[slot + q] = int(sharenums[q])
-            descs[j] = (int(outs[j]), B, padlen, slot, k, m)
-            slot += k
-        if n:
+        sn, bo, _keep, slot0 = self._lay_out_blocks(items)
+        descs = np.zeros(len(items), dtype=DEC_DTYPE)
+        for j, (k, m, blocks, _sharenums, padlen) in enumerate(items):
+            descs[j] = (int(outs[j]), len(blocks[0]), padlen, slot0[j], k, m)
+        if len(items):
             # (not staged=True: when the pieces are too scattered to page-lock, the library
             # copies the present ones into the output first and a large call's kernels read
             # them back from there, the output page-locked for the call)
@@ -789,11 +772,10 @@ class Engine:
             return self._joined(self._decode_parts(items, per_chunk=False))
         from ._hostbytes import _finalize, _new_bytes
 
-        lens = [it[0] * len(it[2][0]) - it[4] for it in items]
-        b, dst = _new_bytes(sum(lens))
+        starts = _decoded_starts(items)
+        b, dst = _new_bytes(starts[-1])
         if dst.size:
-            starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if lens else []
-            self._reassemble(items, [dst.ctypes.data + int(o) for o in starts])
+            self._reassemble(items, [dst.ctypes.data + o for o in starts[:-1]])
         return _finalize(b)
 
     def decode_host_into(self, items, dst: np.ndarray) -> int:
@@ -805,14 +787,12 @@ class Engine:
             if sum(len(v) for v in views) > dst.size:
                 raise ValueError("decode_host_into: destination too small")
             return self._join_into(views, dst.ctypes.data) if dst.size else 0
-        lens = [it[0] * len(it[2][0]) - it[4] for it in items]
-        total = sum(lens)
-        if total > dst.size:
+        starts = _decoded_starts(items)
+        if starts[-1] > dst.size:
             raise ValueError("decode_host_into: destination too small")
-        if total:
-            starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
-            self._reassemble(items, [dst.ctypes.data + int(o) for o in starts])
-        return total
+        if starts[-1]:
+            self._reassemble(items, [dst.ctypes.data + o for o in starts[:-1]])
+        return starts[-1]
 
     def decode_host_chunks(self, items) -> list[bytes]:
         """``decode_host``, one bytes object per chunk."""
@@ -820,7 +800,7 @@ class Engine:
             return [self._joined(p) for p in self._decode_parts(items, per_chunk=True, views=True)]
         from ._hostbytes import _finalize, _new_bytes
 
-        objs = [_new_bytes(it[0] * len(it[2][0]) - it[4]) for it in items]
+        objs = [_new_bytes(_decoded_len(it)) for it in items]
         live = [(it, v.ctypes.data) for it, (_, v) in zip(items, objs) if v.size]
         if live:
             self._reassemble([it for it, _ in live], [a for _, a in live])
@@ -833,8 +813,6 @@ class Engine:
         piece.py:196-197), so it is the join of its blocks, taken as views with no staging or
         PCIe round trip.  Returns per chunk either that chunk's bytes (per_chunk; with `views`
         the list of its buffers instead) or a list of buffers whose concatenation is the output."""
-        n = len(items)
-        as_views = views
         gpu = []  # indices of chunks with a missing primary
         for i, item in enumerate(items):
             check_decode_item(*item)
@@ -845,124 +823,79 @@ class Engine:
         # primaries, B bytes each, in primary order); the chunk is then the join of its present
         # primaries and those rows, so only e * B bytes per chunk come back over PCIe instead of
         # the whole reassembled chunk.
-        rec = {}
+        rec, mv = {}, None
         if gpu:
+            lost = [items[i] for i in gpu]
+            sn, bo, _keep, slot0 = self._lay_out_blocks(lost)
             descs = np.zeros(len(gpu), dtype=DEC_DTYPE)
-            nslots = sum(items[i][0] for i in gpu)
-            sn_arr = np.zeros(nslots, dtype=np.int32)
-            bo = np.zeros(nslots, dtype=np.uint64)
-            keep = []
-            slot = total = 0
-            for j, i in enumerate(gpu):
-                k, m, blocks, sharenums, padlen = items[i]
-                B = len(blocks[0])
-                for q, b in enumerate(blocks):
-                    a, kp = addr(b)
-                    keep.append(kp)
-                    bo[slot + q] = a
-                    sn_arr[slot + q] = int(sharenums[q])
-                e = sum(1 for x in sharenums if int(x) >= k)
-                descs[j] = (total, B, padlen, slot, k, m)
+            total = 0
+            for j, (i, it) in enumerate(zip(gpu, lost)):
+                k, m, blocks, _sharenums, padlen = it
+                descs[j] = (total, len(blocks[0]), padlen, slot0[j], k, m)
                 rec[i] = total
-                slot += k
-                total += e * B
+                total += self._recovered_bytes(it)
             buf = self._out_buffer(total)
-            self.decode_batch(descs, sn_arr, bo, 0, buf, host=True, recover_only=True)
+            self.decode_batch(descs, sn, bo, 0, buf, host=True, recover_only=True)
             mv = memoryview(buf)
         parts = []
-        for i in range(n):
-            k, m, blocks, sharenums, padlen = items[i]
-            B = len(blocks[0])
-            prim = {int(x): q for q, x in enumerate(sharenums) if int(x) < k}  # primary -> its block
-            o = rec.get(i)
-            left = k * B - padlen
-            views = []
-            for j in range(k):
-                if left <= 0:
-                    break
-                if j in prim:
-                    v = memoryview(blocks[prim[j]]).cast("B")
-                else:  # the next recovered row (rows come in primary order)
-                    v = mv[o:o + B]
-                    o += B
-                views.append(v[:left] if left < B else v)
-                left -= B
+        for i, it in enumerate(items):
+            chunk = self._join_views(it, mv, rec.get(i))
             if per_chunk:
-                parts.append(views if as_views else b"".join(views))
+                parts.append(chunk if views else b"".join(chunk))
             else:
-                parts.extend(views)
+                parts.extend(chunk)
         return parts
+
+def _check_blocks(k: int, m: int, blocks, sharenums, *, spares: bool, targets=(), padlen=None) -> None:
+    """The core of the check_*_item preconditions, in the library's order: the block count
+    (exactly k, or with `spares` any n with k <= n <= m), equal lengths, 1 <= k <= m <= 256,
+    sharenums and targets in [0, m) and all distinct, and with `padlen` 0 <= padlen <= k*B."""
+    n = len(blocks)
+    if len(sharenums) != n or (n != k and not spares):
+        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
+    B = len(blocks[0]) if blocks else 0
+    for b in blocks:
+        if len(b) != B:
+            raise Error(_lib.strerror(_lib.SEC_EBLOCKLEN))
+    if not (1 <= k <= m <= 256):
+        raise Error(_lib.strerror(_lib.SEC_EKM))
+    if not (k <= n <= m):
+        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
+    nums = [int(x) for x in sharenums] + [int(x) for x in targets]
+    if any(x < 0 or x >= m for x in nums):
+        raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
+    if len(set(nums)) != len(nums):
+        raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
+    if padlen is not None and not (0 <= padlen <= k * B):
+        raise Error(_lib.strerror(_lib.SEC_EPADLEN))
 
 
 def check_decode_item(k: int, m: int, blocks, sharenums, padlen: int) -> None:
     """zfec's decode preconditions for one chunk (the library's own checks, raised before any
     GPU work): exactly k blocks and sharenums, equal lengths, 1 <= k <= m <= 256, sharenums in
     [0, m) and distinct, 0 <= padlen <= k*B.  Raises Error."""
-    if len(blocks) != k or len(sharenums) != k:
-        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
-    B = len(blocks[0]) if blocks else 0
-    for b in blocks:
-        if len(b) != B:
-            raise Error(_lib.strerror(_lib.SEC_EBLOCKLEN))
-    sn = [int(x) for x in sharenums]
-    if not (1 <= k <= m <= 256):
-        raise Error(_lib.strerror(_lib.SEC_EKM))
-    if any(x < 0 or x >= m for x in sn):
-        raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
-    if len(set(sn)) != k:
-        raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
-    if not (0 <= padlen <= k * B):
-        raise Error(_lib.strerror(_lib.SEC_EPADLEN))
+    _check_blocks(k, m, blocks, sharenums, spares=False, padlen=padlen)
 
 
 def check_repair_item(k: int, m: int, blocks, sharenums, targets) -> None:
     """The repair preconditions for one chunk (the library's own checks, raised before any GPU
     work): exactly k equal-length blocks and k sharenums, 1 <= k <= m <= 256, sources and
     targets in [0, m), all distinct, no target among the sources.  Raises Error."""
-    if len(blocks) != k or len(sharenums) != k:
-        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
-    B = len(blocks[0]) if blocks else 0
-    for b in blocks:
-        if len(b) != B:
-            raise Error(_lib.strerror(_lib.SEC_EBLOCKLEN))
-    if not (1 <= k <= m <= 256):
-        raise Error(_lib.strerror(_lib.SEC_EKM))
-    sn, tg = [int(x) for x in sharenums], [int(x) for x in targets]
-    if any(x < 0 or x >= m for x in sn + tg):
-        raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
-    if len(set(sn + tg)) != k + len(tg):
-        raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
+    _check_blocks(k, m, blocks, sharenums, spares=False, targets=targets)
 
 
 def check_check_item(k: int, m: int, blocks, sharenums) -> None:
     """The check preconditions for one chunk (the library's own checks, raised before any GPU
     work): n equal-length blocks and n sharenums, 1 <= k <= m <= 256, k <= n <= m, sharenums in
     [0, m) and distinct.  Raises Error."""
-    if len(blocks) != len(sharenums):
-        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
-    B = len(blocks[0]) if blocks else 0
-    for b in blocks:
-        if len(b) != B:
-            raise Error(_lib.strerror(_lib.SEC_EBLOCKLEN))
-    if not (1 <= k <= m <= 256):
-        raise Error(_lib.strerror(_lib.SEC_EKM))
-    if not (k <= len(blocks) <= m):
-        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
-    sn = [int(x) for x in sharenums]
-    if any(x < 0 or x >= m for x in sn):
-        raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
-    if len(set(sn)) != len(sn):
-        raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
+    _check_blocks(k, m, blocks, sharenums, spares=True)
 
 
 def check_decode_check_item(k: int, m: int, blocks, sharenums, padlen: int) -> None:
     """The decode + check preconditions for one chunk (the library's own checks, raised before any
     GPU work): n equal-length blocks and n sharenums, 1 <= k <= m <= 256, k <= n <= m, sharenums
     in [0, m) and distinct, 0 <= padlen <= k*B.  Raises Error."""
-    check_check_item(k, m, blocks, sharenums)
-    B = len(blocks[0]) if blocks else 0
-    if not (0 <= padlen <= k * B):
-        raise Error(_lib.strerror(_lib.SEC_EPADLEN))
+    _check_blocks(k, m, blocks, sharenums, spares=True, padlen=padlen)
 
 
 def check_decode_ids_item(k: int, m: int, blocks, sharenums, padlen: int, ids) -> None:
@@ -979,21 +912,7 @@ def check_repair_check_item(k: int, m: int, blocks, sharenums, targets) -> None:
     """The repair + check preconditions for one chunk (the library's own checks, raised before any
     GPU work): n equal-length blocks and n sharenums, 1 <= k <= m <= 256, k <= n <= m, sharenums
     and targets in [0, m), all distinct, no target among the blocks held.  Raises Error."""
-    if len(blocks) != len(sharenums):
-        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
-    B = len(blocks[0]) if blocks else 0
-    for b in blocks:
-        if len(b) != B:
-            raise Error(_lib.strerror(_lib.SEC_EBLOCKLEN))
-    if not (1 <= k <= m <= 256):
-        raise Error(_lib.strerror(_lib.SEC_EKM))
-    if not (k <= len(blocks) <= m):
-        raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
-    sn, tg = [int(x) for x in sharenums], [int(x) for x in targets]
-    if any(x < 0 or x >= m for x in sn + tg):
-        raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
-    if len(set(sn + tg)) != len(sn) + len(tg):
-        raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
+    _check_blocks(k, m, blocks, sharenums, spares=True, targets=targets)
 
 
 # -- matrices (host arithmetic; no device needed) ------------------------------

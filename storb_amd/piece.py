@@ -66,8 +66,9 @@ from pydantic import BaseModel, ConfigDict, Field
 
 from .constants import MAX_PIECE_SIZE, MIN_PIECE_SIZE, PIECE_LENGTH_OFFSET, PIECE_LENGTH_SCALING
 from .easyfec import Decoder, Encoder, Error
-from .engine import (EngineGroup, check_decode_check_item, check_decode_ids_item, check_decode_item, check_locate,
-                     check_repair_check_item, choose_blocks, device_count, get_engine, spread_threads)
+from .engine import (Engine, EngineGroup, _decoded_len, _decoded_starts, check_decode_check_item,
+                     check_decode_ids_item, check_decode_item, check_locate, check_repair_check_item, choose_blocks,
+                     device_count, get_engine, spread_threads)
 
 logger = logging.getLogger(__name__)
 
@@ -435,11 +436,10 @@ def _pieces_parallel(chunks: list, shapes: list, digests: bool = False, hash_ids
     ``hash_ids=True``: (pieces, futures), futures[i][j] = the hashlib SHA-1 hex of piece j of
     chunk i, each started as soon as that piece is filled (data pieces beside the GPU call) and
     still running when this returns."""
+    _short_middle(shapes, chunks)
     hp = _pool("hash")
     out, jobs, hfut = [], [], []
     for c, (k, m, B, _) in zip(chunks, shapes):
-        if k > 1 and (k - 1) * B > len(c):  # easyfec's short middle slice, as Encoder.encode
-            raise Error("Precondition violation: Input blocks are required to be all the same length.")
         src = np.frombuffer(memoryview(c).cast("B"), dtype=np.uint8)
         ps, views = [], []
         for j in range(k):
@@ -453,8 +453,7 @@ def _pieces_parallel(chunks: list, shapes: list, digests: bool = False, hash_ids
     # staged, not page-locked: the pool is faulting in the new pieces meanwhile, and locking
     # waits on the same memory-map lock (6.4 against 0.55 ms for one 8 MiB chunk on MI355X,
     # profiles/r03_upload_ab.jsonl)
-    res = get_engine().encode_host_raw(list(chunks), [(k, m) for (k, m, _, _) in shapes], digests=digests,
-                                       staged=True)
+    res = get_engine().encode_host_raw(list(chunks), _km(shapes), digests=digests, staged=True)
     buf, layout = res[0], res[1]
     for i, (ps, (o, B, p)) in enumerate(zip(out, layout)):
         pj = []
@@ -468,12 +467,7 @@ def _pieces_parallel(chunks: list, shapes: list, digests: bool = False, hash_ids
             else:
                 jobs.append(hp.submit(_fill, v, buf[o + r * B:o + (r + 1) * B]))
                 pj.append((jobs[-1], v))
-    ids = None
-    if digests:
-        hx, ids, f = res[2].tobytes().hex(), [], 0
-        for (_, m, _, _) in shapes:
-            ids.append([hx[40 * (f + j):40 * (f + j + 1)] for j in range(m)])
-            f += m
+    ids = _hex_rows(res[2], shapes) if digests else None
     for f in jobs:  # the pieces must be complete before anyone sees them (and buf is reused)
         f.result()
     if not _FILL_IN_PLACE:
@@ -517,33 +511,45 @@ def _encode_pieces(chunks: list, shapes: list, ids: bool, gpu_parity_ids: bool =
     # staged, not page-locked: the library's threads fault in the new pieces meanwhile, and locking
     # waits on the same memory-map lock (6.4 against 0.55 ms for one 8 MiB chunk on MI355X,
     # profiles/r03_upload_ab.jsonl)
-    if tag_key is None:
-        get_engine().encode_pieces_into(chunks, [(k, m) for (k, m, _, _) in shapes], addrs, dig, staged=True,
-                                        gpu_parity_ids=ids and gpu_parity_ids)
-    else:
-        tags = np.empty(max(256 * len(addrs), 1), dtype=np.uint8)
-        get_engine().encode_pieces_into(chunks, [(k, m) for (k, m, _, _) in shapes], addrs, dig, staged=True,
-                                        gpu_parity_ids=ids and gpu_parity_ids, tags=tags, tag_key=tag_key)
-    pieces = [[_finalize(b) for b, _ in row] for row in objs]
-    hexes = None
-    if ids:
-        hx, hexes, f = dig.tobytes().hex(), [], 0
-        for (_, m, _, _) in shapes:
-            hexes.append([hx[40 * (f + j):40 * (f + j + 1)] for j in range(m)])
-            f += m
+    tagged = {}
     if tag_key is not None:
-        tv, values, f = memoryview(tags), [], 0
-        for (_, m, _, _) in shapes:
-            values.append([int.from_bytes(tv[256 * (f + j):256 * (f + j + 1)], "big") for j in range(m)])
-            f += m
-        return pieces, hexes, values
+        tagged = {"tags": np.empty(max(256 * len(addrs), 1), dtype=np.uint8), "tag_key": tag_key}
+    get_engine().encode_pieces_into(chunks, _km(shapes), addrs, dig, staged=True,
+                                    gpu_parity_ids=ids and gpu_parity_ids, **tagged)
+    pieces = [[_finalize(b) for b, _ in row] for row in objs]
+    hexes = _hex_rows(dig, shapes) if ids else None
+    if tag_key is not None:
+        return pieces, hexes, Engine._tag_ints(tagged["tags"], [m for (_, m, _, _) in shapes])
     return pieces, hexes
+
+
+def _shapes(chunks) -> list:
+    """``chunk_shape`` of every chunk, after encode_chunk's ValueError for an empty one."""
+    shapes = []
+    for c in chunks:
+        n = len(c)
+        piece_length(n)  # same ValueError as encode_chunk for n == 0
+        shapes.append(chunk_shape(n))
+    return shapes
+
+
+def _km(shapes) -> list:
+    return [(k, m) for (k, m, _, _) in shapes]
 
 
 def _short_middle(shapes, chunks) -> None:
     for c, (k, m, B, _) in zip(chunks, shapes):
         if k > 1 and (k - 1) * B > len(c):  # easyfec's short middle slice, as Encoder.encode
             raise Error("Precondition violation: Input blocks are required to be all the same length.")
+
+
+def _hex_rows(dig: np.ndarray, shapes) -> list[list[str]]:
+    """A digest array (20 bytes per piece, chunk-major) as per-chunk rows of SHA-1 hex."""
+    hx, rows, f = dig.tobytes().hex(), [], 0
+    for (_, m, _, _) in shapes:
+        rows.append([hx[40 * (f + j):40 * (f + j + 1)] for j in range(m)])
+        f += m
+    return rows
 
 
 def _build(chunk_idx: int, k: int, m: int, B: int, padlen: int, n: int, blocks: list[bytes]) -> EncodedChunk:
@@ -554,6 +560,17 @@ def _build(chunk_idx: int, k: int, m: int, B: int, padlen: int, n: int, blocks: 
         pieces.append(Piece(piece_type=piece_type, data=block, chunk_idx=chunk_idx, piece_idx=i))
     return EncodedChunk(pieces=pieces, chunk_idx=chunk_idx, k=k, m=m, chunk_size=B, padlen=padlen,
                         original_chunk_size=n)
+
+
+def _split_and_parity(chunks, shapes, parity) -> list[list[bytes]]:
+    """Every chunk's m pieces: its k data slices cut on the caller's thread, then its parity."""
+    return [_split(c, k, B) + par for c, (k, _, B, _), par in zip(chunks, shapes, parity)]
+
+
+def _build_all(first_chunk_idx: int, chunks, shapes, pieces) -> list[EncodedChunk]:
+    """``_build`` of every chunk from its pieces; chunk i gets index first_chunk_idx + i."""
+    return [_build(first_chunk_idx + i, k, m, B, padlen, len(c), ps)
+            for i, (c, (k, m, B, padlen), ps) in enumerate(zip(chunks, shapes, pieces))]
 
 
 def encode_chunk(chunk: bytes, chunk_idx: int) -> EncodedChunk:
@@ -600,11 +617,7 @@ def encode_chunks(chunks: typing.Sequence[bytes], first_chunk_idx: int = 0, *, d
 
     devices (or the module default set by ``use_devices``): the chunks are split by bytes over
     those devices' workers (``EngineGroup``), one GPU call per device, results in chunk order."""
-    shapes = []
-    for c in chunks:
-        n = len(c)
-        piece_length(n)  # same ValueError as encode_chunk for n == 0
-        shapes.append(chunk_shape(n))
+    shapes = _shapes(chunks)
     if not chunks:
         return []
     grp = _group(devices)
@@ -615,34 +628,22 @@ def encode_chunks(chunks: typing.Sequence[bytes], first_chunk_idx: int = 0, *, d
     if HOST_PIECES:
         _short_middle(shapes, chunks)
         pieces, _ = _encode_pieces(list(chunks), shapes, False)
-        return [_build(first_chunk_idx + i, k, m, B, padlen, len(c), ps)
-                for i, (c, (k, m, B, padlen), ps) in enumerate(zip(chunks, shapes, pieces))]
-    if min(B for (_, _, B, _) in shapes) >= PARALLEL_COPY_MIN:  # piece copies in parallel
+    elif min(B for (_, _, B, _) in shapes) >= PARALLEL_COPY_MIN:  # piece copies in parallel
         pieces = _pieces_parallel(list(chunks), shapes)
-        return [_build(first_chunk_idx + i, k, m, B, padlen, len(c), ps)
-                for i, (c, (k, m, B, padlen), ps) in enumerate(zip(chunks, shapes, pieces))]
-    parity = get_engine().encode_host(list(chunks), [(k, m) for (k, m, _, _) in shapes])
-    out = []
-    for i, (c, (k, m, B, padlen), par) in enumerate(zip(chunks, shapes, parity)):
-        out.append(_build(first_chunk_idx + i, k, m, B, padlen, len(c), _split(c, k, B) + par))
-    return out
+    else:
+        pieces = _split_and_parity(chunks, shapes, get_engine().encode_host(list(chunks), _km(shapes)))
+    return _build_all(first_chunk_idx, chunks, shapes, pieces)
 
 
 def encode_chunks_with_ids(chunks: typing.Sequence[bytes],
                            first_chunk_idx: int = 0) -> tuple[list[EncodedChunk], list[list[str]]]:
     """``encode_chunks`` plus every piece's id (``piece_hash``, the SHA-1 the validator computes
     right after encoding, validator.py:1081), hashed on the GPU while the pieces are still there."""
-    shapes = []
-    for c in chunks:
-        n = len(c)
-        piece_length(n)
-        shapes.append(chunk_shape(n))
+    shapes = _shapes(chunks)
     if not chunks:
         return [], []
-    parity, digs = get_engine().encode_host(list(chunks), [(k, m) for (k, m, _, _) in shapes], digests=True)
-    out = []
-    for i, (c, (k, m, B, padlen), par) in enumerate(zip(chunks, shapes, parity)):
-        out.append(_build(first_chunk_idx + i, k, m, B, padlen, len(c), _split(c, k, B) + par))
+    parity, digs = get_engine().encode_host(list(chunks), _km(shapes), digests=True)
+    out = _build_all(first_chunk_idx, chunks, shapes, _split_and_parity(chunks, shapes, parity))
     return out, [[d.hex() for d in ds] for ds in digs]
 
 
@@ -657,19 +658,14 @@ def encode_chunks_with_tags(chunks: typing.Sequence[bytes], challenge_system, fi
     ``wrap_tags(values)``).  Returns (chunks, ids or None, tags): tags[i] = the ``APDPTag`` of
     each of chunk i's m pieces, equal to ``challenge_system.generate_tags`` over those pieces'
     data; chunks and ids as ``encode_chunks_with_ids``.  Errors as ``encode_chunks``."""
-    shapes = []
-    for c in chunks:
-        n = len(c)
-        piece_length(n)  # same ValueError as encode_chunk for n == 0
-        shapes.append(chunk_shape(n))
+    shapes = _shapes(chunks)
     if not chunks:
         return [], ([] if piece_ids else None), []
     _short_middle(shapes, chunks)
     pieces, ids, values = _encode_pieces(list(chunks), shapes, piece_ids, GPU_PARITY_IDS,
                                          tag_key=challenge_system.tag_key())
-    out = [_build(first_chunk_idx + i, k, m, B, padlen, len(c), ps)
-           for i, (c, (k, m, B, padlen), ps) in enumerate(zip(chunks, shapes, pieces))]
-    return out, ids, [challenge_system.wrap_tags(v) for v in values]
+    return (_build_all(first_chunk_idx, chunks, shapes, pieces), ids,
+            [challenge_system.wrap_tags(v) for v in values])
 
 
 def _sharenums(encoded_chunk: EncodedChunk, positional: bool):
@@ -723,36 +719,44 @@ def decode_chunks(encoded_chunks: typing.Sequence[EncodedChunk], *, positional_s
         return get_engine().decode_host(items)
     for it in items:  # zfec's preconditions for every chunk before any device starts
         check_decode_item(*it)
-    lens = [k * len(blocks[0]) - padlen for (k, _, blocks, _, padlen) in items]
-    starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    out, view = _new_bytes(int(starts[-1]))
+    starts = _decoded_starts(items)
+    out, view = _new_bytes(starts[-1])
 
     def share(its, lo):
         return get_engine().decode_host_into(its, view[starts[lo]:starts[lo + len(its)]])
 
-    grp.map_shares(share, items, lens)
+    grp.map_shares(share, items, [_decoded_len(it) for it in items])
     return _finalize(out)
 
 
-def _relevant(pieces: list[Piece], chunk: EncodedChunk) -> list[Piece]:
-    relevant = [piece for piece in pieces if piece.chunk_idx == chunk.chunk_idx]
-    relevant.sort(key=lambda p: p.piece_idx)
+def _by_chunk(pieces: Iterable[Piece]) -> dict[int, list[Piece]]:
+    """The pieces handed over, per ``chunk_idx``, in the order given."""
+    by_chunk: dict[int, list[Piece]] = {}
+    for p in pieces:
+        by_chunk.setdefault(p.chunk_idx, []).append(p)
+    return by_chunk
+
+
+def _take_pieces(chunk: EncodedChunk, by_chunk: dict) -> None:
+    """``reconstruct_data``'s step for one chunk: it gets its pieces in ascending piece_idx, or the
+    reference's ValueError."""
+    relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
     if len(relevant) < chunk.k:
         raise ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
-    return relevant
+    chunk.pieces = relevant
+
+
+def _group_pieces(pieces: list[Piece], chunks: list[EncodedChunk]) -> None:
+    """``reconstruct_data``'s grouping: ``_take_pieces`` for every chunk, in order."""
+    by_chunk = _by_chunk(pieces)
+    for chunk in chunks:
+        _take_pieces(chunk, by_chunk)
 
 
 def reconstruct_data(pieces: list[Piece], chunks: list[EncodedChunk], *, devices=None) -> bytes:
     """Reconstruct the original bytes from pieces (piece.py:201-236), one batched decode (per
     device with `devices` / ``use_devices``: see decode_chunks)."""
-    by_chunk: dict[int, list[Piece]] = {}
-    for p in pieces:
-        by_chunk.setdefault(p.chunk_idx, []).append(p)
-    for chunk in chunks:
-        relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
-        if len(relevant) < chunk.k:
-            raise ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
-        chunk.pieces = relevant
+    _group_pieces(pieces, chunks)
     return decode_chunks(chunks, devices=devices)
 
 
@@ -771,37 +775,13 @@ def repair_chunks(chunks: typing.Sequence[EncodedChunk], targets=None, *, piece_
         raise ValueError("repair_chunks: one target list (or None) per chunk")
     items = []
     for i, ch in enumerate(chunks):
-        if not (1 <= ch.k <= ch.m <= 256):
-            raise Error(f"Precondition violation: 1 <= k <= m <= 256 required (k={ch.k}, m={ch.m})")
-        have: dict[int, Piece] = {}
-        for p in ch.pieces or []:
-            have.setdefault(p.piece_idx, p)
-        use = sorted(have.values(), key=lambda p: p.piece_idx)
-        if len(use) < ch.k:
-            raise ValueError(f"Not enough pieces to repair chunk {ch.chunk_idx}")
-        if len(use) > ch.k:
-            pick = choose_blocks(ch.k, ch.m, [p.piece_idx for p in use])
-            use = [use[j] for j in pick] if pick is not None else use[:ch.k]
-        tg = targets[i] if targets is not None and targets[i] is not None else None
-        if tg is None:
-            tg = [t for t in range(ch.m) if t not in have]
-        items.append((ch.k, ch.m, [p.data for p in use], [p.piece_idx for p in use], [int(t) for t in tg]))
+        held = _held_pieces(ch, "repair")
+        items.append(_basis_item(ch, held, _targets_of(targets, i, ch, held)))
     if not items:
         return []
     res = get_engine().repair_host(items, digests=piece_ids)
     blocks, digs = res if piece_ids else (res, None)
-    out = []
-    for i, (ch, it) in enumerate(zip(chunks, items)):
-        row = []
-        for j, t in enumerate(it[4]):
-            kind = PieceType.Data if t < ch.k else PieceType.Parity
-            if piece_ids:
-                row.append(ProcessedPieceInfo(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind,
-                                              data=blocks[i][j], piece_id=digs[i][j].hex()))
-            else:
-                row.append(Piece(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind, data=blocks[i][j]))
-        out.append(row)
-    return out
+    return _repaired_pieces(chunks, [it[4] for it in items], blocks, digs)
 
 
 def repair_pieces(chunk: EncodedChunk, targets=None, *, piece_ids: bool = False) -> list[Piece]:
@@ -832,6 +812,48 @@ def _check_item(ch: EncodedChunk, held: list[Piece]):
     took = {p.piece_idx for p in basis}
     use = basis + [p for p in held if p.piece_idx not in took]
     return ch.k, ch.m, [p.data for p in use], [p.piece_idx for p in use]
+
+
+def _basis_item(ch: EncodedChunk, held: list[Piece], tail):
+    """(k, m, blocks, sharenums, tail) over the basis of ``_check_item`` alone: the k pieces a
+    decode or a repair reads, and its padlen or targets."""
+    k, m, blocks, sharenums = _check_item(ch, held)
+    return k, m, blocks[:k], sharenums[:k], tail
+
+
+def _targets_of(targets, i: int, ch: EncodedChunk, held: list[Piece]) -> list[int]:
+    """The pieces to regenerate for chunk i: targets[i], or every ``piece_idx`` absent from `held`."""
+    tg = targets[i] if targets is not None and targets[i] is not None else None
+    if tg is None:
+        have = {p.piece_idx for p in held}
+        tg = [t for t in range(ch.m) if t not in have]
+    return [int(t) for t in tg]
+
+
+def _repaired_pieces(chunks, tgs, blocks, digs) -> list[list[Piece]]:
+    """Per chunk its regenerated pieces in target order (tgs[i]), from the blocks, and with `digs`
+    the digests, that the engine returned: ``ProcessedPieceInfo`` with ids, else ``Piece``."""
+    out = []
+    for i, ch in enumerate(chunks):
+        row = []
+        for j, t in enumerate(tgs[i]):
+            kind = PieceType.Data if t < ch.k else PieceType.Parity
+            if digs is not None:
+                row.append(ProcessedPieceInfo(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind,
+                                              data=blocks[i][j], piece_id=digs[i][j].hex()))
+            else:
+                row.append(Piece(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind, data=blocks[i][j]))
+        out.append(row)
+    return out
+
+
+def _begin_check(ch: EncodedChunk, what: str, held: list, out: list) -> list[Piece]:
+    """A check's bookkeeping for one more chunk: its held pieces appended to `held`, and a
+    ``ChunkCheck`` that says consistent until the rounds say otherwise to `out`."""
+    use = _held_pieces(ch, what)
+    held.append(use)
+    out.append(ChunkCheck(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
+    return use
 
 
 def _held_pieces(ch: EncodedChunk, what: str) -> list[Piece]:
@@ -899,9 +921,7 @@ def check_chunks(chunks: typing.Sequence[EncodedChunk], *, locate: bool = True) 
     out: list[ChunkCheck] = []
     held: list[list[Piece]] = []
     for ch in chunks:
-        use = _held_pieces(ch, "check")
-        held.append(use)
-        out.append(ChunkCheck(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
+        _begin_check(ch, "check", held, out)
     _check_rounds(chunks, held, out, locate)
     return out
 
@@ -946,10 +966,7 @@ def decode_chunks_checked(encoded_chunks: typing.Sequence[EncodedChunk], *,
     held: list[list[Piece]] = []
     items = []
     for ch in chunks:
-        use = _held_pieces(ch, "reconstruct")
-        held.append(use)
-        out.append(ChunkCheck(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
-        items.append(_check_item(ch, use))
+        items.append(_check_item(ch, _begin_check(ch, "reconstruct", held, out)))
     if not chunks:
         return b"", []
     full = [it + (ch.padlen,) for it, ch in zip(items, chunks)]
@@ -960,21 +977,16 @@ def decode_chunks_checked(encoded_chunks: typing.Sequence[EncodedChunk], *,
     redo = [i for i, ck in enumerate(out) if ck.located]
     if not redo:
         return data, out
-    again = []
-    for i in redo:  # from the pieces that passed the last re-check
-        k, m, blocks, sharenums = _check_item(chunks[i], held[i])
-        again.append((k, m, blocks[:k], sharenums[:k], chunks[i].padlen))
-    fixed = get_engine().decode_host(again)
-    lens = [it[0] * len(it[2][0]) - it[4] for it in full]
-    starts = [0]
-    for n in lens:
-        starts.append(starts[-1] + n)
+    # from the pieces that passed the last re-check
+    fixed = get_engine().decode_host([_basis_item(chunks[i], held[i], chunks[i].padlen) for i in redo])
+    starts = _decoded_starts(full)
     parts, at, f = [], 0, 0
     view = memoryview(data)
     for i in redo:
+        n = starts[i + 1] - starts[i]
         parts.append(view[at:starts[i]])
-        parts.append(memoryview(fixed)[f:f + lens[i]])
-        f += lens[i]
+        parts.append(memoryview(fixed)[f:f + n])
+        f += n
         at = starts[i + 1]
     parts.append(view[at:])
     return b"".join(parts), out
@@ -1009,15 +1021,9 @@ def repair_chunks_checked(chunks: typing.Sequence[EncodedChunk], targets=None, *
     held: list[list[Piece]] = []
     items, tgs = [], []
     for i, ch in enumerate(chunks):
-        use = _held_pieces(ch, "repair")
-        held.append(use)
-        out.append(ChunkCheck(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
+        use = _begin_check(ch, "repair", held, out)
         items.append(_check_item(ch, use))
-        tg = targets[i] if targets is not None and targets[i] is not None else None
-        if tg is None:
-            have = {p.piece_idx for p in use}
-            tg = [t for t in range(ch.m) if t not in have]
-        tgs.append([int(t) for t in tg])
+        tgs.append(_targets_of(targets, i, ch, use))
     if not chunks:
         return [], []
     full = [it + (tg,) for it, tg in zip(items, tgs)]
@@ -1030,27 +1036,15 @@ def repair_chunks_checked(chunks: typing.Sequence[EncodedChunk], targets=None, *
     if redo:
         again = []
         for i in redo:  # from the pieces that passed the last re-check
-            k, m, blks, sharenums = _check_item(chunks[i], held[i])
             tgs[i] = tgs[i] + [b for b in out[i].bad_piece_idx if b not in tgs[i]]
-            again.append((k, m, blks[:k], sharenums[:k], tgs[i]))
+            again.append(_basis_item(chunks[i], held[i], tgs[i]))
         fixed = get_engine().repair_host(again, digests=piece_ids)
         fblocks, fdigs = fixed if piece_ids else (fixed, None)
         for j, i in enumerate(redo):
             blocks[i] = fblocks[j]
             if piece_ids:
                 digs[i] = fdigs[j]
-    pieces = []
-    for i, ch in enumerate(chunks):
-        row = []
-        for j, t in enumerate(tgs[i]):
-            kind = PieceType.Data if t < ch.k else PieceType.Parity
-            if piece_ids:
-                row.append(ProcessedPieceInfo(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind,
-                                              data=blocks[i][j], piece_id=digs[i][j].hex()))
-            else:
-                row.append(Piece(chunk_idx=ch.chunk_idx, piece_idx=t, piece_type=kind, data=blocks[i][j]))
-        pieces.append(row)
-    return pieces, out
+    return _repaired_pieces(chunks, tgs, blocks, digs), out
 
 
 def repair_pieces_checked(chunk: EncodedChunk, targets=None, *, piece_ids: bool = False,
@@ -1069,14 +1063,7 @@ def reconstruct_data_checked(pieces: list[Piece], chunks: list[EncodedChunk]) ->
     consistent nor located; otherwise returns the bytes, all trustworthy in
     ``decode_chunks_checked``'s sense, and the checks.  One device, one call: objects too large
     for that stream through ``reconstruct_data_stream_checked``."""
-    by_chunk: dict[int, list[Piece]] = {}
-    for p in pieces:
-        by_chunk.setdefault(p.chunk_idx, []).append(p)
-    for chunk in chunks:
-        relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
-        if len(relevant) < chunk.k:
-            raise ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
-        chunk.pieces = relevant
+    _group_pieces(pieces, chunks)
     data, checks = decode_chunks_checked(chunks)
     bad = [ck.chunk_idx for ck in checks if not (ck.consistent or ck.located)]
     if bad:
@@ -1098,6 +1085,13 @@ def _windows(chunks, nbytes, size_of) -> Iterator[list]:
         yield win
 
 
+def _stream_windows(pieces, items, window_bytes, chunk_of):
+    """The set-up of the reconstruct_data_stream* family: (the pieces per chunk, `items` in windows
+    of about `window_bytes`, default STREAM_WINDOW_BYTES, of output); chunk_of(item) = its chunk."""
+    wb = STREAM_WINDOW_BYTES if window_bytes is None else window_bytes
+    return _by_chunk(pieces), _windows(items, wb, lambda it: max(chunk_of(it).original_chunk_size, 1))
+
+
 def _decode_window(window: list, by_chunk: dict):
     """Worker side of reconstruct_data_stream: (per-chunk bytes, error) for one window.  The
     window's chunks up to the first one that cannot be decoded are decoded (one GPU call for
@@ -1105,10 +1099,7 @@ def _decode_window(window: list, by_chunk: dict):
     items, err = [], None
     for chunk in window:
         try:
-            relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
-            if len(relevant) < chunk.k:
-                raise ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
-            chunk.pieces = relevant
+            _take_pieces(chunk, by_chunk)
             blocks, sharenums = _sharenums(chunk, False)
             B = len(blocks[0]) if blocks else 0
             if not (1 <= chunk.k <= chunk.m <= 256) or not (0 <= chunk.padlen <= chunk.k * B):
@@ -1141,43 +1132,56 @@ def reconstruct_data_stream(pieces: list[Piece], chunks: list[EncodedChunk], *,
     those devices' workers, two per device in flight.  Chunks come out in order; a chunk without
     enough pieces raises the reference's ValueError when the stream reaches it, after every
     earlier chunk."""
-    by_chunk: dict[int, list[Piece]] = {}
-    for p in pieces:
-        by_chunk.setdefault(p.chunk_idx, []).append(p)
-    wb = STREAM_WINDOW_BYTES if window_bytes is None else window_bytes
-    wins = _windows(chunks, wb, lambda c: max(c.original_chunk_size, 1))
+    by_chunk, wins = _stream_windows(pieces, chunks, window_bytes, lambda c: c)
     for outs, err in _pipeline(wins, _decode_window, (by_chunk,), _group(devices)):
         yield from outs
         if err is not None:
             raise err
 
 
-def _decode_checked_window(window: list, by_chunk: dict):
-    """Worker side of reconstruct_data_stream_checked: (per-chunk ``(bytes, ChunkCheck)``, error)
-    for one window.  The window's chunks up to the first one without enough pieces go through one
+def _decode_verified_window(window: list, by_chunk: dict, decode):
+    """Worker side of reconstruct_data_stream_checked and reconstruct_data_stream_id_checked: (per-chunk
+    ``(bytes, check)``, error) for one window of ``(chunk, *more)`` rows.  The window's rows up to the
+    first chunk without enough pieces go through one ``decode(chunks, *more columns)``:
     ``decode_chunks_checked`` (one fused GPU call, then the locate rounds and the second decode of
-    the located chunks, all confined to this window); that chunk's error is returned, to be raised
-    in order."""
+    the located chunks) or ``decode_chunks_id_checked``, all confined to this window; that chunk's
+    error is returned, to be raised in order."""
     good, err = [], None
-    for chunk in window:
-        relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
-        if len(relevant) < chunk.k:
-            err = ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
+    for row in window:
+        try:
+            _take_pieces(row[0], by_chunk)
+        except ValueError as e:
+            err = e
             break
-        chunk.pieces = relevant
-        good.append(chunk)
+        good.append(row)
     if not good:
         return [], err
     try:
-        data, checks = decode_chunks_checked(good)
+        data, checks = decode(*map(list, zip(*good)))
     except Exception as e:  # noqa: BLE001 - a precondition or device failure: nothing of the window is trusted
         return [], e
     view, at, pairs = memoryview(data), 0, []
-    for chunk, ck in zip(good, checks):
-        n = chunk.k * len(chunk.pieces[0].data) - chunk.padlen
+    for (chunk, *_), ck in zip(good, checks):
+        n = _decoded_len((chunk.k, chunk.m, [chunk.pieces[0].data], (), chunk.padlen))
         pairs.append((bytes(view[at:at + n]), ck))
         at += n
     return pairs, err
+
+
+def _stream_verified(pieces, rows, window_bytes, decode, trusted, refuse) -> Iterator[tuple]:
+    """The generator of both verified streams: `rows` of ``(chunk, *more)`` in windows through
+    ``_decode_verified_window`` on the stream worker, each chunk yielded as ``(bytes, check)`` once
+    trusted(check); else refuse(check, the checks seen so far) is raised."""
+    by_chunk, wins = _stream_windows(pieces, rows, window_bytes, lambda row: row[0])
+    seen: list = []
+    for pairs, err in _pipeline(wins, _decode_verified_window, (by_chunk, decode), None):
+        for data, ck in pairs:
+            seen.append(ck)
+            if not trusted(ck):
+                raise refuse(ck, list(seen))
+            yield data, ck
+        if err is not None:
+            raise err
 
 
 def reconstruct_data_stream_checked(pieces: list[Piece], chunks: list[EncodedChunk], *,
@@ -1200,21 +1204,10 @@ def reconstruct_data_stream_checked(pieces: list[Piece], chunks: list[EncodedChu
     a chunk that is neither consistent nor located.  Closing the generator early cancels the
     windows not yet started.  One device: ``devices=`` is not provided, as for the whole check
     family."""
-    by_chunk: dict[int, list[Piece]] = {}
-    for p in pieces:
-        by_chunk.setdefault(p.chunk_idx, []).append(p)
-    wb = STREAM_WINDOW_BYTES if window_bytes is None else window_bytes
-    wins = _windows(chunks, wb, lambda c: max(c.original_chunk_size, 1))
-    seen: list[ChunkCheck] = []
-    for pairs, err in _pipeline(wins, _decode_checked_window, (by_chunk,), None):
-        for data, ck in pairs:
-            seen.append(ck)
-            if not (ck.consistent or ck.located):
-                raise PieceCheckError(
-                    f"Held pieces disagree and no corrupt piece could be named in chunk {ck.chunk_idx}", list(seen))
-            yield data, ck
-        if err is not None:
-            raise err
+    yield from _stream_verified(
+        pieces, list(zip(chunks)), window_bytes, decode_chunks_checked, lambda ck: ck.consistent or ck.located,
+        lambda ck, seen: PieceCheckError(
+            f"Held pieces disagree and no corrupt piece could be named in chunk {ck.chunk_idx}", seen))
 
 
 class ChunkIdCheck(BaseModel):
@@ -1313,22 +1306,8 @@ def decode_chunks_id_checked(encoded_chunks: typing.Sequence[EncodedChunk],
         ck = ChunkIdCheck(chunk_idx=ch.chunk_idx, checked=len(use), ok=not bad, bad_piece_idx=bad,
                           decodable=len(good) >= ch.k)
         out.append(ck)
-        k, m, blocks, sharenums = _check_item(ch, good if ck.decodable else use)
-        items.append((k, m, blocks[:k], sharenums[:k], ch.padlen))
+        items.append(_basis_item(ch, good if ck.decodable else use, ch.padlen))
     return get_engine().decode_host(items), out
-
-
-def _group_pieces(pieces: list[Piece], chunks: list[EncodedChunk]) -> None:
-    """``reconstruct_data``'s grouping: each chunk gets its pieces in ascending piece_idx, or the
-    reference's ValueError."""
-    by_chunk: dict[int, list[Piece]] = {}
-    for p in pieces:
-        by_chunk.setdefault(p.chunk_idx, []).append(p)
-    for chunk in chunks:
-        relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
-        if len(relevant) < chunk.k:
-            raise ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
-        chunk.pieces = relevant
 
 
 def reconstruct_data_id_checked(pieces: list[Piece], chunks: list[EncodedChunk],
@@ -1347,34 +1326,6 @@ def reconstruct_data_id_checked(pieces: list[Piece], chunks: list[EncodedChunk],
     return data, checks
 
 
-def _decode_id_checked_window(window: list, by_chunk: dict):
-    """Worker side of reconstruct_data_stream_id_checked: (per-chunk ``(bytes, ChunkIdCheck)``, error)
-    for one window of ``(chunk, ids)`` pairs.  The window's chunks up to the first one without
-    enough pieces go through one ``decode_chunks_id_checked``; that chunk's error is returned, to be
-    raised in order."""
-    good, ids, err = [], [], None
-    for chunk, cid in window:
-        relevant = sorted(by_chunk.get(chunk.chunk_idx, []), key=lambda p: p.piece_idx)
-        if len(relevant) < chunk.k:
-            err = ValueError(f"Not enough pieces to reconstruct chunk {chunk.chunk_idx}")
-            break
-        chunk.pieces = relevant
-        good.append(chunk)
-        ids.append(cid)
-    if not good:
-        return [], err
-    try:
-        data, checks = decode_chunks_id_checked(good, ids)
-    except Exception as e:  # noqa: BLE001 - a precondition or device failure: nothing of the window is trusted
-        return [], e
-    view, at, pairs = memoryview(data), 0, []
-    for chunk, ck in zip(good, checks):
-        n = chunk.k * len(chunk.pieces[0].data) - chunk.padlen
-        pairs.append((bytes(view[at:at + n]), ck))
-        at += n
-    return pairs, err
-
-
 def reconstruct_data_stream_id_checked(pieces: list[Piece], chunks: list[EncodedChunk], piece_ids: typing.Sequence, *,
                                        window_bytes: int | None = None) -> Iterator[tuple[bytes, ChunkIdCheck]]:
     """``reconstruct_data_id_checked``'s contract, delivered as ``reconstruct_data_stream`` delivers:
@@ -1391,21 +1342,10 @@ def reconstruct_data_stream_id_checked(pieces: list[Piece], chunks: list[Encoded
     not provided, as for the whole check family."""
     if len(piece_ids) != len(chunks):
         raise ValueError("reconstruct_data_stream_id_checked: one list of recorded ids per chunk")
-    by_chunk: dict[int, list[Piece]] = {}
-    for p in pieces:
-        by_chunk.setdefault(p.chunk_idx, []).append(p)
-    wb = STREAM_WINDOW_BYTES if window_bytes is None else window_bytes
-    wins = _windows(list(zip(chunks, piece_ids)), wb, lambda pr: max(pr[0].original_chunk_size, 1))
-    seen: list[ChunkIdCheck] = []
-    for pairs, err in _pipeline(wins, _decode_id_checked_window, (by_chunk,), None):
-        for data, ck in pairs:
-            seen.append(ck)
-            if not ck.decodable:
-                raise PieceIdError(f"Fewer than k held pieces match their recorded ids in chunk {ck.chunk_idx}",
-                                   list(seen))
-            yield data, ck
-        if err is not None:
-            raise err
+    yield from _stream_verified(
+        pieces, list(zip(chunks, piece_ids)), window_bytes, decode_chunks_id_checked, lambda ck: ck.decodable,
+        lambda ck, seen: PieceIdError(
+            f"Fewer than k held pieces match their recorded ids in chunk {ck.chunk_idx}", seen))
 
 
 def _pipeline(windows: Iterator[list], fn, args: tuple, grp) -> Iterator:
@@ -1450,14 +1390,11 @@ def _window_shapes(window: list):
     shapes = []
     for c in window:
         try:
-            n = len(c)
-            piece_length(n)
-            k, m, B, padlen = chunk_shape(n)
-            if k > 1 and (k - 1) * B > n:
-                raise Error("Precondition violation: Input blocks are required to be all the same length.")
+            shape = _shapes([c])
+            _short_middle(shape, [c])
         except Exception as e:  # noqa: BLE001 - raised on the caller's thread after the chunks before it
             return shapes, e
-        shapes.append((k, m, B, padlen))
+        shapes += shape
     return shapes, None
 
 
@@ -1481,26 +1418,21 @@ def _encode_window(window: list, first_idx: int, piece_ids: bool, tags=None):
         hp = _pool("hash")
         if GPU_PIECE_IDS and min(B for (_, _, B, _) in shapes) >= PARALLEL_COPY_MIN:
             pieces, ids = _pieces_parallel(window, shapes, digests=True)
-            out = [_build(first_idx + i, k, m, B, padlen, len(c), ps)
-                   for i, (c, (k, m, B, padlen), ps) in enumerate(zip(window, shapes, pieces))]
-            return list(zip(out, ids)), err
+            return list(zip(_build_all(first_idx, window, shapes, pieces), ids)), err
         if HOST_PIECES:  # ids by the library's host threads (OpenSSL; parity ids on the GPU), pieces in the same call
             pieces, ids = _encode_pieces(list(window), shapes, True, GPU_PARITY_IDS)
-            out = [_build(first_idx + i, k, m, B, padlen, len(c), ps)
-                   for i, (c, (k, m, B, padlen), ps) in enumerate(zip(window, shapes, pieces))]
-            return list(zip(out, ids)), err
+            return list(zip(_build_all(first_idx, window, shapes, pieces), ids)), err
         if min(B for (_, _, B, _) in shapes) >= PARALLEL_COPY_MIN:
             pieces = _pieces_parallel(window, shapes)
             futs = [[hp.submit(_sha1_hex, b) for b in ps] for ps in pieces]
         else:  # small pieces: caller-thread copies; data pieces hash while the GPU runs
             prims = [_split(c, k, B) for c, (k, _, B, _) in zip(window, shapes)]
             futs = [[hp.submit(_sha1_hex, b) for b in prim] for prim in prims]
-            parity = get_engine().encode_host(list(window), [(k, m) for (k, m, _, _) in shapes])
+            parity = get_engine().encode_host(list(window), _km(shapes))
             pieces = [prim + par for prim, par in zip(prims, parity)]
             for fs, par in zip(futs, parity):
                 fs.extend(hp.submit(_sha1_hex, b) for b in par)
-        out = [_build(first_idx + i, k, m, B, padlen, len(c), ps)
-               for i, (c, (k, m, B, padlen), ps) in enumerate(zip(window, shapes, pieces))]
+        out = _build_all(first_idx, window, shapes, pieces)
         return [(ec, [f.result() for f in fs]) for ec, fs in zip(out, futs)], err
     except Exception as e:  # noqa: BLE001 - a device failure: nothing of the window is trusted
         return [], e
