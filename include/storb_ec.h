@@ -136,7 +136,7 @@ int sec_ctx_set_timing(sec_ctx *ctx, int enable);
 /* Waits for recorded pairs, returns the summed milliseconds and launch count of
  * kind 0 = encode, 1 = decode, 2 = SHA-1, 3 = bignum (APDP), 4 = repair (its kernels and,
  * with digests, their SHA-1), 5 = check, 6 = decode + check, 7 = repair + check (its main kernel and
- * tail, sec_check_final and, with digests, their SHA-1), and clears them. */
+ * tail, sec_check_final and, with digests, their SHA-1), 8 = decode + correct, and clears them. */
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches);
 
 /* ---- context options --------------------------------------------------------
@@ -369,6 +369,54 @@ int sec_decode_check_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t n
                            const uint64_t *block_avail, const uint8_t *blocks, uint8_t *out,
                            sec_chk_result *results, uint8_t *row_bad, uint8_t *column,
                            unsigned flags);
+
+/* ---- decode + correct: reassemble, and put right one wrong entry per byte position -------------
+ * sec_decode_check_batch detects a corrupt piece; taking it out means dropping the whole piece and
+ * checking again, which gives up once two pieces are damaged and n - k = 2, even when their damage
+ * lies at different offsets.  This call corrects per byte position instead.  Chunks, entries, basis
+ * and block_avail mean what they mean for sec_decode_check_batch: the first k entries are the basis
+ * in any order, the rest check rows, bytes past an entry's avail read as zero and nothing past them
+ * is read.  For every position p in [0, B) the n bytes at p are a column, and the call does to it
+ * exactly what sec_check_locate says of it:
+ *   -1, a code word        nothing to correct;
+ *   a check-row entry      counted as corrected; the output is unaffected;
+ *   a basis entry          that entry's byte is replaced by the one value that makes the column a
+ *                          code word; counted as corrected;
+ *   -2 (every bad position when n - k < 2)   open: left as held.
+ * `out` receives what sec_decode_batch_ex would write from the basis AFTER those replacements:
+ * k*B - padlen bytes at out + out_off and nothing past them.  At open positions it holds the decode
+ * of the basis as held, the bytes sec_decode_check_batch writes there.  results[c] (8-byte aligned)
+ * is chunk c's sec_cor_result.  entry_hits (nullable) has one uint32_t per entry, in the caller's
+ * order: the positions at which that entry was the one changed; every entry of the call is
+ * written, zero included.  Nothing is ever written to the blocks; every call starts from clean
+ * state.  A chunk with n == k is a plain decode and is reported consistent.
+ * What it promises.  The code has distance n - k + 1.  With n - k >= 2 a position where at most
+ * one held byte is wrong is always put right.  With n - k >= 3 a position where two are wrong is
+ * always reported open.  With n - k = 2 a position where two are wrong may be attributed to a
+ * third entry (two errors are never a code word, but can look like one error elsewhere).
+ * The call always takes its own kernel (sec_decode_correct_kernel): there is no bit-sliced form,
+ * and sec_ctx_check_methods, sec_ctx_decode_paths and sec_ctx_decode_methods do not count it;
+ * sec_ctx_host_paths counts a SEC_F_HOST call as staged.
+ * Aliasing: sec_decode_batch's rule (no output range may overlap any block of the call).
+ * Flags: none or SEC_F_ASYNC (device pointers); SEC_F_HOST (host pointers) is ALWAYS staged
+ * through pinned slabs as sec_decode_check_batch's: n*B bytes per chunk are gathered ONCE, and the
+ * output, the results and the hits are scattered back.  SEC_F_HOST with SEC_F_ASYNC,
+ * SEC_F_RECOVER and any other flag are SEC_EINVAL.
+ * Errors, all before any device work, in sec_decode_check_batch's order: SEC_EINVAL a NULL array,
+ * NULL results, NULL `out` where a chunk has bytes to write, n < 0 or a NULL context; SEC_EKM;
+ * SEC_ENBLOCKS; SEC_ESHARENUM; SEC_EDUPSHARE; SEC_EPADLEN; SEC_ESIZE.
+ * sec_timing_collect kind 8 times this call's kernels. */
+typedef struct sec_cor_result {
+    uint64_t first;      /* lowest position whose held bytes are no code word; UINT64_MAX: consistent */
+    uint64_t first_open; /* lowest position that no single-entry change explains; UINT64_MAX: none    */
+    uint32_t corrected;  /* positions where one entry was changed to reach a code word                */
+    uint32_t open;       /* positions that are no code word and were left as held                     */
+} sec_cor_result; /* 24 bytes */
+
+int sec_decode_correct_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t nchunks,
+                             const int32_t *sharenums, const uint64_t *block_offs,
+                             const uint64_t *block_avail, const uint8_t *blocks, uint8_t *out,
+                             sec_cor_result *results, uint32_t *entry_hits, unsigned flags);
 
 /* ---- repair + check: regenerate lost pieces and check the spare ones in one pass ---------------
  * A repair runs because a miner is gone, and the caller usually still reaches more than k of the

@@ -77,6 +77,11 @@ class sec_chk_result(ctypes.Structure):
     _fields_ = [("first", ctypes.c_uint64), ("nbad", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
+class sec_cor_result(ctypes.Structure):
+    _fields_ = [("first", ctypes.c_uint64), ("first_open", ctypes.c_uint64), ("corrected", ctypes.c_uint32),
+                ("open", ctypes.c_uint32)]
+
+
 # numpy mirrors of the descriptor structs (same layout: 4 x u64 + 2 x i32 = 40 B)
 ENC_DTYPE = np.dtype([("in_off", "<u8"), ("n", "<u8"), ("parity_off", "<u8"), ("parity_stride", "<u8"),
                       ("k", "<i4"), ("m", "<i4")], align=True)
@@ -92,6 +97,8 @@ RCHK_DTYPE = np.dtype([("B", "<u8"), ("slot0", "<u8"), ("tgt0", "<u8"), ("ntarge
                        ("m", "<i4")], align=True)  # sec_rchk_chunk
 CHK_RESULT_DTYPE = np.dtype([("first", "<u8"), ("nbad", "<u4"), ("pad", "<u4")], align=True)  # sec_chk_result
 CHK_CONSISTENT = 0xFFFFFFFFFFFFFFFF  # sec_chk_result.first of a consistent chunk
+COR_RESULT_DTYPE = np.dtype([("first", "<u8"), ("first_open", "<u8"), ("corrected", "<u4"), ("open", "<u4")],
+                            align=True)  # sec_cor_result; first / first_open: CHK_CONSISTENT when there is none
 MSG_DTYPE = np.dtype([("addr", "<u8"), ("len", "<u8"), ("avail", "<u8")], align=True)
 COPY_DTYPE = np.dtype([("dst", "<u8"), ("src", "<u8"), ("len", "<u8")], align=True)  # sec_copy
 
@@ -108,6 +115,7 @@ assert CHK_DTYPE.itemsize == ctypes.sizeof(sec_chk_chunk) == 32
 assert DCHK_DTYPE.itemsize == ctypes.sizeof(sec_dchk_chunk) == 48
 assert RCHK_DTYPE.itemsize == ctypes.sizeof(sec_rchk_chunk) == 40
 assert CHK_RESULT_DTYPE.itemsize == ctypes.sizeof(sec_chk_result) == 16
+assert COR_RESULT_DTYPE.itemsize == ctypes.sizeof(sec_cor_result) == 24
 
 # every symbol include/storb_ec.h declares: name -> (restype, argtypes)
 _vp = ctypes.c_void_p
@@ -138,6 +146,8 @@ _SIGS = {
     "sec_check_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint]),
     "sec_decode_check_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               ctypes.c_uint]),
+    "sec_decode_correct_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                ctypes.c_uint]),
     "sec_repair_check_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               _vp, ctypes.c_uint]),
     "sec_check_locate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,

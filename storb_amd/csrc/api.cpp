@@ -338,6 +338,7 @@ struct Plan {
     int64_t nsyn = 0, ndirect = 0, nfused = 0;  // decode: chunks with a lost primary, by method
     int64_t nrow_bs = 0, nrow_direct = 0;  // row operations: the chunks Op::bs_judged, by the kernels they took
     uint64_t nflags = 0;                        // check: flag words of the whole call
+    uint64_t ncnt = 0;                          // decode + correct: counter words behind the flag words
 };
 
 // Device-resident GF coefficient tables (5 dwords per coefficient), keyed by
@@ -716,14 +717,14 @@ struct sec_ctx {
     hipStream_t own = nullptr;
     hipStream_t ext = nullptr;
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[8];  // by timing kind
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[9];  // by timing kind
     std::vector<hipEvent_t> ev_pool;
     hipEvent_t stop_ev = nullptr;  // between timing_begin and timing_end of an attached launch
     PinBuf pin{nullptr, 0, false};  // metadata image staging (its own, not pooled: small, every call)
     hipEvent_t pin_ev = nullptr, meta_ev = nullptr;
     TableCache enc_tabs, dec_tabs;
     Plan enc_plan, dec_plan, sha_plan, bn_plan;
-    RowOpState row_ops[4];  // repair, check, decode + check, repair + check (by their Op::kId)
+    RowOpState row_ops[5];  // repair, check, decode + check, repair + check, decode + correct (by their Op::kId)
     DevBuf bn_scratch;  // host-mode staging of sec_bn_modexp / mulmod operands
     DevBuf bn_part;     // partial residues of segmented reductions (one region per slot)
     DevBuf syn;         // syndrome rows of device-mode syndrome decodes
@@ -1787,6 +1788,8 @@ int launch_decode_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
 // and its RowChunk view, the device descriptor and slots the tile kernels take, the order of its
 // precondition errors (screen_first over the whole batch, then screen chunk by chunk), its timing
 // kind, and, in a base struct per family (CheckBsFamily, RepairBsFamily), its bit-sliced kernel.
+// A fifth, decode + correct (DecodeCorrectOp), is decode + check with kernels, words and results of
+// its own (kCorrects): it judges every position's column instead of comparing whole rows.
 
 // A chunk of any of the four, in common terms (fields an operation lacks are 0)
 struct RowChunk {
@@ -1807,12 +1810,15 @@ struct RowArgs {
     sec_chk_result *results;
     uint8_t *row_bad, *column;
     unsigned flags;
+    sec_cor_result *cor;  // decode + correct: its results and (nullable) per-entry hits
+    uint32_t *hits;
 };
 
 // What a descriptor is made from
 struct RowInfo {
     uint32_t B, k, ns, nr, tab, slot0, tgt0, flag0, valid;  // ns stored rows, nr compared rows
     uint64_t out_off, nout;                                 // decode + check: the chunk's output
+    uint32_t cnt0;                                          // decode + correct: CorDesc::cnt0
 };
 
 sec::ChkDesc chk_desc(const RowInfo &r, uint32_t res, uint32_t cslot0)
@@ -1831,6 +1837,7 @@ int check_held(const RowChunk &c, const RowArgs &a, const int32_t *targets = nul
 struct CheckBsFamily {
     using BsDesc = sec::CbsDesc;
     static constexpr const char *kBsKernel = "sec_check_bs_kernel";
+    static constexpr bool kCorrects = false;
     static bool bs_judged(const RowChunk &c) { return c.n > c.k; }
     static int bs_shape(const Options &o, const RowChunk &c, const int32_t *sn, const uint64_t *avail, bool copies)
     {
@@ -1848,6 +1855,7 @@ struct CheckBsFamily {
 struct RepairBsFamily {
     using BsDesc = sec::RbsDesc;
     static constexpr const char *kBsKernel = "sec_repair_bs_kernel";
+    static constexpr bool kCorrects = false;
     static bool bs_judged(const RowChunk &c) { return c.nt >= 1; }
     static int bs_shape(const Options &o, const RowChunk &c, const int32_t *sn, const uint64_t *avail, bool)
     {
@@ -1954,6 +1962,28 @@ struct DecodeCheckOp : CheckBsFamily {
             return SEC_EPADLEN;
         return c.B >= (1ull << 31) ? SEC_ESIZE : SEC_OK;
     }
+};
+
+// Decode + correct: decode + check's chunks, screening, table and staging; its own kernels (never the
+// bit-sliced one: bs_judged), descriptor, words and results.  SEC_F_RECOVER is no flag of it.
+struct DecodeCorrectOp : DecodeCheckOp {
+    using Desc = sec::CorDesc;
+    using Slots = sec::CorSlots;
+    static constexpr int kId = 4, kTiming = 8;
+    static constexpr bool kCorrects = true;
+    static constexpr const char *kTile = "sec_decode_correct_kernel", *kTail = "sec_decode_correct_tail";
+    static bool bs_judged(const RowChunk &) { return false; }
+    static Desc desc(const RowInfo &r, uint32_t res, uint32_t cslot0)
+    {
+        return {r.out_off, r.nout, r.B, r.k, r.ns, r.nr, r.tab, r.slot0, r.flag0, r.valid, r.cnt0, res, cslot0, 0};
+    }
+    static Slots slots(const DevBuf &m, const SubPlan &sp, uint32_t *flags)
+    {
+        return {m.as<uint64_t>(sp.off_soff), m.as<uint32_t>(sp.off_savail), m.as<uint32_t>(sp.off_srow),
+                m.as<uint32_t>(sp.off_mrow), m.as<uint32_t>(sp.off_cpos), m.as<uint32_t>(sp.off_echunk), flags};
+    }
+    // rows per group of the chunk's tiles: the least the kernel is built for that holds all its rows
+    static int group_rows(int rows) { return rows <= 2 ? 2 : rows <= 4 ? 4 : 8; }
 };
 
 struct RepairCheckOp : RepairBsFamily {
@@ -2075,7 +2105,7 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
                    const SlotLayout &L, bool host)
 {
     using Desc = typename Op::Desc;
-    constexpr bool separate_cdesc = Op::kChecks && !std::is_same<Desc, sec::ChkDesc>::value;
+    constexpr bool separate_cdesc = Op::kChecks && !Op::kCorrects && !std::is_same<Desc, sec::ChkDesc>::value;
     Plan &plan = ctx->row_ops[Op::kId].plan;
     TableCache &tc = ctx->row_ops[Op::kId].tabs;
     const bool recover = a.flags & SEC_F_RECOVER, digest = a.digests != nullptr;
@@ -2134,7 +2164,7 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         (size_t)ctx->opt[digest ? O_SLAB_BYTES_DIGEST : O_SLAB_BYTES]);
     Image img;
     plan.subs.clear();
-    plan.nflags = 0;
+    plan.nflags = plan.ncnt = 0;
     for (auto [c0, c1] : ranges) {
         SubPlan sp;
         sp.c0 = c0;
@@ -2154,6 +2184,11 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             sp.chk_rows = (uint64_t)(c1 - c0) * sizeof(sec::ChkResult);
             sp.chk_col = sp.chk_rows + nent;
             sp.pay_off = align_up(sp.chk_col + nent, 256);
+            if (Op::kCorrects) {  // the results, then one hits word per entry
+                sp.chk_rows = (uint64_t)(c1 - c0) * sizeof(sec::CorResult);
+                sp.chk_col = sp.chk_rows + nent * 4;
+                sp.pay_off = align_up(sp.chk_col, 256);
+            }
         }
         sp.out_bytes = Op::kStores ? sp.pay_off : sp.chk_col + nent;
         for (int64_t i = c0; i < c1; ++i) {
@@ -2168,6 +2203,7 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             r.slot0 = (uint32_t)soff.size();
             r.tgt0 = (uint32_t)toff.size();
             r.flag0 = (uint32_t)plan.nflags;
+            r.cnt0 = (uint32_t)(2 * (uint64_t)nchunks + plan.ncnt);  // (CorSlots::flags: 2 words per chunk first)
             uint64_t min_avail = c.B;
             for (int e = 0; e < c.n; ++e) {
                 const int from = entry_from(L, i, c.k, e);
@@ -2206,8 +2242,12 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
             descs[i - c0] = Op::desc(r, (uint32_t)(host ? i - c0 : i), (uint32_t)(host ? r.slot0 : c.slot0));
             if (separate_cdesc)
                 cdescs[i - c0] = chk_desc(r, (uint32_t)(host ? i - c0 : i), (uint32_t)(host ? r.slot0 : c.slot0));
-            if (Op::kChecks)
+            if (Op::kCorrects) {
+                plan.nflags += 2;
+                plan.ncnt += 2 + (uint64_t)c.n;
+            } else if (Op::kChecks) {
                 plan.nflags += 1 + r.nr;
+            }
             for (int t = 0; t < c.nt; ++t) {
                 const uint64_t to = host ? sp.out_bytes + (uint64_t)t * c.B : a.target_offs[c.tgt0 + t];
                 if (digest) {
@@ -2230,7 +2270,10 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
                 continue;
             }
             // (a chunk with no row and nothing to copy has no work)
-            if (r.ns + r.nr > 0 || (Op::kDecodes && !recover && r.nout > 0))
+            if constexpr (Op::kCorrects) {  // one tile per run of positions, all rows
+                if (r.ns + r.nr > 0 || r.nout > 0)
+                    add_work(bins, tail, (uint32_t)(i - c0), c.B, valid, Op::group_rows((int)(r.ns + r.nr)), c.k, true);
+            } else if (r.ns + r.nr > 0 || (Op::kDecodes && !recover && r.nout > 0))
                 add_work(bins, tail, (uint32_t)(i - c0), c.B, valid, (int)(r.ns + r.nr), c.k, true, false,
                          dec_small_kb(c.k));
         }
@@ -2273,7 +2316,7 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         sp.off_soff = img.put(soff.data(), soff.size() * 8);
         plan.subs.push_back(std::move(sp));
     }
-    if (plan.nflags >= UINT32_MAX)
+    if (plan.nflags + plan.ncnt >= UINT32_MAX)
         return SEC_EINVAL;
     RC(upload_plan(ctx, plan, img, tc, pending));
     plan.gen = tc.gen;
@@ -2310,16 +2353,35 @@ int launch_row_sub(sec_ctx *ctx, const SubPlan &sp, bool host, const uint8_t *bl
         if (e)
             return hip_fail((hipError_t)e, Op::kBsKernel);
     }
-    for (const Group &g : sp.groups) {
-        int e = sec_launch_rows(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
-                                g.mfma);
-        if (e)
-            return hip_fail((hipError_t)e, Op::kTile);
-    }
-    if (sp.ntail) {
-        int e = sec_launch_rows_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
+    if constexpr (Op::kCorrects) {  // its own kernels; results: sec::CorResult, row_bad: the hits words
+        for (const Group &g : sp.groups) {
+            int e = sec_launch_correct(g.rows, blocks, out, dd, dt + g.first, g.count, tabs, sl, s);
+            if (e)
+                return hip_fail((hipError_t)e, Op::kTile);
+        }
+        int e =
+            sec_launch_correct_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
         if (e)
             return hip_fail((hipError_t)e, Op::kTail);
+        e = sec_launch_correct_final(dd, sp.nentries, sl, (sec::CorResult *)results, (uint32_t *)row_bad, s);
+        if (e)
+            return hip_fail((hipError_t)e, "sec_decode_correct_final");
+        if (timed)
+            RC(timing_end(ctx, t0, Op::kTiming, s));
+        return SEC_OK;
+    } else {
+        for (const Group &g : sp.groups) {
+            int e = sec_launch_rows(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
+                                    g.mfma);
+            if (e)
+                return hip_fail((hipError_t)e, Op::kTile);
+        }
+        if (sp.ntail) {
+            int e =
+                sec_launch_rows_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
+            if (e)
+                return hip_fail((hipError_t)e, Op::kTail);
+        }
     }
     if (Op::kChecks) {
         const sec::ChkSlots csl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
@@ -2454,9 +2516,10 @@ template <class Op>
 int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, const RowArgs &a)
 {
     using Chunk = typename Op::Chunk;
-    const unsigned allowed = SEC_F_HOST | SEC_F_ASYNC | (Op::kDecodes ? SEC_F_RECOVER : 0u);
+    const unsigned allowed = SEC_F_HOST | SEC_F_ASYNC | (Op::kDecodes && !Op::kCorrects ? SEC_F_RECOVER : 0u);
+    const bool has_results = Op::kCorrects ? a.cor != nullptr : a.results != nullptr;
     if (!ctx || nchunks < 0 ||
-        (nchunks > 0 && (!chunks || !a.sharenums || !a.block_offs || (Op::kChecks && !a.results))) ||
+        (nchunks > 0 && (!chunks || !a.sharenums || !a.block_offs || (Op::kChecks && !has_results))) ||
         (a.flags & ~allowed) || ((a.flags & SEC_F_HOST) && (a.flags & SEC_F_ASYNC)))
         return SEC_EINVAL;
     if (nchunks == 0)
@@ -2534,13 +2597,16 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
     if (Op::kChecks) {
         // every call starts from clean flag words (0xFFFFFFFF: no position yet, row agrees), whatever
         // the last call on this plan found
-        RC(st.flags.ensure((size_t)plan.nflags * 4));
+        RC(st.flags.ensure((size_t)(plan.nflags + plan.ncnt) * 4));
         CK(hipMemsetAsync(st.flags.p, 0xFF, (size_t)plan.nflags * 4, ctx->stream()));
+        if (plan.ncnt)  // decode + correct: the counters behind them start at zero
+            CK(hipMemsetAsync(st.flags.as<uint32_t>() + plan.nflags, 0, (size_t)plan.ncnt * 4, ctx->stream()));
     }
 
     if (!host) {
-        RC(launch_row_sub<Op>(ctx, plan.subs[0], false, a.blocks, a.out, a.digests, (sec::ChkResult *)a.results,
-                              a.row_bad, a.column, ctx->stream()));
+        RC(launch_row_sub<Op>(ctx, plan.subs[0], false, a.blocks, a.out, a.digests,
+                              Op::kCorrects ? (sec::ChkResult *)a.cor : (sec::ChkResult *)a.results,
+                              Op::kCorrects ? (uint8_t *)a.hits : a.row_bad, a.column, ctx->stream()));
         if (!(a.flags & SEC_F_ASYNC))
             CK(hipStreamSynchronize(ctx->stream()));
         return SEC_OK;
@@ -2568,12 +2634,16 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
         }
     };
     auto scatter = [&](const SubPlan &sp, char *stage, std::vector<sec::CopyJob> &jobs) {
-        if (Op::kChecks)
+        if (Op::kCorrects)
+            jobs.push_back(sec::CopyJob{a.cor + sp.c0, stage, (uint64_t)(sp.c1 - sp.c0) * sizeof(sec_cor_result)});
+        else if (Op::kChecks)
             jobs.push_back(
                 sec::CopyJob{a.results + sp.c0, stage, (uint64_t)(sp.c1 - sp.c0) * sizeof(sec_chk_result)});
         uint64_t o = 0, b = sp.pay_off, g = sp.dig_off;
         for (int64_t i = sp.c0; i < sp.c1; ++i) {
             const RowChunk c = Op::view(chunks[i]);
+            if (Op::kCorrects && a.hits)
+                jobs.push_back(sec::CopyJob{a.hits + c.slot0, stage + sp.chk_rows + o * 4, (uint64_t)c.n * 4});
             if (Op::kChecks && a.row_bad)
                 jobs.push_back(sec::CopyJob{a.row_bad + c.slot0, stage + sp.chk_rows + o, (uint64_t)c.n});
             if (Op::kChecks && a.column)
@@ -2602,7 +2672,8 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
     };
     auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
         return launch_row_sub<Op>(ctx, sp, true, din, dout, dout + sp.dig_off, (sec::ChkResult *)dout,
-                                  a.row_bad ? dout + sp.chk_rows : nullptr, a.column ? dout + sp.chk_col : nullptr, s);
+                                  a.row_bad || a.hits ? dout + sp.chk_rows : nullptr,
+                                  a.column ? dout + sp.chk_col : nullptr, s);
     };
     RC(run_pipeline(ctx, plan, gather, scatter, launch));
     if (Op::kChecks && a.column)
@@ -2954,7 +3025,7 @@ const char *sec_option_name(int index)
 
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches)
 {
-    if (!ctx || kind < 0 || kind > 7 || !total_ms || !launches)
+    if (!ctx || kind < 0 || kind > 8 || !total_ms || !launches)
         return SEC_EINVAL;
     RC(set_dev(ctx));
     double tot = 0;
@@ -4349,6 +4420,19 @@ int sec_decode_check_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t n
     return row_op<DecodeCheckOp>(ctx, chunks, nchunks,
                                  RowArgs{sharenums, block_offs, block_avail, blocks, nullptr, nullptr, out, nullptr,
                                          results, row_bad, column, flags});
+}
+
+int sec_decode_correct_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                             const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
+                             uint8_t *out, sec_cor_result *results, uint32_t *entry_hits, unsigned flags)
+{
+    static_assert(sizeof(sec_cor_result) == 24 && sizeof(sec::CorResult) == 24 && sizeof(sec::CorDesc) == 64,
+                  "ABI layout");
+    RowArgs a{sharenums, block_offs, block_avail, blocks, nullptr, nullptr, out, nullptr,
+              nullptr, nullptr, nullptr, flags};
+    a.cor = results;
+    a.hits = entry_hits;
+    return row_op<DecodeCorrectOp>(ctx, chunks, nchunks, a);
 }
 
 int sec_repair_check_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,

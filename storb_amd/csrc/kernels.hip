@@ -1643,6 +1643,362 @@ __global__ __launch_bounds__(256) void sec_repair_check_tail(const u8 *__restric
     }
 }
 
+// ---- decode + correct: reassemble, and put right one wrong entry per byte position -------------
+// The chunk's table is decode + check's (rows 0 .. e-1 the missing primaries, rows e .. e+nr-1 the
+// check rows, over the k basis slots).  At every position the n held bytes are a column, and the
+// kernel does to it what sec_check_locate (gf_host.hpp check_locate) says of it: a code word is
+// decoded as it is; one differing check row is that row's own error (the output is unaffected);
+// all nr differing with d_j = R[j][s] * v for one basis slot s means slot s is wrong by v, and the
+// output is the decode of the basis with that byte put right; anything else is open and decoded as
+// held.  A sibling of dchk_main, not a change to it (DESIGN §5 "Corrected decode").
+//
+// Two levels.  A tile is (chunk, t0) and takes ALL rows of its positions, in groups of R rows
+// (a position's verdict needs every check row, and the fix every stored row).  A lane with 16
+// whole positions below `valid` first forms the check deltas of every group with the v_perm
+// products and ORs them (cor_rows: 8-slot load batches, coalesced entry by entry); with the OR zero
+// it has located nothing and goes on to store the recovered rows and copy the present primaries, a
+// plain decode.  Only a lane whose OR is nonzero takes its 16 positions byte by byte (cor_pos),
+// and stores nothing as a vector: no output byte is written twice, so no store has to be ordered
+// after another.  The lane that straddles `valid`, the ragged end [valid, B) and the chunks too
+// small for a tile go byte by byte as well.
+//
+// cor_byte keeps nothing per row or per slot beyond one group of R rows and one batch of 16 slot
+// bytes (nr reaches 32, k 64: no dynamically indexed array, no scratch): the deltas are formed
+// group by group, counted, and rows 0 and 1 kept.  The slot search needs no division:
+// d_0 = R[0][s] v and d_1 = R[1][s] v  <=>  R[1][s] d_0 = R[0][s] d_1 (R[0][s] != 0), two products
+// by constants the table already has, and at most one s passes since every 2 x 2 minor of the
+// matrix is nonzero.  v = d_0 / R[0][s] through the exp/log tables (R[0][s] is byte 1 of the
+// table's first dword), and rows 2 .. nr-1 are formed again to confirm.
+//
+// Counters are ordinary vector atomics on the call's words (CorDesc::flag0 / cnt0), summed over
+// the wave's active lanes first: a wholly corrupt piece makes every position hit the same words.
+struct CorVerdict {
+    int hit;    // the entry (kernel order: basis slots, then check rows) that was changed, or -1
+    bool bad;   // the column is no code word
+    bool open;  // ... and no single-entry change explains it
+};
+
+__device__ __forceinline__ u32 cor_lane()
+{
+    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+}
+
+// *w += the number of active lanes with pred
+__device__ __forceinline__ void wave_count(u32 *w, bool pred)
+{
+    const u64 m = __ballot(pred);
+    if (pred && cor_lane() == (u32)__builtin_ctzll(m))
+        atomicAdd(w, (u32)__builtin_popcountll(m));
+}
+
+__device__ __forceinline__ void min_word(u32 *w, u32 v)
+{
+    if (*(volatile u32 *)w > v)
+        atomicMin(w, v);
+}
+
+// WAVE: every lane of the wave is on the same chunk (the tile kernel), so their counts go through
+// one atomic per word; else (the tail kernel: a lane per item of any chunk) each lane adds its own.
+template <bool WAVE>
+__device__ __forceinline__ void cor_tally(const sec::CorDesc &d, const sec::CorSlots sl, u32 p, const CorVerdict v)
+{
+    u32 *f = sl.flags + d.flag0, *c = sl.flags + d.cnt0;
+    if (v.bad)
+        min_word(f, p);
+    if (v.open)
+        min_word(f + 1, p);
+    if constexpr (!WAVE) {
+        if (v.hit >= 0) {
+            atomicAdd(c, 1u);
+            atomicAdd(c + 2 + v.hit, 1u);
+        }
+        if (v.open)
+            atomicAdd(c + 1, 1u);
+        return;
+    }
+    wave_count(c, v.hit >= 0);
+    wave_count(c + 1, v.open);
+    // one atomic per distinct entry among the wave's active lanes
+    // (the loop is wave-uniform: `rem` is a ballot, so no lane leaves it ahead of another)
+    u64 rem = __ballot(v.hit >= 0);
+    while (rem) {
+        const u32 lead = (u32)__builtin_ctzll(rem);
+        const int h = __builtin_amdgcn_readlane(v.hit, (int)lead);
+        const u64 m = __ballot(v.hit == h);
+        if (cor_lane() == lead)
+            atomicAdd(c + 2 + h, (u32)__builtin_popcountll(m));
+        rem &= ~m;
+    }
+}
+
+// Position p of a chunk, whole: the verdict on its column and every output byte there.  Rows go in
+// groups of R and the slots' bytes in batches of kBatch loads issued together (repair_ragged: a loop
+// of dependent single-byte loads costs one memory latency per slot and row).
+template <int R>
+__device__ __forceinline__ CorVerdict cor_byte(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                               const sec::CorDesc &d, const u32 *__restrict__ tabs,
+                                               const sec::CorSlots sl, u32 p)
+{
+    const u32 k = d.k, e = d.e, nr = d.nr, nrows = e + nr;
+    auto tab = [&](u32 c, u32 r) { return tabs + d.tab + (c * nrows + r) * sec::kTabDwords; };
+    // acc[r] = XOR_c T[c][min(row0 + r, rlast)] * (slot c's byte, slot `fix` changed by `val`)
+    auto rows = [&](u32 (&acc)[R], u32 row0, u32 rlast, u32 fix, u32 val) {
+        for (u32 c0 = 0; c0 < k; c0 += kBatch) {
+            u32 x[kBatch];
+            load_slot_bytes(x, blocks, sl, d.slot0, c0, k, p);
+#pragma unroll
+            for (u32 q = 0; q < kBatch; ++q)
+                if (c0 + q < k) {
+                    const u32 xv = x[q] ^ (c0 + q == fix ? val : 0u);
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+                        acc[r] ^= gf_mul_byte(tab(c0 + q, min(row0 + (u32)r, rlast)), xv);
+                }
+        }
+    };
+    // the deltas of check rows g0 .. g0 + R - 1 (those past nr - 1 repeat row nr - 1)
+    auto deltas = [&](u32 (&acc)[R], u32 g0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const u32 ent = d.slot0 + k + min(g0 + (u32)r, nr - 1);
+            acc[r] = p < sl.avail[ent] ? (u32)blocks[sl.off[ent] + p] : 0u;
+        }
+        rows(acc, e + g0, nrows - 1, ~0u, 0u);
+    };
+    u32 cnt = 0, last = 0, d0 = 0, d1 = 0;
+    for (u32 g0 = 0; g0 < nr; g0 += R) {
+        u32 acc[R];
+        deltas(acc, g0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const u32 j = g0 + r;
+            if (j < nr && acc[r]) {
+                ++cnt;
+                last = j;
+            }
+            d0 = j == 0 ? acc[r] : d0;
+            d1 = j == 1 ? acc[r] : d1;
+        }
+    }
+    CorVerdict v{-1, cnt != 0, false};
+    u32 fix = ~0u, val = 0;  // basis slot put right, by which value
+    if (cnt == 0) {
+    } else if (nr < 2) {
+        v.open = true;
+    } else if (cnt == 1) {
+        v.hit = (int)(k + last);
+    } else if (cnt == nr) {
+        u32 s = 0;
+        for (; s < k; ++s) {
+            const u32 r0 = (tab(s, e)[0] >> 8) & 0xFFu;  // R[0][s]
+            if (r0 && gf_mul_byte(tab(s, e + 1), d0) == gf_mul_byte(tab(s, e), d1)) {
+                val = c_gf.exp[(u32)c_gf.log[d0] + 255u - (u32)c_gf.log[r0]];
+                break;
+            }
+        }
+        bool ok = s < k;
+        for (u32 g0 = 0; ok && nr > 2 && g0 < nr; g0 += R) {  // rows 2 .. nr - 1 confirm the slot
+            u32 acc[R];
+            deltas(acc, g0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const u32 j = g0 + r;
+                if (j >= 2 && j < nr && gf_mul_byte(tab(s, e + j), val) != acc[r])
+                    ok = false;
+            }
+        }
+        if (ok) {
+            fix = s;
+            v.hit = (int)s;
+        } else {
+            v.open = true;
+        }
+    } else {
+        v.open = true;
+    }
+    u8 *dst = out + d.out_off + p;
+    for (u32 c0 = 0; c0 < k; c0 += kBatch) {
+        u32 x[kBatch];
+        load_slot_bytes(x, blocks, sl, d.slot0, c0, k, p);
+#pragma unroll
+        for (u32 q = 0; q < kBatch; ++q)
+            if (c0 + q < k) {
+                const u32 orow = sl.row[d.slot0 + c0 + q];
+                if (orow != 0xFFFFFFFFu && (u64)orow * d.B + p < d.n)
+                    dst[(u64)orow * d.B] = (u8)(x[q] ^ (c0 + q == fix ? val : 0u));
+            }
+    }
+    for (u32 g0 = 0; g0 < e; g0 += R) {
+        u32 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            acc[r] = 0u;
+        rows(acc, g0, e - 1, fix, val);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (g0 + r < e) {
+                const u32 orow = sl.miss[d.slot0 + g0 + r];
+                if ((u64)orow * d.B + p < d.n)
+                    dst[(u64)orow * d.B] = (u8)acc[r];
+            }
+    }
+    return v;
+}
+
+template <int R, bool WAVE = true>
+__device__ __forceinline__ void cor_pos(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
+                                        const u32 *__restrict__ tabs, const sec::CorSlots sl, u32 p)
+{
+    cor_tally<WAVE>(d, sl, p, cor_byte<R>(blocks, out, d, tabs, sl, p));
+}
+
+constexpr int kCorBatch = 8;  // slots per load batch of cor_rows
+
+// acc[r] = XOR_c T[c][min(row0 + r, rlast)] * slot_c[pos .. pos + 16): R rows of the chunk's table
+// from row0 on (a group's rows past rlast repeat row rlast; the caller drops them)
+template <int R>
+__device__ __forceinline__ void cor_rows(u32x4 (&acc)[R], const u8 *__restrict__ blocks, const sec::CorDesc &d,
+                                         const u32 *__restrict__ tabs, const sec::CorSlots sl, u32 pos, u32 row0,
+                                         u32 rlast)
+{
+    const u32 k = d.k, nrows = d.e + d.nr;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        acc[r] = u32x4{0u, 0u, 0u, 0u};
+    const u32 *rt[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        rt[r] = tabs + d.tab + min(row0 + (u32)r, rlast) * sec::kTabDwords;
+    const u32 tstep = nrows * sec::kTabDwords;
+#pragma unroll 1
+    for (u32 c0 = 0; c0 < k; c0 += kCorBatch) {
+        u32x4 xs[kCorBatch][1];
+#pragma unroll
+        for (int c = 0; c < kCorBatch; ++c)
+            if (c0 + c < k)
+                xs[c][0] = load16(blocks + sl.off[d.slot0 + c0 + c] + pos);
+#pragma unroll
+        for (int c = 0; c < kCorBatch; ++c)
+            if (c0 + c < k) {
+                const Sel<1> s(xs[c]);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const u32 *t = rt[r] + (c0 + c) * tstep;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w)
+                        acc[r][w] = xor3(acc[r][w], perm(t[1], t[0], s.s0[0][w]), perm(t[3], t[2], s.s1[0][w])) ^
+                                    perm(t[4], t[4], s.s2[0][w]);
+                }
+            }
+    }
+}
+
+// A lane's 16 whole positions [pos, pos + 16), all below `valid`
+template <int R>
+__device__ __forceinline__ void cor_main(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
+                                         u32 pos, const u32 *__restrict__ tabs, const sec::CorSlots sl)
+{
+    const u32 k = d.k, e = d.e, nr = d.nr;
+    u32x4 acc[R];
+    u32 any = 0;
+#pragma unroll 1
+    for (u32 g0 = 0; g0 < nr; g0 += R) {
+        cor_rows<R>(acc, blocks, d, tabs, sl, pos, e + g0, e + nr - 1);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (g0 + r < nr) {
+                const u32x4 st = load16(blocks + sl.off[d.slot0 + k + g0 + r] + pos);
+#pragma unroll
+                for (int w = 0; w < 4; ++w)
+                    any |= acc[r][w] ^ st[w];
+            }
+    }
+    if (any) {
+        for (u32 i = 0; i < (u32)sec::kLaneBytes; ++i)
+            cor_pos<R>(blocks, out, d, tabs, sl, pos + i);
+        return;
+    }
+    u8 *dst = out + d.out_off + pos;
+#pragma unroll 1
+    for (u32 g0 = 0; g0 < e; g0 += R) {
+        cor_rows<R>(acc, blocks, d, tabs, sl, pos, g0, e - 1);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (g0 + r < e)
+                store16<SEC_DEC_ST>(dst + (u64)sl.miss[d.slot0 + g0 + r] * d.B, acc[r]);
+    }
+#pragma unroll 1
+    for (u32 c0 = 0; c0 < k; c0 += 4) {
+        u32x4 x[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c0 + c < k && sl.row[d.slot0 + c0 + c] != 0xFFFFFFFFu)
+                x[c] = load16(blocks + sl.off[d.slot0 + c0 + c] + pos);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c0 + c < k && sl.row[d.slot0 + c0 + c] != 0xFFFFFFFFu)
+                store16<SEC_DEC_ST>(dst + (u64)sl.row[d.slot0 + c0 + c] * d.B, x[c]);
+    }
+}
+
+// R: rows per group (the plan picks the least of 2, 4, 8 that holds the chunk's e + nr rows, else 8)
+template <int R>
+__global__ __launch_bounds__(sec::kLanes) void sec_decode_correct_kernel(const u8 *__restrict__ blocks,
+                                                                         u8 *__restrict__ out,
+                                                                         const sec::CorDesc *__restrict__ descs,
+                                                                         const sec::Tile *__restrict__ tiles,
+                                                                         const u32 *__restrict__ tabs,
+                                                                         const sec::CorSlots sl)
+{
+    const sec::Tile tl = sec::own_tile(tiles);
+    const sec::CorDesc d = descs[tl.chunk];
+    const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
+    if (t + sec::kLaneBytes <= d.valid) {
+        cor_main<R>(blocks, out, d, t, tabs, sl);
+    } else if (t < d.valid) {  // the lane that straddles `valid`
+        for (u32 p = t; p < d.valid; ++p)
+            cor_pos<R>(blocks, out, d, tabs, sl, p);
+    }
+    if (tl.ntail)
+        for (u32 i = ragged_lane0(d.valid, tl.t0); i < tl.ntail; i += blockDim.x)
+            cor_pos<R>(blocks, out, d, tabs, sl, d.valid + i);
+}
+
+// One thread per (chunk, position) of the chunks too small for a tile (valid < 16)
+__global__ __launch_bounds__(256) void sec_decode_correct_tail(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                               const sec::CorDesc *__restrict__ descs,
+                                                               const sec::TailItem *__restrict__ items, u32 nitems,
+                                                               const u32 *__restrict__ tabs, const sec::CorSlots sl)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nitems)
+        return;
+    const sec::TailItem it = items[i];
+    const sec::CorDesc d = descs[it.chunk];
+    cor_pos<4, false>(blocks, out, d, tabs, sl, it.t);
+}
+
+// One thread per entry, after the kernels above: the entry's counter into hits (the caller's
+// order); the chunk's first entry also turns the chunk's words into its result.
+__global__ __launch_bounds__(256) void sec_decode_correct_final(const sec::CorDesc *__restrict__ descs, u32 nentries,
+                                                                const sec::CorSlots sl,
+                                                                sec::CorResult *__restrict__ results,
+                                                                u32 *__restrict__ hits)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nentries)
+        return;
+    const sec::CorDesc d = descs[sl.echunk[i]];
+    const u32 e = i - d.slot0;
+    if (hits)
+        hits[d.cslot0 + sl.cpos[i]] = sl.flags[d.cnt0 + 2 + e];
+    if (e == 0) {
+        const u32 first = sl.flags[d.flag0], fopen = sl.flags[d.flag0 + 1];
+        results[d.res] = sec::CorResult{first == ~0u ? ~(u64)0 : (u64)first, fopen == ~0u ? ~(u64)0 : (u64)fopen,
+                                        sl.flags[d.cnt0], sl.flags[d.cnt0 + 1]};
+    }
+}
+
 // ---- SHA-1 of pieces (storb piece ids, /root/reference/storb/util/piece.py:54-68) ----
 // One lane per message: SHA-1 is a sequential chain of 64-byte compressions, so a
 // message cannot be split; the kernel is latency-bound on each lane's round chain
@@ -2203,4 +2559,37 @@ int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uin
         return hipSuccess;
     return launch(sec_check_final, dim3((nentries + 255) / 256), dim3(256), (hipStream_t)stream, blocks, descs,
                   nentries, sl, results, row_bad, column);
+}
+
+int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::Tile *tiles,
+                       uint32_t ntiles, const uint32_t *tabs, sec::CorSlots sl, void *stream)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    const dim3 grid(ntiles), block(sec::kLanes);
+    hipStream_t s = (hipStream_t)stream;
+    switch (rows) {
+    case 2: return launch(sec_decode_correct_kernel<2>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
+    case 4: return launch(sec_decode_correct_kernel<4>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
+    case 8: return launch(sec_decode_correct_kernel<8>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::TailItem *items,
+                            uint32_t nitems, const uint32_t *tabs, sec::CorSlots sl, void *stream)
+{
+    if (nitems == 0)
+        return hipSuccess;
+    return launch(sec_decode_correct_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out,
+                  descs, items, nitems, tabs, sl);
+}
+
+int sec_launch_correct_final(const sec::CorDesc *descs, uint32_t nentries, sec::CorSlots sl, sec::CorResult *results,
+                             uint32_t *hits, void *stream)
+{
+    if (nentries == 0)
+        return hipSuccess;
+    return launch(sec_decode_correct_final, dim3((nentries + 255) / 256), dim3(256), (hipStream_t)stream, descs,
+                  nentries, sl, results, hits);
 }

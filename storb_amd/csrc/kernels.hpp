@@ -145,6 +145,45 @@ struct DChkSlots {
     uint32_t *flags;        // see ChkDesc::flag0
 };
 
+// One decode + correct chunk, device copy (64 B): DChkDesc's fields with the same meaning (the table,
+// the n entries, row / miss), and the chunk's words in CorSlots::flags.
+struct CorDesc {
+    uint64_t out_off;
+    uint64_t n;
+    uint32_t B;
+    uint32_t k;
+    uint32_t e;
+    uint32_t nr;
+    uint32_t tab;
+    uint32_t slot0;
+    uint32_t flag0;   // flags[flag0]: the first position that is no code word, flags[flag0 + 1]: the first
+                      // open one (atomicMin; 0xFFFFFFFF when none)
+    uint32_t valid;   // as DChkDesc::valid
+    uint32_t cnt0;    // flags[cnt0]: positions corrected, flags[cnt0 + 1]: open, flags[cnt0 + 2 + j]: positions
+                      // at which entry j (basis slots in normalised order, then check rows) was the one changed
+    uint32_t res;     // the chunk's index in the launch's results[]
+    uint32_t cslot0;  // the chunk's first entry in the launch's hits[]
+    uint32_t pad;
+};
+
+struct CorSlots {
+    const uint64_t *off;
+    const uint32_t *avail;
+    const uint32_t *row;
+    const uint32_t *miss;
+    const uint32_t *cpos;    // as ChkSlots
+    const uint32_t *echunk;
+    uint32_t *flags;         // the call's words: [0, 2 * chunks) start as 0xFFFFFFFF, the counters behind as 0
+};
+
+// sec_cor_result's device mirror (include/storb_ec.h)
+struct CorResult {
+    uint64_t first;
+    uint64_t first_open;
+    uint32_t corrected;
+    uint32_t open;
+};
+
 // One repair + check chunk, device copy (40 B): nt lost blocks regenerated from k basis blocks, each
 // a whole B-byte piece at an address of its own, and nr check rows predicted from the same basis and
 // compared with the stored rows.  Its n = k + nr entries in RChkSlots::off / avail are those of its
@@ -401,4 +440,13 @@ int sec_launch_rows_tail(const uint8_t *blocks, uint8_t *out, const Desc *descs,
 // and, for an inconsistent chunk, column[d.cslot0 + ..] (row_bad, column nullable)
 int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uint32_t nentries, sec::ChkSlots slots,
                            sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, void *stream);
+// Decode + correct: sec_decode_correct_kernel over tiles (chunk, t0) that take all rows of their
+// positions in groups of `rows` (2, 4 or 8), its byte-granular tail kernel, and, after both, one
+// thread per entry: the chunks' words into results[d.res] and hits[d.cslot0 + ..] (hits nullable)
+int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::Tile *tiles,
+                       uint32_t ntiles, const uint32_t *tabs, sec::CorSlots slots, void *stream);
+int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::TailItem *items,
+                            uint32_t nitems, const uint32_t *tabs, sec::CorSlots slots, void *stream);
+int sec_launch_correct_final(const sec::CorDesc *descs, uint32_t nentries, sec::CorSlots slots, sec::CorResult *results,
+                             uint32_t *hits, void *stream);
 }

@@ -24,8 +24,9 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (CHK_DTYPE, CHK_RESULT_DTYPE, COPY_DTYPE, DCHK_DTYPE, DEC_DTYPE, ENC_DTYPE, MSG_DTYPE, RCHK_DTYPE,
-                   REP_DTYPE, SEC_F_ASYNC, SEC_F_GPU_PARITY_IDS, SEC_F_HOST, SEC_F_RECOVER, SEC_F_STAGED)
+from ._lib import (CHK_DTYPE, CHK_RESULT_DTYPE, COPY_DTYPE, COR_RESULT_DTYPE, DCHK_DTYPE, DEC_DTYPE, ENC_DTYPE,
+                   MSG_DTYPE, RCHK_DTYPE, REP_DTYPE, SEC_F_ASYNC, SEC_F_GPU_PARITY_IDS, SEC_F_HOST, SEC_F_RECOVER,
+                   SEC_F_STAGED)
 
 
 class Error(Exception):
@@ -109,7 +110,7 @@ def device_count() -> int:
 
 
 _TIMING_KINDS = {"encode": 0, "decode": 1, "sha1": 2, "bignum": 3, "repair": 4, "check": 5,
-                 "decode_check": 6, "repair_check": 7}
+                 "decode_check": 6, "repair_check": 7, "decode_correct": 8}
 
 
 class Engine:
@@ -448,6 +449,49 @@ class Engine:
         mv = memoryview(buf)
         views = [v for it, o in zip(items, rec) for v in self._join_views(it, mv, o)]
         return self._joined(views), self._check_results(items, slot0, res, rb, col)
+
+    def decode_correct_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks, out,
+                             results, *, block_avail: np.ndarray | None = None, entry_hits=None, host: bool = False,
+                             asynchronous: bool = False) -> None:
+        """sec_decode_correct_batch: every byte position's column of each chunk's n entries
+        (DCHK_DTYPE descriptors) judged as ``check_locate`` judges it, and `out` what decode_batch
+        writes from the first k entries after the one wrong basis byte of a position, if any, is
+        put right.  results: one COR_RESULT_DTYPE per chunk; entry_hits (optional): one uint32 per
+        slot entry, the positions at which that entry was the one changed; both where the blocks
+        live.  host: host buffers, always staged, every entry gathered once."""
+        self._row_call(self.lib.sec_decode_correct_batch, DCHK_DTYPE, descs, sharenums, block_offs, block_avail, None,
+                       (blocks, out, results, entry_hits), host=host, asynchronous=asynchronous)
+
+    def decode_correct_host(self, items):
+        """Reassemble host chunks, correcting one wrong block per byte position, in one call.
+
+        items: [(k, m, blocks, sharenums, padlen)] as ``decode_check_host`` takes them.  Returns
+        ``(data, results)``: data = every chunk's k*B - padlen bytes concatenated; results = per
+        chunk ``(first, first_open, corrected, open, hits)``: the lowest position whose column is
+        no code word and the lowest one left open (None: there is none), the counts of corrected
+        and of open positions, and per block of the chunk the positions at which it was the one
+        changed."""
+        for it in items:
+            check_decode_correct_item(*it)
+        if not items:
+            return b"", []
+        sn, bo, _keep, slot0 = self._lay_out_blocks(items)
+        descs = np.zeros(len(items), dtype=DCHK_DTYPE)
+        starts = _decoded_starts(items)
+        for j, (k, m, blocks, _sharenums, padlen) in enumerate(items):
+            descs[j] = (starts[j], len(blocks[0]), padlen, slot0[j], len(blocks), k, m, 0)
+        buf = self._out_buffer(max(starts[-1], 1))
+        res = np.zeros(len(items), dtype=COR_RESULT_DTYPE)
+        hits = np.zeros(sn.size, dtype=np.uint32)
+        self.decode_correct_batch(descs, sn, bo, 0, buf, res, entry_hits=hits, host=True)
+        none = _lib.CHK_CONSISTENT
+        out = []
+        for j, it in enumerate(items):
+            first, fopen = int(res[j]["first"]), int(res[j]["first_open"])
+            out.append((None if first == none else first, None if fopen == none else fopen,
+                        int(res[j]["corrected"]), int(res[j]["open"]),
+                        [int(h) for h in hits[slot0[j]:slot0[j] + len(it[2])]]))
+        return buf[:starts[-1]].tobytes(), out
 
     def repair_check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
                            target_nums: np.ndarray, target_offs: np.ndarray, out, results, *,
@@ -896,6 +940,12 @@ def check_decode_check_item(k: int, m: int, blocks, sharenums, padlen: int) -> N
     GPU work): n equal-length blocks and n sharenums, 1 <= k <= m <= 256, k <= n <= m, sharenums
     in [0, m) and distinct, 0 <= padlen <= k*B.  Raises Error."""
     _check_blocks(k, m, blocks, sharenums, spares=True, padlen=padlen)
+
+
+def check_decode_correct_item(k: int, m: int, blocks, sharenums, padlen: int) -> None:
+    """The decode + correct preconditions for one chunk: check_decode_check_item's, in its order
+    (the library's own checks, raised before any GPU work).  Raises Error."""
+    check_decode_check_item(k, m, blocks, sharenums, padlen)
 
 
 def check_decode_ids_item(k: int, m: int, blocks, sharenums, padlen: int, ids) -> None:

@@ -67,8 +67,8 @@ from pydantic import BaseModel, ConfigDict, Field
 from .constants import MAX_PIECE_SIZE, MIN_PIECE_SIZE, PIECE_LENGTH_OFFSET, PIECE_LENGTH_SCALING
 from .easyfec import Decoder, Encoder, Error
 from .engine import (Engine, EngineGroup, _decoded_len, _decoded_starts, check_decode_check_item,
-                     check_decode_ids_item, check_decode_item, check_locate, check_repair_check_item, choose_blocks,
-                     device_count, get_engine, spread_threads)
+                     check_decode_correct_item, check_decode_ids_item, check_decode_item, check_locate,
+                     check_repair_check_item, choose_blocks, device_count, get_engine, spread_threads)
 
 logger = logging.getLogger(__name__)
 
@@ -81,6 +81,8 @@ __all__ = [
     "decode_chunks_checked", "reconstruct_data_checked", "PieceCheckError", "repair_chunks_checked",
     "repair_pieces_checked", "ChunkIdCheck", "PieceIdError",
     "decode_chunks_id_checked", "reconstruct_data_id_checked", "reconstruct_data_stream_id_checked",
+    "ChunkCorrection", "PieceCorrectionError", "decode_chunks_corrected", "reconstruct_data_corrected",
+    "reconstruct_data_stream_corrected",
 ]
 
 PREFETCH_PIECE_IDS = True  # encode_chunk hashes its pieces on a thread pool (see module doc)
@@ -1208,6 +1210,116 @@ def reconstruct_data_stream_checked(pieces: list[Piece], chunks: list[EncodedChu
         pieces, list(zip(chunks)), window_bytes, decode_chunks_checked, lambda ck: ck.consistent or ck.located,
         lambda ck, seen: PieceCheckError(
             f"Held pieces disagree and no corrupt piece could be named in chunk {ck.chunk_idx}", seen))
+
+
+class ChunkCorrection(BaseModel):
+    """What ``decode_chunks_corrected`` found, and put right, for one chunk."""
+
+    chunk_idx: int
+    checked: int  # pieces checked (the distinct pieces held)
+    consistent: bool  # every held piece agrees with the others: nothing was corrected
+    first_bad_offset: typing.Optional[int] = None  # lowest byte offset at which the pieces disagree
+    corrected_positions: int = 0  # offsets at which changing one piece's byte gave a code word
+    open_positions: int = 0  # offsets that disagree and that no single piece's change explains
+    first_open_offset: typing.Optional[int] = None  # the lowest of them
+    # piece_idx -> offsets at which that piece was the one changed; the keys are the pieces to
+    # regenerate: repair_pieces(rest, targets=list(damaged))
+    damaged: dict[int, int] = Field(default_factory=dict)
+
+
+class PieceCorrectionError(ValueError):
+    """``reconstruct_data_corrected``: at some offset of some chunk the held pieces disagree and no
+    single piece's change explains it, so those bytes cannot be trusted.  ``checks``: every chunk's
+    ``ChunkCorrection``."""
+
+    def __init__(self, message: str, checks: list[ChunkCorrection]):
+        super().__init__(message)
+        self.checks = checks
+
+
+def decode_chunks_corrected(encoded_chunks: typing.Sequence[EncodedChunk]) -> tuple[bytes, list[ChunkCorrection]]:
+    """``decode_chunks_checked`` that corrects instead of dropping: the concatenation of every
+    chunk's bytes with one corrupt piece per byte offset put right, and per chunk what was found.
+
+    Round one is ``decode_chunks_checked``'s fused call (``Engine.decode_check_host``), with the
+    pieces ordered as there, so a clean download costs exactly what it costs there.  The chunks
+    it reports inconsistent, and only those, go through ONE ``Engine.decode_correct_host`` call,
+    which judges every byte offset's column of pieces as ``check_locate`` does and decodes from
+    the corrected column; their bytes are spliced into the result.  Where ``decode_chunks_checked``
+    names one piece per round and gives up once fewer than two spare pieces are left, damage to any
+    number of pieces is corrected here as long as no two of them are damaged at the same offset.
+
+    A chunk's bytes are trustworthy exactly when its ``open_positions`` is 0.  What that means:
+    with two or more pieces beyond k, an offset where at most one piece is wrong is always put
+    right; with three or more, an offset where two are wrong is always reported open; with exactly
+    two, two wrong bytes at one offset may be attributed to a third piece, which only the recorded
+    piece ids exclude.  With fewer than two spare pieces nothing can be corrected and every bad
+    offset is open.  One device, one call; the streaming form is
+    ``reconstruct_data_stream_corrected``."""
+    chunks = list(encoded_chunks)
+    out: list[ChunkCorrection] = []
+    full = []
+    for ch in chunks:
+        use = _held_pieces(ch, "reconstruct")
+        out.append(ChunkCorrection(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
+        full.append(_check_item(ch, use) + (ch.padlen,))
+    if not chunks:
+        return b"", []
+    for it in full:  # every chunk's preconditions before any device work
+        check_decode_correct_item(*it)
+    data, res = get_engine().decode_check_host(full)
+    redo = [i for i, (first_at, _bad, _column) in enumerate(res) if first_at is not None]
+    if not redo:
+        return data, out
+    fixed, cor = get_engine().decode_correct_host([full[i] for i in redo])
+    starts = _decoded_starts(full)
+    parts, at, f = [], 0, 0
+    view = memoryview(data)
+    for i, (first, first_open, corrected, opened, hits) in zip(redo, cor):
+        ck = out[i]
+        ck.consistent = first is None
+        ck.first_bad_offset = first
+        ck.corrected_positions = corrected
+        ck.open_positions = opened
+        ck.first_open_offset = first_open
+        ck.damaged = {int(idx): h for idx, h in zip(full[i][3], hits) if h}
+        n = starts[i + 1] - starts[i]
+        parts.append(view[at:starts[i]])
+        parts.append(memoryview(fixed)[f:f + n])
+        f += n
+        at = starts[i + 1]
+    parts.append(view[at:])
+    return b"".join(parts), out
+
+
+def reconstruct_data_corrected(pieces: list[Piece],
+                               chunks: list[EncodedChunk]) -> tuple[bytes, list[ChunkCorrection]]:
+    """``reconstruct_data`` with one corrupt piece per byte offset put right
+    (``decode_chunks_corrected`` over every piece handed over, grouped as ``reconstruct_data``
+    groups them).  Raises ``ValueError("Not enough pieces to reconstruct chunk N")`` as
+    ``reconstruct_data`` does, before any decode, and ``PieceCorrectionError`` (carrying
+    ``.checks``) when some chunk has open positions; otherwise returns the bytes, all trustworthy
+    in ``decode_chunks_corrected``'s sense, and the checks."""
+    _group_pieces(pieces, chunks)
+    data, checks = decode_chunks_corrected(chunks)
+    bad = [ck.chunk_idx for ck in checks if ck.open_positions]
+    if bad:
+        raise PieceCorrectionError(f"Held pieces disagree beyond what one piece per offset explains in chunk(s) {bad}",
+                                   checks)
+    return data, checks
+
+
+def reconstruct_data_stream_corrected(pieces: list[Piece], chunks: list[EncodedChunk], *,
+                                      window_bytes: int | None = None) -> Iterator[tuple[bytes, ChunkCorrection]]:
+    """``reconstruct_data_corrected``'s contract, delivered as ``reconstruct_data_stream_checked``
+    delivers: yield ``(bytes, ChunkCorrection)`` chunk by chunk, in order, each window one
+    ``decode_chunks_corrected`` on the stream worker.  ``PieceCorrectionError`` (``.checks``: the
+    checks of the chunks seen so far, that chunk's last) is raised when the stream reaches a chunk
+    with open positions, after every earlier chunk has been yielded."""
+    yield from _stream_verified(
+        pieces, list(zip(chunks)), window_bytes, decode_chunks_corrected, lambda ck: not ck.open_positions,
+        lambda ck, seen: PieceCorrectionError(
+            f"Held pieces disagree beyond what one piece per offset explains in chunk {ck.chunk_idx}", seen))
 
 
 class ChunkIdCheck(BaseModel):
