@@ -136,7 +136,8 @@ int sec_ctx_set_timing(sec_ctx *ctx, int enable);
 /* Waits for recorded pairs, returns the summed milliseconds and launch count of
  * kind 0 = encode, 1 = decode, 2 = SHA-1, 3 = bignum (APDP), 4 = repair (its kernels and,
  * with digests, their SHA-1), 5 = check, 6 = decode + check, 7 = repair + check (its main kernel and
- * tail, sec_check_final and, with digests, their SHA-1), 8 = decode + correct, and clears them. */
+ * tail, sec_check_final and, with digests, their SHA-1), 8 = the correcting calls: decode + correct, repair +
+ * correct (with digests, their SHA-1 too), and clears them. */
 int sec_timing_collect(sec_ctx *ctx, int kind, double *total_ms, int64_t *launches);
 
 /* ---- context options --------------------------------------------------------
@@ -470,6 +471,65 @@ int sec_repair_check_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t n
                            const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out,
                            uint8_t *digests, sec_chk_result *results, uint8_t *row_bad,
                            uint8_t *column, unsigned flags);
+
+/* ---- repair + correct: regenerate and heal pieces from the column-corrected code word ----------
+ * A repair's output is seeded to other miners, so a damaged survivor that gets through becomes
+ * permanent.  sec_repair_check_batch names one corrupt piece and the caller drops it whole, which
+ * gives up once two pieces are damaged and n - k = 2, even at different offsets.  This call corrects
+ * per byte position, as sec_decode_correct_batch does, and gives PIECES back.  The contract is the
+ * COMPOSITION of two existing ones:
+ *   - chunks (sec_rchk_chunk), entries, basis and block_avail mean what they mean for
+ *     sec_repair_check_batch: the first k entries, in any order, are the basis, the rest check rows;
+ *     bytes past an entry's avail read as zero and nothing past them is read.
+ *   - for every position p in [0, B) the n held bytes are a column, judged exactly as
+ *     sec_decode_correct_batch / sec_check_locate judge it: a code word; a check-row entry wrong
+ *     (counted); a basis entry wrong (replaced by the one value that makes the column a code word,
+ *     counted); open (left as held: every bad position when n - k < 2).
+ * Targets.  Target j of chunk c is block target_nums[tgt0 + j], written whole at
+ * out + target_offs[tgt0 + j]: B bytes at any byte alignment, in the caller's order, data block k-1
+ * with its zero padding.  One rule defines its bytes:
+ *     byte p = (row target_nums[tgt0 + j] of the repair matrix over the basis)
+ *              . (the basis column at p after the replacement above).
+ * A target MAY be one of the n held entries (a heal target), so
+ *   - a lost block is regenerated;
+ *   - a held basis entry comes back as held, with its byte replaced wherever it was the entry
+ *     changed;
+ *   - a held check-row entry comes back as the prediction from the corrected basis: its held byte
+ *     wherever the column is a code word or a basis entry was changed, the corrected byte where
+ *     that row was the entry changed;
+ *   - at OPEN positions every target is what the basis as held predicts, which for a held check
+ *     row may differ from the byte it holds there.
+ * Targets are distinct among themselves.  digests (nullable): 20 bytes per target at
+ * digests + 20 (tgt0 + j), the SHA-1 of the target as written, from the SHA-1 kernel while the
+ * targets are device-resident, as sec_repair_batch's.  results[c] (8-byte aligned) is chunk c's
+ * sec_cor_result; entry_hits (nullable) has one uint32_t per entry of the call in the caller's
+ * order, zero included, exactly sec_decode_correct_batch's.  What the verdicts promise is stated
+ * there (the code has distance n - k + 1; with n - k = 2 two wrong bytes at one position may be
+ * attributed to a third entry).
+ * A chunk with n == k is a plain repair, reported consistent (a heal target is then a copy); one
+ * with ntargets == 0 judges and counts and writes no block (`out` may then be NULL).  Nothing is
+ * ever written to the blocks; every call starts from clean state.
+ * Aliasing: sec_repair_batch's rule (no target range may overlap a block or another target of the
+ * call): healing is never in place.
+ * The call always takes its own kernels (sec_repair_correct_kernel): there is no bit-sliced form,
+ * and sec_ctx_check_methods, sec_ctx_repair_methods, sec_ctx_decode_paths and
+ * sec_ctx_decode_methods do not count it.
+ * Flags: none or SEC_F_ASYNC (device pointers); SEC_F_HOST (host pointers) is ALWAYS staged through
+ * pinned slabs: the n*B bytes of a chunk are gathered ONCE, and the targets, digests, results and
+ * hits are scattered back; sec_ctx_host_paths counts the call as staged.  SEC_F_HOST with
+ * SEC_F_ASYNC and every other flag are SEC_EINVAL.
+ * Errors, all before any device work, in sec_repair_check_batch's order: SEC_EINVAL a NULL array,
+ * NULL results, a NULL context, n < 0, ntargets < 0 or targets without their arrays; SEC_EKM;
+ * SEC_ENBLOCKS n < k or n > m; SEC_ESHARENUM an entry or a target outside [0, m); SEC_EDUPSHARE a
+ * repeat among the n entries or a repeated target (a target that is an entry is NOT an error
+ * here); SEC_ESIZE B >= 2^31.
+ * sec_timing_collect kind 8 times this call's kernels and, with digests, their SHA-1. */
+int sec_repair_correct_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks,
+                             const int32_t *sharenums, const uint64_t *block_offs,
+                             const uint64_t *block_avail, const uint8_t *blocks,
+                             const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out,
+                             uint8_t *digests, sec_cor_result *results, uint32_t *entry_hits,
+                             unsigned flags);
 
 /* Which single entry explains an inconsistent column (host arithmetic, no device needed).
  * sharenums: the n block numbers, the first k the basis; column: the n bytes sec_check_batch

@@ -150,6 +150,8 @@ _SIGS = {
                                                 ctypes.c_uint]),
     "sec_repair_check_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               _vp, ctypes.c_uint]),
+    "sec_repair_correct_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, ctypes.c_uint]),
     "sec_check_locate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,
                                         ctypes.POINTER(ctypes.c_int32)]),
     "sec_check_method": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_uint64, _vp,

@@ -724,7 +724,10 @@ struct sec_ctx {
     hipEvent_t pin_ev = nullptr, meta_ev = nullptr;
     TableCache enc_tabs, dec_tabs;
     Plan enc_plan, dec_plan, sha_plan, bn_plan;
-    RowOpState row_ops[5];  // repair, check, decode + check, repair + check, decode + correct (by their Op::kId)
+    // repair, check, decode + check, repair + check, the correcting two (by their Op::kId).  Decode +
+    // correct and repair + correct share one state: a caller that alternates the two calls rebuilds
+    // and uploads the plan on every call (the table cache is kept); a state of its own would end that
+    RowOpState row_ops[5];
     DevBuf bn_scratch;  // host-mode staging of sec_bn_modexp / mulmod operands
     DevBuf bn_part;     // partial residues of segmented reductions (one region per slot)
     DevBuf syn;         // syndrome rows of device-mode syndrome decodes
@@ -1035,7 +1038,10 @@ int check_sharenums(int k, int m, const int32_t *s)
 //   in_turn (repair, sec_repair_matrix, sec_check_locate: n is k): each number is judged in its
 //     turn, range then duplicate, as zfec judges sharenums;
 //   else (the check family): k <= n <= m, and every range error comes before any duplicate.
-int check_blocks(int k, int m, const int32_t *held, int n, const int32_t *targets, int nt, bool in_turn)
+//   held_targets (repair + correct): a target may be a held block; the targets are distinct among
+//     themselves only.
+int check_blocks(int k, int m, const int32_t *held, int n, const int32_t *targets, int nt, bool in_turn,
+                 bool held_targets = false)
 {
     if (nt < 0 || !held || (nt > 0 && !targets) || (!in_turn && n < 0))
         return SEC_EINVAL;
@@ -1051,7 +1057,9 @@ int check_blocks(int k, int m, const int32_t *held, int n, const int32_t *target
                 if (nums[a][i] < 0 || nums[a][i] >= m)
                     return SEC_ESHARENUM;
     bool seen[256] = {false};
-    for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < 2; ++a) {
+        if (a == 1 && held_targets)
+            std::fill(seen, seen + 256, false);
         for (int i = 0; i < count[a]; ++i) {
             const int b = nums[a][i];
             if (in_turn && (b < 0 || b >= m))
@@ -1060,6 +1068,7 @@ int check_blocks(int k, int m, const int32_t *held, int n, const int32_t *target
                 return SEC_EDUPSHARE;
             seen[b] = true;
         }
+    }
     return SEC_OK;
 }
 
@@ -1790,6 +1799,15 @@ int launch_decode_sub(sec_ctx *ctx, const Plan &plan, const SubPlan &sp, const u
 // kind, and, in a base struct per family (CheckBsFamily, RepairBsFamily), its bit-sliced kernel.
 // A fifth, decode + correct (DecodeCorrectOp), is decode + check with kernels, words and results of
 // its own (kCorrects): it judges every position's column instead of comparing whole rows.
+// A sixth, repair + correct (RepairCorrectOp), is to repair + check what the fifth is to decode +
+// check:
+//   decode + correct   n            as decode + check, from the           every column     no
+//                                   corrected basis                       judged
+//   repair + correct   n            targets, at caller addresses, from    every column     optional
+//                                   the corrected basis; a target may     judged
+//                                   be a held entry (a heal target)
+// The two correcting operations share one RowOpState (kId 4: plan, table cache and words; the plan
+// key carries the operation) and one timing kind (8).
 
 // A chunk of any of the four, in common terms (fields an operation lacks are 0)
 struct RowChunk {
@@ -1827,9 +1845,9 @@ sec::ChkDesc chk_desc(const RowInfo &r, uint32_t res, uint32_t cslot0)
 }
 
 // Preconditions of a check (sec_check_batch), and of the held blocks of the others
-int check_held(const RowChunk &c, const RowArgs &a, const int32_t *targets = nullptr)
+int check_held(const RowChunk &c, const RowArgs &a, const int32_t *targets = nullptr, bool held_targets = false)
 {
-    return check_blocks(c.k, c.m, a.sharenums + c.slot0, c.n, targets, c.nt, false);
+    return check_blocks(c.k, c.m, a.sharenums + c.slot0, c.n, targets, c.nt, false, held_targets);
 }
 
 // The bit-sliced kernel of an operation's family: its descriptor, the chunks its rule judges (bs_judged)
@@ -2019,6 +2037,41 @@ struct RepairCheckOp : RepairBsFamily {
         return c.B >= (1ull << 31) ? SEC_ESIZE : SEC_OK;
     }
 };
+
+// Repair + correct: repair + check's chunks, screening order, targets and staging, except that a
+// target may be a held entry; decode + correct's descriptor, words, results and state (kId), and
+// kernels of its own (never the bit-sliced one: bs_judged).
+struct RepairCorrectOp : RepairCheckOp {
+    using Desc = sec::CorDesc;
+    using Slots = sec::RCorSlots;
+    static constexpr int kId = 4, kTiming = 8;
+    static constexpr bool kCorrects = true;
+    static constexpr const char *kTile = "sec_repair_correct_kernel", *kTail = "sec_repair_correct_tail";
+    static bool bs_judged(const RowChunk &) { return false; }
+    static Desc desc(const RowInfo &r, uint32_t res, uint32_t cslot0)
+    {
+        return {0, 0, r.B, r.k, r.ns, r.nr, r.tab, r.slot0, r.flag0, r.valid, r.cnt0, res, cslot0, r.tgt0};
+    }
+    static Slots slots(const DevBuf &m, const SubPlan &sp, uint32_t *flags)
+    {
+        return {m.as<uint64_t>(sp.off_soff), m.as<uint32_t>(sp.off_savail), m.as<uint64_t>(sp.off_toff),
+                m.as<uint32_t>(sp.off_cpos), m.as<uint32_t>(sp.off_echunk), flags};
+    }
+    // the targets: in [0, m) and distinct among themselves; one that is held is a heal target
+    static int screen(const Chunk &c, const RowArgs &a)
+    {
+        RC(check_held(view(c), a, c.ntargets ? a.target_nums + c.tgt0 : nullptr, true));
+        return c.B >= (1ull << 31) ? SEC_ESIZE : SEC_OK;
+    }
+    static int group_rows(int rows) { return DecodeCorrectOp::group_rows(rows); }
+};
+
+// What sec_decode_correct_final reads of an operation's slots
+sec::CorSlots final_slots(const sec::CorSlots &sl) { return sl; }
+sec::CorSlots final_slots(const sec::RCorSlots &sl)
+{
+    return {sl.off, sl.avail, nullptr, nullptr, sl.cpos, sl.echunk, sl.flags};
+}
 
 // The cache key of the table of the blocks `rows` over the k blocks idx[0..k) (a table's contents
 // depend on nothing else)
@@ -2363,12 +2416,10 @@ int launch_row_sub(sec_ctx *ctx, const SubPlan &sp, bool host, const uint8_t *bl
             sec_launch_correct_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
         if (e)
             return hip_fail((hipError_t)e, Op::kTail);
-        e = sec_launch_correct_final(dd, sp.nentries, sl, (sec::CorResult *)results, (uint32_t *)row_bad, s);
+        e = sec_launch_correct_final(dd, sp.nentries, final_slots(sl), (sec::CorResult *)results, (uint32_t *)row_bad,
+                                     s);
         if (e)
             return hip_fail((hipError_t)e, "sec_decode_correct_final");
-        if (timed)
-            RC(timing_end(ctx, t0, Op::kTiming, s));
-        return SEC_OK;
     } else {
         for (const Group &g : sp.groups) {
             int e = sec_launch_rows(g.rows, g.U, g.wide, g.lanes, blocks, out, dd, dt + g.first, g.count, tabs, sl, s,
@@ -2383,7 +2434,7 @@ int launch_row_sub(sec_ctx *ctx, const SubPlan &sp, bool host, const uint8_t *bl
                 return hip_fail((hipError_t)e, Op::kTail);
         }
     }
-    if (Op::kChecks) {
+    if (Op::kChecks && !Op::kCorrects) {
         const sec::ChkSlots csl{plan.meta.as<uint64_t>(sp.off_soff), plan.meta.as<uint32_t>(sp.off_savail),
                                 plan.meta.as<uint32_t>(sp.off_cpos), plan.meta.as<uint32_t>(sp.off_echunk), flags};
         int e = sec_launch_check_final(blocks, plan.meta.as<sec::ChkDesc>(sp.off_cdesc), sp.nentries, csl, results,
@@ -2575,7 +2626,7 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
         }
     }
     key.put((a.flags & (SEC_F_HOST | SEC_F_RECOVER)) | (!host && a.block_avail ? 0x10000u : 0u) |
-            (digest ? 0x20000u : 0u));
+            (digest ? 0x20000u : 0u) | (Op::kCorrects && Op::kTargets ? 0x40000u : 0u));  // (kId 4 serves two)
     const bool reuse = plan_reusable(plan, st.tabs, key);
     SlotLayout L;
     if (!reuse || host)
@@ -4444,6 +4495,18 @@ int sec_repair_check_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t n
     return row_op<RepairCheckOp>(ctx, chunks, nchunks,
                                  RowArgs{sharenums, block_offs, block_avail, blocks, target_nums, target_offs, out,
                                          digests, results, row_bad, column, flags});
+}
+
+int sec_repair_correct_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                             const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
+                             const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out, uint8_t *digests,
+                             sec_cor_result *results, uint32_t *entry_hits, unsigned flags)
+{
+    RowArgs a{sharenums, block_offs, block_avail, blocks, target_nums, target_offs, out, digests,
+              nullptr, nullptr, nullptr, flags};
+    a.cor = results;
+    a.hits = entry_hits;
+    return row_op<RepairCorrectOp>(ctx, chunks, nchunks, a);
 }
 
 int sec_check_method(int k, int m, const int32_t *sharenums, int n, uint64_t B, const uint64_t *block_avail,

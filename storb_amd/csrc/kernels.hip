@@ -1699,8 +1699,8 @@ __device__ __forceinline__ void min_word(u32 *w, u32 v)
 
 // WAVE: every lane of the wave is on the same chunk (the tile kernel), so their counts go through
 // one atomic per word; else (the tail kernel: a lane per item of any chunk) each lane adds its own.
-template <bool WAVE>
-__device__ __forceinline__ void cor_tally(const sec::CorDesc &d, const sec::CorSlots sl, u32 p, const CorVerdict v)
+template <bool WAVE, class Slots>
+__device__ __forceinline__ void cor_tally(const sec::CorDesc &d, const Slots sl, u32 p, const CorVerdict v)
 {
     u32 *f = sl.flags + d.flag0, *c = sl.flags + d.cnt0;
     if (v.bad)
@@ -1731,30 +1731,46 @@ __device__ __forceinline__ void cor_tally(const sec::CorDesc &d, const sec::CorS
     }
 }
 
-// Position p of a chunk, whole: the verdict on its column and every output byte there.  Rows go in
-// groups of R and the slots' bytes in batches of kBatch loads issued together (repair_ragged: a loop
-// of dependent single-byte loads costs one memory latency per slot and row).
-template <int R>
-__device__ __forceinline__ CorVerdict cor_byte(const u8 *__restrict__ blocks, u8 *__restrict__ out,
-                                               const sec::CorDesc &d, const u32 *__restrict__ tabs,
-                                               const sec::CorSlots sl, u32 p)
+// Position p of a chunk, whole, in two parts both correcting operations share the first of: the
+// verdict on its column (cor_judge) and every output byte there (cor_byte: the decode's; rcor_byte:
+// the repair's targets).  Rows go in groups of R and the slots' bytes in batches of kBatch loads
+// issued together (repair_ragged: a loop of dependent single-byte loads costs one memory latency per
+// slot and row).
+struct CorFix {
+    CorVerdict v;
+    u32 fix, val;  // the basis slot put right (~0u: none), by which value
+};
+
+// acc[r] ^= XOR_c T[c][min(row0 + r, rlast)] * (slot c's byte at p, slot `fix` changed by `val`)
+template <int R, class Slots>
+__device__ __forceinline__ void cor_byte_rows(u32 (&acc)[R], const u8 *__restrict__ blocks, const sec::CorDesc &d,
+                                              const u32 *__restrict__ tabs, const Slots sl, u32 p, u32 row0,
+                                              u32 rlast, u32 fix, u32 val)
+{
+    const u32 k = d.k, nrows = d.e + d.nr;
+    for (u32 c0 = 0; c0 < k; c0 += kBatch) {
+        u32 x[kBatch];
+        load_slot_bytes(x, blocks, sl, d.slot0, c0, k, p);
+#pragma unroll
+        for (u32 q = 0; q < kBatch; ++q)
+            if (c0 + q < k) {
+                const u32 xv = x[q] ^ (c0 + q == fix ? val : 0u);
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    acc[r] ^= gf_mul_byte(
+                        tabs + d.tab + ((c0 + q) * nrows + min(row0 + (u32)r, rlast)) * sec::kTabDwords, xv);
+            }
+    }
+}
+
+template <int R, class Slots>
+__device__ __forceinline__ CorFix cor_judge(const u8 *__restrict__ blocks, const sec::CorDesc &d,
+                                            const u32 *__restrict__ tabs, const Slots sl, u32 p)
 {
     const u32 k = d.k, e = d.e, nr = d.nr, nrows = e + nr;
     auto tab = [&](u32 c, u32 r) { return tabs + d.tab + (c * nrows + r) * sec::kTabDwords; };
-    // acc[r] = XOR_c T[c][min(row0 + r, rlast)] * (slot c's byte, slot `fix` changed by `val`)
     auto rows = [&](u32 (&acc)[R], u32 row0, u32 rlast, u32 fix, u32 val) {
-        for (u32 c0 = 0; c0 < k; c0 += kBatch) {
-            u32 x[kBatch];
-            load_slot_bytes(x, blocks, sl, d.slot0, c0, k, p);
-#pragma unroll
-            for (u32 q = 0; q < kBatch; ++q)
-                if (c0 + q < k) {
-                    const u32 xv = x[q] ^ (c0 + q == fix ? val : 0u);
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                        acc[r] ^= gf_mul_byte(tab(c0 + q, min(row0 + (u32)r, rlast)), xv);
-                }
-        }
+        cor_byte_rows<R>(acc, blocks, d, tabs, sl, p, row0, rlast, fix, val);
     };
     // the deltas of check rows g0 .. g0 + R - 1 (those past nr - 1 repeat row nr - 1)
     auto deltas = [&](u32 (&acc)[R], u32 g0) {
@@ -1816,6 +1832,18 @@ __device__ __forceinline__ CorVerdict cor_byte(const u8 *__restrict__ blocks, u8
     } else {
         v.open = true;
     }
+    return {v, fix, val};
+}
+
+// The decode's output part: the present primaries' bytes and the recovered rows', from the basis
+// column with slot `fix` changed by `val`, up to the chunk's length
+template <int R>
+__device__ __forceinline__ CorVerdict cor_byte(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                               const sec::CorDesc &d, const u32 *__restrict__ tabs,
+                                               const sec::CorSlots sl, u32 p)
+{
+    const CorFix f = cor_judge<R>(blocks, d, tabs, sl, p);
+    const u32 k = d.k, e = d.e, fix = f.fix, val = f.val;
     u8 *dst = out + d.out_off + p;
     for (u32 c0 = 0; c0 < k; c0 += kBatch) {
         u32 x[kBatch];
@@ -1833,7 +1861,7 @@ __device__ __forceinline__ CorVerdict cor_byte(const u8 *__restrict__ blocks, u8
 #pragma unroll
         for (int r = 0; r < R; ++r)
             acc[r] = 0u;
-        rows(acc, g0, e - 1, fix, val);
+        cor_byte_rows<R>(acc, blocks, d, tabs, sl, p, g0, e - 1, fix, val);
 #pragma unroll
         for (int r = 0; r < R; ++r)
             if (g0 + r < e) {
@@ -1842,7 +1870,31 @@ __device__ __forceinline__ CorVerdict cor_byte(const u8 *__restrict__ blocks, u8
                     dst[(u64)orow * d.B] = (u8)acc[r];
             }
     }
-    return v;
+    return f.v;
+}
+
+// The repair's output part: every target's byte, (its row of the table) . (the basis column with
+// slot `fix` changed by `val`), at the target's own address.  A held target goes through the table
+// like a lost one: a basis entry's row is the unit row, a check row's its own row once more.
+template <int R>
+__device__ __forceinline__ CorVerdict rcor_byte(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                const sec::CorDesc &d, const u32 *__restrict__ tabs,
+                                                const sec::RCorSlots sl, u32 p)
+{
+    const CorFix f = cor_judge<R>(blocks, d, tabs, sl, p);
+    const u32 nt = d.e;
+    for (u32 g0 = 0; g0 < nt; g0 += R) {
+        u32 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            acc[r] = 0u;
+        cor_byte_rows<R>(acc, blocks, d, tabs, sl, p, g0, nt - 1, f.fix, f.val);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (g0 + r < nt)
+                out[sl.tgt_off[d.tgt0 + g0 + r] + p] = (u8)acc[r];
+    }
+    return f.v;
 }
 
 template <int R, bool WAVE = true>
@@ -1852,13 +1904,20 @@ __device__ __forceinline__ void cor_pos(const u8 *__restrict__ blocks, u8 *__res
     cor_tally<WAVE>(d, sl, p, cor_byte<R>(blocks, out, d, tabs, sl, p));
 }
 
+template <int R, bool WAVE = true>
+__device__ __forceinline__ void cor_pos(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
+                                        const u32 *__restrict__ tabs, const sec::RCorSlots sl, u32 p)
+{
+    cor_tally<WAVE>(d, sl, p, rcor_byte<R>(blocks, out, d, tabs, sl, p));
+}
+
 constexpr int kCorBatch = 8;  // slots per load batch of cor_rows
 
 // acc[r] = XOR_c T[c][min(row0 + r, rlast)] * slot_c[pos .. pos + 16): R rows of the chunk's table
 // from row0 on (a group's rows past rlast repeat row rlast; the caller drops them)
-template <int R>
+template <int R, class Slots>
 __device__ __forceinline__ void cor_rows(u32x4 (&acc)[R], const u8 *__restrict__ blocks, const sec::CorDesc &d,
-                                         const u32 *__restrict__ tabs, const sec::CorSlots sl, u32 pos, u32 row0,
+                                         const u32 *__restrict__ tabs, const Slots sl, u32 pos, u32 row0,
                                          u32 rlast)
 {
     const u32 k = d.k, nrows = d.e + d.nr;
@@ -1893,13 +1952,13 @@ __device__ __forceinline__ void cor_rows(u32x4 (&acc)[R], const u8 *__restrict__
     }
 }
 
-// A lane's 16 whole positions [pos, pos + 16), all below `valid`
-template <int R>
-__device__ __forceinline__ void cor_main(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
-                                         u32 pos, const u32 *__restrict__ tabs, const sec::CorSlots sl)
+// The OR of every check row's delta over a lane's 16 whole positions [pos, pos + 16), all below
+// `valid`: zero when all 16 columns are code words
+template <int R, class Slots>
+__device__ __forceinline__ u32 cor_lane_deltas(u32x4 (&acc)[R], const u8 *__restrict__ blocks, const sec::CorDesc &d,
+                                               u32 pos, const u32 *__restrict__ tabs, const Slots sl)
 {
     const u32 k = d.k, e = d.e, nr = d.nr;
-    u32x4 acc[R];
     u32 any = 0;
 #pragma unroll 1
     for (u32 g0 = 0; g0 < nr; g0 += R) {
@@ -1913,6 +1972,17 @@ __device__ __forceinline__ void cor_main(const u8 *__restrict__ blocks, u8 *__re
                     any |= acc[r][w] ^ st[w];
             }
     }
+    return any;
+}
+
+// A lane's 16 whole positions [pos, pos + 16), all below `valid`
+template <int R>
+__device__ __forceinline__ void cor_main(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
+                                         u32 pos, const u32 *__restrict__ tabs, const sec::CorSlots sl)
+{
+    const u32 k = d.k, e = d.e;
+    u32x4 acc[R];
+    const u32 any = cor_lane_deltas<R>(acc, blocks, d, pos, tabs, sl);
     if (any) {
         for (u32 i = 0; i < (u32)sec::kLaneBytes; ++i)
             cor_pos<R>(blocks, out, d, tabs, sl, pos + i);
@@ -1997,6 +2067,80 @@ __global__ __launch_bounds__(256) void sec_decode_correct_final(const sec::CorDe
         results[d.res] = sec::CorResult{first == ~0u ? ~(u64)0 : (u64)first, fopen == ~0u ? ~(u64)0 : (u64)fopen,
                                         sl.flags[d.cnt0], sl.flags[d.cnt0 + 1]};
     }
+}
+
+// ---- repair + correct: regenerate and heal pieces from the column-corrected code word ----------
+// Decode + correct with repair + check's outputs.  The chunk's table has rows 0 .. nt-1 for the
+// targets (CorDesc::e is nt) and rows nt .. nt+nr-1 for the check rows; every column is judged by
+// cor_judge, the verdict decode + correct reaches, and counted by cor_tally into the same words, so
+// sec_decode_correct_final reports both.  Target r is a whole B-byte piece at out +
+// tgt_off[tgt0 + r], any alignment: byte p = (row r) . (the basis column at p, one slot put right
+// where the verdict says so).  A target may be a held entry; it takes the same route through the
+// table (a basis entry's row is the unit row, a held check row's equals its check row), so at an
+// open position it is what the basis as held predicts.  The two levels are cor_main's: a lane whose
+// 16 columns are code words stores every target row as one unaligned 16-byte vector (rchk_main's
+// stores), in groups of R rows over the same positions; a lane with a nonzero delta, the lane that
+// straddles `valid`, the ragged end [valid, B) and the tail kernel's chunks go byte by byte
+// (rcor_byte), and no output byte is written twice.  valid = min(B, every entry's avail): every
+// target byte up to B is stored.
+template <int R>
+__device__ __forceinline__ void rcor_main(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
+                                          u32 pos, const u32 *__restrict__ tabs, const sec::RCorSlots sl)
+{
+    const u32 nt = d.e;
+    u32x4 acc[R];
+    const u32 any = cor_lane_deltas<R>(acc, blocks, d, pos, tabs, sl);
+    if (any) {
+        for (u32 i = 0; i < (u32)sec::kLaneBytes; ++i)
+            cor_pos<R>(blocks, out, d, tabs, sl, pos + i);
+        return;
+    }
+    const u64 *to = sl.tgt_off + d.tgt0;
+#pragma unroll 1
+    for (u32 g0 = 0; g0 < nt; g0 += R) {
+        cor_rows<R>(acc, blocks, d, tabs, sl, pos, g0, nt - 1);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (g0 + r < nt)
+                store16<SEC_DEC_ST>(out + to[g0 + r] + pos, acc[r]);
+    }
+}
+
+// R: rows per group (the plan picks the least of 2, 4, 8 that holds the chunk's nt + nr rows, else 8)
+template <int R>
+__global__ __launch_bounds__(sec::kLanes) void sec_repair_correct_kernel(const u8 *__restrict__ blocks,
+                                                                         u8 *__restrict__ out,
+                                                                         const sec::CorDesc *__restrict__ descs,
+                                                                         const sec::Tile *__restrict__ tiles,
+                                                                         const u32 *__restrict__ tabs,
+                                                                         const sec::RCorSlots sl)
+{
+    const sec::Tile tl = sec::own_tile(tiles);
+    const sec::CorDesc d = descs[tl.chunk];
+    const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
+    if (t + sec::kLaneBytes <= d.valid) {
+        rcor_main<R>(blocks, out, d, t, tabs, sl);
+    } else if (t < d.valid) {  // the lane that straddles `valid`
+        for (u32 p = t; p < d.valid; ++p)
+            cor_pos<R>(blocks, out, d, tabs, sl, p);
+    }
+    if (tl.ntail)
+        for (u32 i = ragged_lane0(d.valid, tl.t0); i < tl.ntail; i += blockDim.x)
+            cor_pos<R>(blocks, out, d, tabs, sl, d.valid + i);
+}
+
+// One thread per (chunk, position) of the chunks too small for a tile (valid < 16)
+__global__ __launch_bounds__(256) void sec_repair_correct_tail(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                               const sec::CorDesc *__restrict__ descs,
+                                                               const sec::TailItem *__restrict__ items, u32 nitems,
+                                                               const u32 *__restrict__ tabs, const sec::RCorSlots sl)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nitems)
+        return;
+    const sec::TailItem it = items[i];
+    const sec::CorDesc d = descs[it.chunk];
+    cor_pos<4, false>(blocks, out, d, tabs, sl, it.t);
 }
 
 // ---- SHA-1 of pieces (storb piece ids, /root/reference/storb/util/piece.py:54-68) ----
@@ -2582,6 +2726,30 @@ int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorD
     if (nitems == 0)
         return hipSuccess;
     return launch(sec_decode_correct_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out,
+                  descs, items, nitems, tabs, sl);
+}
+
+int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::Tile *tiles,
+                       uint32_t ntiles, const uint32_t *tabs, sec::RCorSlots sl, void *stream)
+{
+    if (ntiles == 0)
+        return hipSuccess;
+    const dim3 grid(ntiles), block(sec::kLanes);
+    hipStream_t s = (hipStream_t)stream;
+    switch (rows) {
+    case 2: return launch(sec_repair_correct_kernel<2>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
+    case 4: return launch(sec_repair_correct_kernel<4>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
+    case 8: return launch(sec_repair_correct_kernel<8>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::TailItem *items,
+                            uint32_t nitems, const uint32_t *tabs, sec::RCorSlots sl, void *stream)
+{
+    if (nitems == 0)
+        return hipSuccess;
+    return launch(sec_repair_correct_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out,
                   descs, items, nitems, tabs, sl);
 }
 

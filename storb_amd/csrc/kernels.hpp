@@ -163,7 +163,7 @@ struct CorDesc {
                       // at which entry j (basis slots in normalised order, then check rows) was the one changed
     uint32_t res;     // the chunk's index in the launch's results[]
     uint32_t cslot0;  // the chunk's first entry in the launch's hits[]
-    uint32_t pad;
+    uint32_t tgt0;    // repair + correct: first entry in RCorSlots::tgt_off (decode + correct: 0)
 };
 
 struct CorSlots {
@@ -174,6 +174,18 @@ struct CorSlots {
     const uint32_t *cpos;    // as ChkSlots
     const uint32_t *echunk;
     uint32_t *flags;         // the call's words: [0, 2 * chunks) start as 0xFFFFFFFF, the counters behind as 0
+};
+
+// One repair + correct chunk is a CorDesc as well: e its nt target rows (rows 0 .. nt-1 of the table,
+// each stored whole at out + tgt_off[tgt0 + r], as RChkDesc's), nr, the n entries and the words as
+// above; out_off and n are unused (0), valid = min(B, every avail).  A target may be a held entry.
+struct RCorSlots {
+    const uint64_t *off;
+    const uint32_t *avail;
+    const uint64_t *tgt_off;  // target address: out + tgt_off[target], any byte alignment
+    const uint32_t *cpos;     // as ChkSlots
+    const uint32_t *echunk;
+    uint32_t *flags;          // as CorSlots::flags
 };
 
 // sec_cor_result's device mirror (include/storb_ec.h)
@@ -449,4 +461,11 @@ int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorD
                             uint32_t nitems, const uint32_t *tabs, sec::CorSlots slots, void *stream);
 int sec_launch_correct_final(const sec::CorDesc *descs, uint32_t nentries, sec::CorSlots slots, sec::CorResult *results,
                              uint32_t *hits, void *stream);
+// Repair + correct: sec_repair_correct_kernel and its tail kernel over the same tiles and items, the
+// targets stored whole at their own addresses; its results by sec_launch_correct_final (slots: off,
+// avail, cpos, echunk and flags of the RCorSlots, row / miss unused)
+int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::Tile *tiles,
+                       uint32_t ntiles, const uint32_t *tabs, sec::RCorSlots slots, void *stream);
+int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::TailItem *items,
+                            uint32_t nitems, const uint32_t *tabs, sec::RCorSlots slots, void *stream);
 }

@@ -160,7 +160,8 @@ class Engine:
     def collect_timing(self, kind: str) -> tuple[float, int]:
         """(summed kernel ms, launch count) recorded since the last collect;
         kind 'encode' | 'decode' | 'sha1' | 'bignum' | 'repair' | 'check' | 'decode_check' |
-        'repair_check'."""
+        'repair_check' | 'decode_correct' (the correcting calls: decode + correct and
+        repair + correct, the latter's SHA-1 included)."""
         ms = ctypes.c_double(0)
         n = ctypes.c_int64(0)
         self._check(self.lib.sec_timing_collect(self._ctx, _TIMING_KINDS[kind], ctypes.byref(ms),
@@ -484,14 +485,7 @@ class Engine:
         res = np.zeros(len(items), dtype=COR_RESULT_DTYPE)
         hits = np.zeros(sn.size, dtype=np.uint32)
         self.decode_correct_batch(descs, sn, bo, 0, buf, res, entry_hits=hits, host=True)
-        none = _lib.CHK_CONSISTENT
-        out = []
-        for j, it in enumerate(items):
-            first, fopen = int(res[j]["first"]), int(res[j]["first_open"])
-            out.append((None if first == none else first, None if fopen == none else fopen,
-                        int(res[j]["corrected"]), int(res[j]["open"]),
-                        [int(h) for h in hits[slot0[j]:slot0[j] + len(it[2])]]))
-        return buf[:starts[-1]].tobytes(), out
+        return buf[:starts[-1]].tobytes(), self._correct_results(items, slot0, res, hits)
 
     def repair_check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
                            target_nums: np.ndarray, target_offs: np.ndarray, out, results, *,
@@ -528,6 +522,59 @@ class Engine:
         out, digs = self._targets_done(objs, dig)
         checks = self._check_results(items, slot0, res, rb, col)
         return (out, digs, checks) if digests else (out, checks)
+
+    def repair_correct_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
+                             target_nums: np.ndarray, target_offs: np.ndarray, out, results, *,
+                             block_avail: np.ndarray | None = None, digests=None, entry_hits=None,
+                             host: bool = False, asynchronous: bool = False) -> None:
+        """sec_repair_correct_batch: every byte position's column of each chunk's n entries
+        (RCHK_DTYPE descriptors) judged as ``check_locate`` judges it, and every target written
+        whole from the first k entries after the one wrong basis byte of a position, if any, is
+        put right.  A target may be a held entry (a heal target).  digests as repair_batch;
+        results and entry_hits as decode_correct_batch.  host: host buffers, always staged, every
+        entry gathered once."""
+        self._row_call(self.lib.sec_repair_correct_batch, RCHK_DTYPE, descs, sharenums, block_offs, block_avail,
+                       (target_nums, target_offs), (blocks, out, digests, results, entry_hits), host=host,
+                       asynchronous=asynchronous)
+
+    def repair_correct_host(self, items, digests: bool = False):
+        """Blocks of host chunks regenerated or healed from the column-corrected code word, in one
+        call.
+
+        items: [(k, m, blocks, sharenums, targets)] as ``repair_check_host`` takes them, except
+        that a target may be one of the blocks held: it comes back whole with the bytes put right
+        at which it was the block changed.  Returns what ``repair_host`` returns (per chunk the
+        target blocks as bytes in the order of `targets`; with ``digests=True`` also, per chunk,
+        each one's SHA-1 digest) followed by what ``decode_correct_host`` returns per chunk:
+        ``(first, first_open, corrected, open, hits)``, hits per block of the chunk in the
+        caller's order."""
+        for it in items:
+            check_repair_correct_item(*it)
+        if not items:
+            return ([], [], []) if digests else ([], [])
+        sn, bo, _keep, slot0 = self._lay_out_blocks(items)
+        tn, to, dig, objs, tgt0, _views = self._lay_out_targets(items, digests)
+        descs = np.zeros(len(items), dtype=RCHK_DTYPE)
+        for j, (k, m, blocks, _sharenums, targets) in enumerate(items):
+            descs[j] = (len(blocks[0]), slot0[j], tgt0[j], len(targets), len(blocks), k, m)
+        res = np.zeros(len(items), dtype=COR_RESULT_DTYPE)
+        hits = np.zeros(sn.size, dtype=np.uint32)
+        self.repair_correct_batch(descs, sn, bo, 0, tn, to, 0, res, digests=dig, entry_hits=hits, host=True)
+        out, digs = self._targets_done(objs, dig)
+        cor = self._correct_results(items, slot0, res, hits)
+        return (out, digs, cor) if digests else (out, cor)
+
+    @staticmethod
+    def _correct_results(items, first, res, hits):
+        """Per item ``(first, first_open, corrected, open, hits)`` from a correcting call's results."""
+        none = _lib.CHK_CONSISTENT
+        out = []
+        for j, it in enumerate(items):
+            bad, fopen = int(res[j]["first"]), int(res[j]["first_open"])
+            out.append((None if bad == none else bad, None if fopen == none else fopen,
+                        int(res[j]["corrected"]), int(res[j]["open"]),
+                        [int(h) for h in hits[first[j]:first[j] + len(it[2])]]))
+        return out
 
     def encode_digest_batch(self, descs: np.ndarray, src, parity, digests, *, host: bool = False,
                             asynchronous: bool = False) -> None:
@@ -890,10 +937,12 @@ class Engine:
                 parts.extend(chunk)
         return parts
 
-def _check_blocks(k: int, m: int, blocks, sharenums, *, spares: bool, targets=(), padlen=None) -> None:
+def _check_blocks(k: int, m: int, blocks, sharenums, *, spares: bool, targets=(), padlen=None,
+                  held_targets: bool = False) -> None:
     """The core of the check_*_item preconditions, in the library's order: the block count
     (exactly k, or with `spares` any n with k <= n <= m), equal lengths, 1 <= k <= m <= 256,
-    sharenums and targets in [0, m) and all distinct, and with `padlen` 0 <= padlen <= k*B."""
+    sharenums and targets in [0, m) and all distinct (with `held_targets`: each of the two
+    distinct in itself), and with `padlen` 0 <= padlen <= k*B."""
     n = len(blocks)
     if len(sharenums) != n or (n != k and not spares):
         raise Error(_lib.strerror(_lib.SEC_ENBLOCKS))
@@ -908,7 +957,11 @@ def _check_blocks(k: int, m: int, blocks, sharenums, *, spares: bool, targets=()
     nums = [int(x) for x in sharenums] + [int(x) for x in targets]
     if any(x < 0 or x >= m for x in nums):
         raise Error(_lib.strerror(_lib.SEC_ESHARENUM))
-    if len(set(nums)) != len(nums):
+    if held_targets:
+        groups = [nums[:n], nums[n:]]
+    else:
+        groups = [nums]
+    if any(len(set(g)) != len(g) for g in groups):
         raise Error(_lib.strerror(_lib.SEC_EDUPSHARE))
     if padlen is not None and not (0 <= padlen <= k * B):
         raise Error(_lib.strerror(_lib.SEC_EPADLEN))
@@ -963,6 +1016,13 @@ def check_repair_check_item(k: int, m: int, blocks, sharenums, targets) -> None:
     GPU work): n equal-length blocks and n sharenums, 1 <= k <= m <= 256, k <= n <= m, sharenums
     and targets in [0, m), all distinct, no target among the blocks held.  Raises Error."""
     _check_blocks(k, m, blocks, sharenums, spares=True, targets=targets)
+
+
+def check_repair_correct_item(k: int, m: int, blocks, sharenums, targets) -> None:
+    """The repair + correct preconditions for one chunk: check_repair_check_item's, in its order,
+    except that a target may be one of the blocks held (a heal target); the targets are distinct
+    among themselves.  Raises Error."""
+    _check_blocks(k, m, blocks, sharenums, spares=True, targets=targets, held_targets=True)
 
 
 # -- matrices (host arithmetic; no device needed) ------------------------------

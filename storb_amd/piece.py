@@ -68,7 +68,8 @@ from .constants import MAX_PIECE_SIZE, MIN_PIECE_SIZE, PIECE_LENGTH_OFFSET, PIEC
 from .easyfec import Decoder, Encoder, Error
 from .engine import (Engine, EngineGroup, _decoded_len, _decoded_starts, check_decode_check_item,
                      check_decode_correct_item, check_decode_ids_item, check_decode_item, check_locate,
-                     check_repair_check_item, choose_blocks, device_count, get_engine, spread_threads)
+                     check_repair_check_item, check_repair_correct_item, choose_blocks, device_count, get_engine,
+                     spread_threads)
 
 logger = logging.getLogger(__name__)
 
@@ -82,7 +83,7 @@ __all__ = [
     "repair_pieces_checked", "ChunkIdCheck", "PieceIdError",
     "decode_chunks_id_checked", "reconstruct_data_id_checked", "reconstruct_data_stream_id_checked",
     "ChunkCorrection", "PieceCorrectionError", "decode_chunks_corrected", "reconstruct_data_corrected",
-    "reconstruct_data_stream_corrected",
+    "reconstruct_data_stream_corrected", "repair_chunks_corrected", "repair_pieces_corrected",
 ]
 
 PREFETCH_PIECE_IDS = True  # encode_chunk hashes its pieces on a thread pool (see module doc)
@@ -1223,8 +1224,21 @@ class ChunkCorrection(BaseModel):
     open_positions: int = 0  # offsets that disagree and that no single piece's change explains
     first_open_offset: typing.Optional[int] = None  # the lowest of them
     # piece_idx -> offsets at which that piece was the one changed; the keys are the pieces to
-    # regenerate: repair_pieces(rest, targets=list(damaged))
+    # heal: repair_pieces_corrected(chunk) returns each of them whole and corrected, from the same
+    # held pieces, even where fewer than k of them are undamaged
     damaged: dict[int, int] = Field(default_factory=dict)
+
+
+def _note_correction(ck: ChunkCorrection, piece_idx, found) -> None:
+    """One chunk's result of a correcting engine call (``(first, first_open, corrected, open,
+    hits)``, hits in the order of `piece_idx`) into its ``ChunkCorrection``."""
+    first, first_open, corrected, opened, hits = found
+    ck.consistent = first is None
+    ck.first_bad_offset = first
+    ck.corrected_positions = corrected
+    ck.open_positions = opened
+    ck.first_open_offset = first_open
+    ck.damaged = {int(idx): h for idx, h in zip(piece_idx, hits) if h}
 
 
 class PieceCorrectionError(ValueError):
@@ -1275,14 +1289,8 @@ def decode_chunks_corrected(encoded_chunks: typing.Sequence[EncodedChunk]) -> tu
     starts = _decoded_starts(full)
     parts, at, f = [], 0, 0
     view = memoryview(data)
-    for i, (first, first_open, corrected, opened, hits) in zip(redo, cor):
-        ck = out[i]
-        ck.consistent = first is None
-        ck.first_bad_offset = first
-        ck.corrected_positions = corrected
-        ck.open_positions = opened
-        ck.first_open_offset = first_open
-        ck.damaged = {int(idx): h for idx, h in zip(full[i][3], hits) if h}
+    for i, found in zip(redo, cor):
+        _note_correction(out[i], full[i][3], found)
         n = starts[i + 1] - starts[i]
         parts.append(view[at:starts[i]])
         parts.append(memoryview(fixed)[f:f + n])
@@ -1320,6 +1328,78 @@ def reconstruct_data_stream_corrected(pieces: list[Piece], chunks: list[EncodedC
         pieces, list(zip(chunks)), window_bytes, decode_chunks_corrected, lambda ck: not ck.open_positions,
         lambda ck, seen: PieceCorrectionError(
             f"Held pieces disagree beyond what one piece per offset explains in chunk {ck.chunk_idx}", seen))
+
+
+def repair_chunks_corrected(chunks: typing.Sequence[EncodedChunk], targets=None, *, piece_ids: bool = False,
+                            heal: bool = True) -> tuple[list[list[Piece]], list[ChunkCorrection]]:
+    """``repair_chunks_checked`` that corrects instead of dropping: per chunk the regenerated
+    pieces, the damaged held pieces healed, and what was found.
+
+    Round one is ``repair_chunks_checked``'s fused call (``Engine.repair_check_host``), with the
+    pieces ordered as there, so clean input costs exactly what it costs there and launches nothing
+    new.  The chunks it reports inconsistent, and only those, go through ONE
+    ``Engine.repair_correct_host`` call, which judges every byte offset's column of pieces as
+    ``check_locate`` does and makes every piece from the corrected column.  targets: as
+    ``repair_chunks``' (default: every absent ``piece_idx``; explicit targets must be absent).
+    With ``heal`` that call's targets are followed by every held piece, so damage is healed even
+    where fewer than k undamaged pieces are left, as long as no two pieces are damaged at the same
+    offset; healing is never in place, the held pieces are not written.
+
+    A chunk returns its requested targets in order, then, with ``heal``, the held pieces whose
+    hit count is nonzero, in ascending ``piece_idx``, each the whole corrected piece (regenerated
+    copies of undamaged held pieces are dropped); with ``piece_ids`` every returned piece is a
+    ``ProcessedPieceInfo`` carrying the id the GPU hashed from it.  The ``ChunkCorrection`` is
+    filled as ``decode_chunks_corrected`` fills it; with ``heal`` the keys of ``damaged`` are
+    exactly the healed pieces returned.
+
+    A chunk's pieces are trustworthy exactly when its ``open_positions`` is 0.  What that means:
+    with two or more pieces beyond k, an offset where at most one piece is wrong is always put
+    right; with three or more, an offset where two are wrong is always reported open; with exactly
+    two, two wrong bytes at one offset may be attributed to a third piece, which only the recorded
+    piece ids exclude.  With fewer than two spare pieces nothing can be corrected and every bad
+    offset is open; at an open offset a piece holds what the first k pieces as held predict.
+    One device, one call; ``repair_chunks`` and ``repair_chunks_checked`` are unchanged."""
+    chunks = list(chunks)
+    if targets is not None and len(targets) != len(chunks):
+        raise ValueError("repair_chunks_corrected: one target list (or None) per chunk")
+    out: list[ChunkCorrection] = []
+    full = []
+    for i, ch in enumerate(chunks):
+        use = _held_pieces(ch, "repair")
+        out.append(ChunkCorrection(chunk_idx=ch.chunk_idx, checked=len(use), consistent=True))
+        full.append(_check_item(ch, use) + (_targets_of(targets, i, ch, use),))
+    if not chunks:
+        return [], []
+    for it in full:  # every chunk's preconditions before any device work
+        check_repair_check_item(*it)
+    res = get_engine().repair_check_host(full, digests=piece_ids)
+    blocks, digs, checks = res if piece_ids else (res[0], None, res[1])
+    tgs = [it[4] for it in full]
+    redo = [i for i, (first_at, _bad, _column) in enumerate(checks) if first_at is not None]
+    if redo:
+        again = [full[i][:4] + (tgs[i] + (sorted(full[i][3]) if heal else []),) for i in redo]
+        for it in again:
+            check_repair_correct_item(*it)
+        fixed = get_engine().repair_correct_host(again, digests=piece_ids)
+        fblocks, fdigs, cor = fixed if piece_ids else (fixed[0], None, fixed[1])
+        for j, i in enumerate(redo):
+            ck = out[i]
+            _note_correction(ck, full[i][3], cor[j])
+            asked = again[j][4]
+            keep = [q for q, t in enumerate(asked) if q < len(tgs[i]) or t in ck.damaged]
+            tgs[i] = [asked[q] for q in keep]
+            blocks[i] = [fblocks[j][q] for q in keep]
+            if piece_ids:
+                digs[i] = [fdigs[j][q] for q in keep]
+    return _repaired_pieces(chunks, tgs, blocks, digs), out
+
+
+def repair_pieces_corrected(chunk: EncodedChunk, targets=None, *, piece_ids: bool = False,
+                            heal: bool = True) -> tuple[list[Piece], ChunkCorrection]:
+    """``repair_chunks_corrected`` for one chunk."""
+    pieces, checks = repair_chunks_corrected([chunk], None if targets is None else [targets], piece_ids=piece_ids,
+                                             heal=heal)
+    return pieces[0], checks[0]
 
 
 class ChunkIdCheck(BaseModel):
