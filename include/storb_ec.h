@@ -543,6 +543,57 @@ int sec_repair_correct_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t
 int sec_check_locate(int k, int m, const int32_t *sharenums, int n, const uint8_t *column,
                      int32_t *culprit);
 
+/* ---- decode + correct and repair + correct, several errors per byte position -------------------
+ * sec_decode_correct_batch and sec_repair_correct_batch put right ONE wrong entry per position,
+ * whatever n - k is.  The n held blocks of a chunk are a Reed-Solomon code of distance r + 1,
+ * r = n - k, which carries floor(r / 2) errors per position; these two calls use it.  They take the
+ * arguments of their namesakes, with the same meaning, and max_errors behind them.  The bound is
+ *     t = min(T, floor(r / 2), 16),  T = max_errors, or no limit when max_errors == 0,
+ * and a position whose column is no code word is
+ *   corrected  when some code word differs from the column in at most t entries.  That word is
+ *              unique (2t <= r).  Every differing entry counts one hit in entry_hits, the position
+ *              counts once in `corrected`, and every output byte there is computed from the
+ *              corrected column (a repair target: its row of the repair matrix times the corrected
+ *              basis column, every changed basis entry applied);
+ *   open       when no such code word exists: the column is left as held, counted in `open`, and the
+ *              outputs there are what the basis as held gives.
+ * sec_cor_result, first, first_open and entry_hits keep their layout and meaning, "the entry
+ * changed" read as "an entry changed".  What this promises:
+ *   - at most t wrong bytes at a position are always put right;
+ *   - more than t and at most r - t wrong bytes are always reported open;
+ *   - beyond r - t the column may lie within t of ANOTHER code word and is then corrected to that
+ *     one: only the piece ids the caller recorded exclude it;
+ *   - with max_errors == 1 results, hits and every output byte equal sec_decode_correct_batch's /
+ *     sec_repair_correct_batch's exactly, for every r.
+ * Heal targets, digests, flags, staging, aliasing, timing (kind 8; sec_ctx_*_methods count none of
+ * it) and the errors with their order are the namesakes'; max_errors < 0 is SEC_EINVAL, reported
+ * with the other SEC_EINVALs, before SEC_EKM.  The kernels are sec_decode_correct_ex_kernel and
+ * sec_repair_correct_ex_kernel: clean lanes decode or repair as vectors exactly as the namesakes'
+ * do; only a lane with a nonzero check delta runs, per position, a bounded-distance decoder
+ * (syndromes from the check deltas, Berlekamp-Massey in exactly 2t steps, a root search over the n
+ * held points, the error values, and the check rows once more on the changed column). */
+int sec_decode_correct_ex_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t nchunks,
+                                const int32_t *sharenums, const uint64_t *block_offs,
+                                const uint64_t *block_avail, const uint8_t *blocks, uint8_t *out,
+                                sec_cor_result *results, uint32_t *entry_hits, int max_errors,
+                                unsigned flags);
+
+int sec_repair_correct_ex_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks,
+                                const int32_t *sharenums, const uint64_t *block_offs,
+                                const uint64_t *block_avail, const uint8_t *blocks,
+                                const int32_t *target_nums, const uint64_t *target_offs,
+                                uint8_t *out, uint8_t *digests, sec_cor_result *results,
+                                uint32_t *entry_hits, int max_errors, unsigned flags);
+
+/* The one-column model of that contract (host arithmetic, no device needed), beside
+ * sec_check_locate.  sharenums: the n block numbers, the first k the basis; column: the n held
+ * bytes of one position.  fixed receives the n corrected bytes; *nchanged = 0: the column is a code
+ * word; 1 .. t: that many entries were changed to reach the one code word within t; -2: open
+ * (fixed = column).  t as above; with max_errors == 1 the verdict is sec_check_locate's.
+ * Errors: sec_check_locate's; SEC_EINVAL also for max_errors < 0 or a NULL fixed or nchanged. */
+int sec_check_correct(int k, int m, const int32_t *sharenums, int n, const uint8_t *column,
+                      int max_errors, uint8_t *fixed, int32_t *nchanged);
+
 /* Whether a chunk of sec_check_batch / sec_decode_check_batch is eligible for the bit-sliced check
  * kernel (host logic, no device needed): *method = 1 when (k, m) is one of the bit-sliced shapes
  * ((10,14), (8,12), (16,24), (32,48), (64,96), (8,11)), B >= 16, n > k, the first k sharenums are

@@ -152,8 +152,14 @@ _SIGS = {
                                               _vp, ctypes.c_uint]),
     "sec_repair_correct_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, ctypes.c_uint]),
+    "sec_decode_correct_ex_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   ctypes.c_int, ctypes.c_uint]),
+    "sec_repair_correct_ex_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, ctypes.c_int, ctypes.c_uint]),
     "sec_check_locate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,
                                         ctypes.POINTER(ctypes.c_int32)]),
+    "sec_check_correct": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp,
+                                         ctypes.POINTER(ctypes.c_int32)]),
     "sec_check_method": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_uint64, _vp,
                                         ctypes.c_int64, ctypes.POINTER(ctypes.c_int)]),
     "sec_ctx_check_methods": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),

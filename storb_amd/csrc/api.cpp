@@ -1830,6 +1830,7 @@ struct RowArgs {
     unsigned flags;
     sec_cor_result *cor;  // decode + correct: its results and (nullable) per-entry hits
     uint32_t *hits;
+    int max_errors = 1;   // the _ex calls (Op::kEx): errors put right per position, 0 = the code's limit
 };
 
 // What a descriptor is made from
@@ -1855,7 +1856,7 @@ int check_held(const RowChunk &c, const RowArgs &a, const int32_t *targets = nul
 struct CheckBsFamily {
     using BsDesc = sec::CbsDesc;
     static constexpr const char *kBsKernel = "sec_check_bs_kernel";
-    static constexpr bool kCorrects = false;
+    static constexpr bool kCorrects = false, kEx = false;
     static bool bs_judged(const RowChunk &c) { return c.n > c.k; }
     static int bs_shape(const Options &o, const RowChunk &c, const int32_t *sn, const uint64_t *avail, bool copies)
     {
@@ -1873,7 +1874,7 @@ struct CheckBsFamily {
 struct RepairBsFamily {
     using BsDesc = sec::RbsDesc;
     static constexpr const char *kBsKernel = "sec_repair_bs_kernel";
-    static constexpr bool kCorrects = false;
+    static constexpr bool kCorrects = false, kEx = false;
     static bool bs_judged(const RowChunk &c) { return c.nt >= 1; }
     static int bs_shape(const Options &o, const RowChunk &c, const int32_t *sn, const uint64_t *avail, bool)
     {
@@ -2066,6 +2067,32 @@ struct RepairCorrectOp : RepairCheckOp {
     static int group_rows(int rows) { return DecodeCorrectOp::group_rows(rows); }
 };
 
+// The two correcting operations with several errors per position (sec_*_correct_ex_batch): the same
+// plan, words and state; a table that carries the held points and weights behind its rows
+// (ex_coef), a plan key bit of their own, and the _ex kernels, which take the call's bound.
+struct DecodeCorrectExOp : DecodeCorrectOp {
+    static constexpr bool kEx = true;
+    static constexpr const char *kTile = "sec_decode_correct_ex_kernel", *kTail = "sec_decode_correct_ex_tail";
+};
+
+struct RepairCorrectExOp : RepairCorrectOp {
+    static constexpr bool kEx = true;
+    static constexpr const char *kTile = "sec_repair_correct_ex_kernel", *kTail = "sec_repair_correct_ex_tail";
+};
+
+// What the _ex kernels' judge needs of a chunk's n entries `nums` (the basis in normalised order,
+// then the check rows), appended to its table's coefficients: x_j, then u_j, then 1 / u_j
+// (gf_host.hpp held_weights)
+void ex_coef(const std::vector<int> &nums, std::vector<uint8_t> &cf)
+{
+    std::vector<uint8_t> x, u;
+    sec::held_weights(nums, x, u);
+    cf.insert(cf.end(), x.begin(), x.end());
+    cf.insert(cf.end(), u.begin(), u.end());
+    for (uint8_t v : u)
+        cf.push_back(sec::gf().inv[v]);
+}
+
 // What sec_decode_correct_final reads of an operation's slots
 sec::CorSlots final_slots(const sec::CorSlots &sl) { return sl; }
 sec::CorSlots final_slots(const sec::RCorSlots &sl)
@@ -2202,11 +2229,25 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
         if (rows.empty())
             return 0;
         key = rows_key(chunks[i].k, chunks[i].m, idx, rows);
+        if (Op::kEx) {
+            // the table with ex_coef's 3n coefficients behind its rows.  They depend on which of the
+            // rows are check rows (the held entries), which the rows' concatenation does not say:
+            // the key carries the split, so chunks that share it share basis, entries and table
+            key += "|x" + std::to_string(ns_of[i]);
+            return (size_t)chunks[i].k * rows.size() + 3 * (size_t)Op::view(chunks[i]).n;
+        }
         return (size_t)chunks[i].k * rows.size();
     };
     auto coef = [&](int64_t i, std::vector<uint8_t> &cf) {
         const int *idx = rows_of(i);
-        return rows_coef(chunks[i].k, chunks[i].m, idx, rows, cf);
+        RC(rows_coef(chunks[i].k, chunks[i].m, idx, rows, cf));
+        if (Op::kEx) {
+            const RowChunk c = Op::view(chunks[i]);
+            sn.assign(idx, idx + c.k);
+            sn.insert(sn.end(), a.sharenums + c.slot0 + c.k, a.sharenums + c.slot0 + c.n);
+            ex_coef(sn, cf);
+        }
+        return (int)SEC_OK;
     };
     RC(resolve_tables(ctx, tc, nchunks, slack_double, want, coef, tab_of, pending));
     const int bs_lanes = ctx->opt.lanes(O_BS_LANES);
@@ -2383,7 +2424,7 @@ int build_row_plan(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchun
 // launches sec_check_final alone is untimed.
 template <class Op>
 int launch_row_sub(sec_ctx *ctx, const SubPlan &sp, bool host, const uint8_t *blocks, uint8_t *out, uint8_t *digests,
-                   sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, hipStream_t s)
+                   sec::ChkResult *results, uint8_t *row_bad, uint8_t *column, hipStream_t s, uint32_t tmax = 0)
 {
     const RowOpState &st = ctx->row_ops[Op::kId];
     const Plan &plan = st.plan;
@@ -2408,12 +2449,12 @@ int launch_row_sub(sec_ctx *ctx, const SubPlan &sp, bool host, const uint8_t *bl
     }
     if constexpr (Op::kCorrects) {  // its own kernels; results: sec::CorResult, row_bad: the hits words
         for (const Group &g : sp.groups) {
-            int e = sec_launch_correct(g.rows, blocks, out, dd, dt + g.first, g.count, tabs, sl, s);
+            int e = sec_launch_correct(g.rows, blocks, out, dd, dt + g.first, g.count, tabs, sl, s, tmax);
             if (e)
                 return hip_fail((hipError_t)e, Op::kTile);
         }
-        int e =
-            sec_launch_correct_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl, s);
+        int e = sec_launch_correct_tail(blocks, out, dd, plan.meta.as<sec::TailItem>(sp.off_tail), sp.ntail, tabs, sl,
+                                        s, tmax);
         if (e)
             return hip_fail((hipError_t)e, Op::kTail);
         e = sec_launch_correct_final(dd, sp.nentries, final_slots(sl), (sec::CorResult *)results, (uint32_t *)row_bad,
@@ -2571,7 +2612,7 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
     const bool has_results = Op::kCorrects ? a.cor != nullptr : a.results != nullptr;
     if (!ctx || nchunks < 0 ||
         (nchunks > 0 && (!chunks || !a.sharenums || !a.block_offs || (Op::kChecks && !has_results))) ||
-        (a.flags & ~allowed) || ((a.flags & SEC_F_HOST) && (a.flags & SEC_F_ASYNC)))
+        (a.flags & ~allowed) || ((a.flags & SEC_F_HOST) && (a.flags & SEC_F_ASYNC)) || (Op::kEx && a.max_errors < 0))
         return SEC_EINVAL;
     if (nchunks == 0)
         return SEC_OK;
@@ -2579,6 +2620,9 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
         return SEC_EINVAL;
     const bool host = a.flags & SEC_F_HOST;
     const bool digest = a.digests != nullptr;
+    // the _ex kernels' bound (never 0: that selects the kernels of one error); a launch argument, no part of the plan
+    const uint32_t tmax =
+        !Op::kEx ? 0u : a.max_errors == 0 ? (uint32_t)sec::kMaxErrors : (uint32_t)std::min(a.max_errors, sec::kMaxErrors);
     RC(set_dev(ctx));
 
     // preconditions of every chunk before any device work, in the operation's own order
@@ -2626,7 +2670,8 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
         }
     }
     key.put((a.flags & (SEC_F_HOST | SEC_F_RECOVER)) | (!host && a.block_avail ? 0x10000u : 0u) |
-            (digest ? 0x20000u : 0u) | (Op::kCorrects && Op::kTargets ? 0x40000u : 0u));  // (kId 4 serves two)
+            (digest ? 0x20000u : 0u) | (Op::kCorrects && Op::kTargets ? 0x40000u : 0u) |  // (kId 4 serves two,
+            (Op::kEx ? 0x80000u : 0u));                                                   // each in two forms)
     const bool reuse = plan_reusable(plan, st.tabs, key);
     SlotLayout L;
     if (!reuse || host)
@@ -2657,7 +2702,7 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
     if (!host) {
         RC(launch_row_sub<Op>(ctx, plan.subs[0], false, a.blocks, a.out, a.digests,
                               Op::kCorrects ? (sec::ChkResult *)a.cor : (sec::ChkResult *)a.results,
-                              Op::kCorrects ? (uint8_t *)a.hits : a.row_bad, a.column, ctx->stream()));
+                              Op::kCorrects ? (uint8_t *)a.hits : a.row_bad, a.column, ctx->stream(), tmax));
         if (!(a.flags & SEC_F_ASYNC))
             CK(hipStreamSynchronize(ctx->stream()));
         return SEC_OK;
@@ -2724,7 +2769,7 @@ int row_op(sec_ctx *ctx, const typename Op::Chunk *chunks, int64_t nchunks, cons
     auto launch = [&](const SubPlan &sp, uint8_t *din, uint8_t *dout, hipStream_t s) {
         return launch_row_sub<Op>(ctx, sp, true, din, dout, dout + sp.dig_off, (sec::ChkResult *)dout,
                                   a.row_bad || a.hits ? dout + sp.chk_rows : nullptr,
-                                  a.column ? dout + sp.chk_col : nullptr, s);
+                                  a.column ? dout + sp.chk_col : nullptr, s, tmax);
     };
     RC(run_pipeline(ctx, plan, gather, scatter, launch));
     if (Op::kChecks && a.column)
@@ -4509,6 +4554,33 @@ int sec_repair_correct_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t
     return row_op<RepairCorrectOp>(ctx, chunks, nchunks, a);
 }
 
+int sec_decode_correct_ex_batch(sec_ctx *ctx, const sec_dchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                                const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
+                                uint8_t *out, sec_cor_result *results, uint32_t *entry_hits, int max_errors,
+                                unsigned flags)
+{
+    RowArgs a{sharenums, block_offs, block_avail, blocks, nullptr, nullptr, out, nullptr,
+              nullptr, nullptr, nullptr, flags};
+    a.cor = results;
+    a.hits = entry_hits;
+    a.max_errors = max_errors;
+    return row_op<DecodeCorrectExOp>(ctx, chunks, nchunks, a);
+}
+
+int sec_repair_correct_ex_batch(sec_ctx *ctx, const sec_rchk_chunk *chunks, int64_t nchunks, const int32_t *sharenums,
+                                const uint64_t *block_offs, const uint64_t *block_avail, const uint8_t *blocks,
+                                const int32_t *target_nums, const uint64_t *target_offs, uint8_t *out,
+                                uint8_t *digests, sec_cor_result *results, uint32_t *entry_hits, int max_errors,
+                                unsigned flags)
+{
+    RowArgs a{sharenums, block_offs, block_avail, blocks, target_nums, target_offs, out, digests,
+              nullptr, nullptr, nullptr, flags};
+    a.cor = results;
+    a.hits = entry_hits;
+    a.max_errors = max_errors;
+    return row_op<RepairCorrectExOp>(ctx, chunks, nchunks, a);
+}
+
 int sec_check_method(int k, int m, const int32_t *sharenums, int n, uint64_t B, const uint64_t *block_avail,
                      int64_t padlen, int *method)
 {
@@ -4542,6 +4614,19 @@ int sec_check_locate(int k, int m, const int32_t *sharenums, int n, const uint8_
     if (!sec::check_locate(k, m, std::vector<int>(sharenums, sharenums + n), column, &who))
         return SEC_ESINGULAR;
     *culprit = who;
+    return SEC_OK;
+}
+
+int sec_check_correct(int k, int m, const int32_t *sharenums, int n, const uint8_t *column, int max_errors,
+                      uint8_t *fixed, int32_t *nchanged)
+{
+    RC(check_blocks(k, m, sharenums, k, sharenums ? sharenums + k : nullptr, n - k, true));
+    if (!column || !fixed || !nchanged || max_errors < 0)
+        return SEC_EINVAL;
+    int changed = -2;
+    if (!sec::check_correct(k, m, std::vector<int>(sharenums, sharenums + n), column, max_errors, fixed, &changed))
+        return SEC_ESINGULAR;
+    *nchanged = changed;
     return SEC_OK;
 }
 

@@ -273,4 +273,162 @@ inline bool check_locate(int k, int m, const std::vector<int> &sharenums, const 
     return true;
 }
 
+// ---- bounded-distance correction of one column (sec_check_correct) ---------------------------
+// zfec's code is an evaluation code: block i of a column is f(p_i), deg f < k, p_i = point(i).  So
+// any n held blocks with points x_j are a Reed-Solomon code of distance r + 1, r = n - k, and with
+//     u_j = 1 / prod_{i != j} (x_j + x_i)
+// the syndromes S_l = sum_j u_j x_j^l y_j, l < r (0^0 = 1), vanish exactly on code words.
+constexpr int kMaxErrors = 16;  // the kernels' state per position holds no more
+
+// t = min(max_errors, floor(r / 2), kMaxErrors); max_errors = 0: the code's limit
+inline int error_bound(int r, int max_errors)
+{
+    int t = r / 2 < kMaxErrors ? r / 2 : kMaxErrors;
+    if (max_errors > 0 && max_errors < t)
+        t = max_errors;
+    return t < 0 ? 0 : t;
+}
+
+// x_j and u_j of the held blocks `nums` (distinct)
+inline void held_weights(const std::vector<int> &nums, std::vector<uint8_t> &x, std::vector<uint8_t> &u)
+{
+    const Gf &g = gf();
+    const size_t n = nums.size();
+    x.resize(n);
+    u.resize(n);
+    for (size_t j = 0; j < n; ++j)
+        x[j] = point(nums[j]);
+    for (size_t j = 0; j < n; ++j) {
+        uint8_t p = 1;
+        for (size_t i = 0; i < n; ++i)
+            if (i != j)
+                p = g.mul(p, x[j] ^ x[i]);
+        u[j] = g.inv[p];
+    }
+}
+
+// The code word within t = error_bound(n - k, max_errors) entries of `column`, if there is one (it is
+// unique: 2t <= r).  fixed: the n corrected bytes; *nchanged: 0 for a code word, 1 .. t the entries
+// changed, -2 open (fixed = column).  The kernels' judge (kernels.hip corx_judge) step for step:
+//   * the check deltas d_j, as check_locate's.  The column less the code word its basis spans is zero
+//     on the basis and d_j on check row j, and syndromes are linear, so S_l = sum_j u_j x_j^l d_j
+//     over the r check rows alone, l < 2t;
+//   * Berlekamp-Massey, exactly 2t steps: the shortest recurrence S_i = sum_{1..L} C_q S_{i-q}; with
+//     errors on a set E of at most t entries L = |E| and C(z) = prod_E (1 + x_j z).  L > t: open;
+//   * the roots among the n held points of R(z) = sum_q C_q z^(L-q) = prod_E (z + x_j), L Horner steps
+//     each.  Block 0's point is 0, a factor 1 of C: its error shows as deg C = L - 1, which makes 0 a
+//     root of R like any other point.  Other than L roots: open;
+//   * the values: with Q(z) = R(z) / (z + x_j) = sum_l q_l z^l (synthetic division),
+//     sum_l q_l S_l = u_j e_j Q(x_j), so e_j = sum_l q_l S_l / (Q(x_j) u_j); a zero value: open;
+//   * the check rows once more on the changed column: any nonzero delta, open.  This makes the
+//     verdict exact whatever the steps before it did.
+// More than t and at most r - t wrong entries are therefore always open; beyond r - t the column may
+// lie within t of another code word and is corrected to that.  false: singular basis (never).
+inline bool check_correct(int k, int m, const std::vector<int> &sharenums, const uint8_t *column, int max_errors,
+                          uint8_t *fixed, int *nchanged)
+{
+    const Gf &g = gf();
+    const int n = (int)sharenums.size(), r = n - k, t = error_bound(r, max_errors);
+    std::vector<int> idx(sharenums.begin(), sharenums.begin() + k), perm;
+    normalise_slots(k, idx, perm);
+    std::vector<uint8_t> rm;
+    if (!repair_matrix(k, m, idx, std::vector<int>(sharenums.begin() + k, sharenums.end()), rm))
+        return false;
+    auto deltas = [&](const uint8_t *col, std::vector<uint8_t> &d) {
+        bool any = false;
+        d.assign((size_t)r, 0);
+        for (int j = 0; j < r; ++j) {
+            uint8_t p = col[k + j];
+            for (int s = 0; s < k; ++s)
+                p ^= g.mul(rm[(size_t)j * k + s], col[perm[s]]);
+            d[j] = p;
+            any |= p != 0;
+        }
+        return any;
+    };
+    memcpy(fixed, column, (size_t)n);
+    std::vector<uint8_t> d;
+    if (!deltas(column, d)) {
+        *nchanged = 0;
+        return true;
+    }
+    *nchanged = -2;
+    if (t == 0)
+        return true;
+    std::vector<uint8_t> x, u;
+    held_weights(sharenums, x, u);
+    uint8_t S[2 * kMaxErrors] = {0}, C[kMaxErrors + 1] = {1}, Bp[kMaxErrors + 1] = {1};
+    for (int j = 0; j < r; ++j) {
+        uint8_t term = g.mul(u[k + j], d[j]);
+        for (int l = 0; l < 2 * t; ++l) {
+            S[l] ^= term;
+            term = g.mul(term, x[k + j]);
+        }
+    }
+    int L = 0, sh = 1;
+    uint8_t b = 1;
+    for (int i = 0; i < 2 * t; ++i) {
+        uint8_t dd = S[i];
+        for (int q = 1; q <= kMaxErrors; ++q)
+            if (q <= L && q <= i)
+                dd ^= g.mul(C[q], S[i - q]);
+        if (dd == 0) {
+            ++sh;
+            continue;
+        }
+        const uint8_t f = g.mul(dd, g.inv[b]);
+        const bool grow = 2 * L <= i;
+        for (int q = kMaxErrors; q >= 0; --q) {  // C += f z^sh B, and B = the old C where L grows, in place
+            const uint8_t c = C[q];
+            if (q >= sh)
+                C[q] = c ^ g.mul(f, Bp[q - sh]);
+            if (grow)
+                Bp[q] = c;
+        }
+        if (grow) {
+            L = i + 1 - L;
+            b = dd;
+            sh = 1;
+        } else {
+            ++sh;
+        }
+    }
+    if (L > t)
+        return true;
+    int loc[kMaxErrors], nloc = 0;
+    for (int j = 0; j < n; ++j) {
+        uint8_t v = 0;
+        for (int q = 0; q <= L; ++q)
+            v = g.mul(v, x[j]) ^ C[q];
+        if (v == 0) {
+            if (nloc == L)
+                return true;
+            loc[nloc++] = j;
+        }
+    }
+    if (nloc != L)
+        return true;
+    for (int a = 0; a < L; ++a) {
+        const int j = loc[a];
+        uint8_t q = 0, num = 0, den = 0;
+        for (int l = L - 1; l >= 0; --l) {
+            q = C[L - 1 - l] ^ g.mul(x[j], q);
+            num ^= g.mul(q, S[l]);
+            den = g.mul(den, x[j]) ^ q;
+        }
+        const uint8_t e = g.mul(g.mul(num, g.inv[den]), g.inv[u[j]]);
+        if (den == 0 || e == 0) {
+            memcpy(fixed, column, (size_t)n);
+            return true;
+        }
+        fixed[j] ^= e;
+    }
+    if (deltas(fixed, d)) {
+        memcpy(fixed, column, (size_t)n);
+        return true;
+    }
+    *nchanged = L;
+    return true;
+}
+
 }  // namespace sec

@@ -1897,18 +1897,336 @@ __device__ __forceinline__ CorVerdict rcor_byte(const u8 *__restrict__ blocks, u
     return f.v;
 }
 
+// Which judge the byte level runs: cor_judge (one error), or corx_judge with the call's bound
+struct CorOne {};
+struct CorMany {
+    u32 tmax;  // min(max_errors, 16), 16 for max_errors == 0; a chunk's t = min(tmax, nr / 2)
+};
+
 template <int R, bool WAVE = true>
 __device__ __forceinline__ void cor_pos(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
-                                        const u32 *__restrict__ tabs, const sec::CorSlots sl, u32 p)
+                                        const u32 *__restrict__ tabs, const sec::CorSlots sl, u32 p, CorOne = {})
 {
     cor_tally<WAVE>(d, sl, p, cor_byte<R>(blocks, out, d, tabs, sl, p));
 }
 
 template <int R, bool WAVE = true>
 __device__ __forceinline__ void cor_pos(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
-                                        const u32 *__restrict__ tabs, const sec::RCorSlots sl, u32 p)
+                                        const u32 *__restrict__ tabs, const sec::RCorSlots sl, u32 p, CorOne = {})
 {
     cor_tally<WAVE>(d, sl, p, rcor_byte<R>(blocks, out, d, tabs, sl, p));
+}
+
+// ---- the byte level with several errors per position (sec_*_correct_ex_kernel) -----------------
+// The judge is a bounded-distance Reed-Solomon decoder on one column, gf_host.hpp check_correct step
+// for step (the reasoning is there): syndromes from the check deltas, Berlekamp-Massey, the roots of
+// the reversed connection polynomial among the n held points (piece 0's point, 0, is a root like any
+// other there), the error values by synthetic division, and the check rows once more on the changed
+// column, which makes the verdict exact.  The chunk's table carries, behind its k * (e + nr) row
+// coefficients, 3n more in entry order (basis slots, then check rows): x_j, u_j and 1 / u_j, each
+// expanded like a coefficient, so every product by one of them is gf_mul_byte (the judge needs them
+// in no other way).  Products of two variables go through c_gf.
+//
+// State per position: 32 syndromes, two polynomials of 17 coefficients and 16 (entry, value) fixes,
+// all indexed at run time, so they live in LDS, byte i of lane l at i * 256 + l (four lanes to a
+// dword, no two lanes on one bank's different dwords).  The fixes' entries take the place of
+// Berlekamp-Massey's second polynomial, which is dead once the locator stands: 82 bytes per lane,
+// 20.5 KiB per workgroup, so seven workgroups fit a CU's 160 KiB as seven waves per SIMD do the
+// registers of the R = 2 kernels.  Every loop is bounded by a constant or a chunk field: 2t
+// Berlekamp-Massey steps, n root evaluations of L <= 16 Horner steps, nr rows to verify.  A miscount
+// gives a wrong verdict, which the verification turns into open.
+constexpr u32 kCxT = 16;  // sec::kMaxErrors (gf_host.hpp)
+constexpr u32 kCxS = 0, kCxC = 2 * kCxT, kCxB = kCxC + kCxT + 1, kCxSlot = kCxB, kCxVal = kCxB + kCxT + 1,
+              kCxBytes = kCxVal + kCxT;
+
+struct CxState {
+    u8 *p;
+    __device__ __forceinline__ u8 &at(u32 i) const { return p[i * 256u]; }
+    __device__ __forceinline__ u8 &S(u32 i) const { return at(kCxS + i); }
+    __device__ __forceinline__ u8 &C(u32 i) const { return at(kCxC + i); }
+    __device__ __forceinline__ u8 &B(u32 i) const { return at(kCxB + i); }
+    __device__ __forceinline__ u8 &slot(u32 i) const { return at(kCxSlot + i); }
+    __device__ __forceinline__ u8 &val(u32 i) const { return at(kCxVal + i); }
+};
+
+// The calling lane's slice (kernels of 256 lanes)
+__device__ __forceinline__ CxState cx_state()
+{
+    __shared__ u8 s_cx[kCxBytes * 256u];
+    return {s_cx + threadIdx.x};
+}
+
+__device__ __forceinline__ u32 gf_mul2(u32 a, u32 b)
+{
+    return a && b ? (u32)c_gf.exp[(u32)c_gf.log[a] + (u32)c_gf.log[b]] : 0u;
+}
+
+__device__ __forceinline__ u32 gf_div2(u32 a, u32 b)  // b != 0
+{
+    return a ? (u32)c_gf.exp[(u32)c_gf.log[a] + 255u - (u32)c_gf.log[b]] : 0u;
+}
+
+struct CxVerdict {
+    bool bad, open;
+    u32 nfix;  // entries changed: st.slot(f) (kernel order), st.val(f), f < nfix
+};
+
+// cor_byte_rows with the first nfix fixes of st applied to the basis bytes
+template <int R, class Slots>
+__device__ __forceinline__ void corx_byte_rows(u32 (&acc)[R], const u8 *__restrict__ blocks, const sec::CorDesc &d,
+                                               const u32 *__restrict__ tabs, const Slots sl, u32 p, u32 row0,
+                                               u32 rlast, const CxState st, u32 nfix)
+{
+    const u32 k = d.k, nrows = d.e + d.nr;
+    for (u32 c0 = 0; c0 < k; c0 += kBatch) {
+        u32 x[kBatch];
+        load_slot_bytes(x, blocks, sl, d.slot0, c0, k, p);
+        for (u32 f = 0; f < nfix; ++f) {
+            const u32 s = st.slot(f), v = st.val(f);
+#pragma unroll
+            for (u32 q = 0; q < kBatch; ++q)
+                x[q] ^= s == c0 + q ? v : 0u;
+        }
+#pragma unroll
+        for (u32 q = 0; q < kBatch; ++q)
+            if (c0 + q < k) {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    acc[r] ^= gf_mul_byte(
+                        tabs + d.tab + ((c0 + q) * nrows + min(row0 + (u32)r, rlast)) * sec::kTabDwords, x[q]);
+            }
+    }
+}
+
+template <int R, class Slots>
+__device__ __forceinline__ CxVerdict corx_judge(const u8 *__restrict__ blocks, const sec::CorDesc &d,
+                                                const u32 *__restrict__ tabs, const Slots sl, u32 p, u32 tmax,
+                                                const CxState st)
+{
+    const u32 k = d.k, e = d.e, nr = d.nr, nrows = e + nr, n = k + nr;
+    const u32 t = min(min(tmax, nr / 2), kCxT);
+    const u32 *xt = tabs + d.tab + k * nrows * sec::kTabDwords;  // read only when t > 0: the chunk then has a table
+    auto xtab = [&](u32 j) { return xt + j * sec::kTabDwords; };
+    auto utab = [&](u32 j) { return xt + (n + j) * sec::kTabDwords; };
+    auto vtab = [&](u32 j) { return xt + (2 * n + j) * sec::kTabDwords; };
+    // the deltas of check rows g0 .. g0 + R - 1 (those past nr - 1 repeat row nr - 1) of the column with the
+    // first nfix fixes applied
+    auto deltas = [&](u32 (&acc)[R], u32 g0, u32 nfix) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const u32 ent = d.slot0 + k + min(g0 + (u32)r, nr - 1);
+            acc[r] = p < sl.avail[ent] ? (u32)blocks[sl.off[ent] + p] : 0u;
+        }
+        for (u32 f = 0; f < nfix; ++f) {
+            const u32 s = st.slot(f), v = st.val(f);
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                acc[r] ^= s == k + min(g0 + (u32)r, nr - 1) ? v : 0u;
+        }
+        corx_byte_rows<R>(acc, blocks, d, tabs, sl, p, e + g0, nrows - 1, st, nfix);
+    };
+    for (u32 l = 0; l < 2 * t; ++l)
+        st.S(l) = 0;
+    bool bad = false;
+    for (u32 g0 = 0; g0 < nr; g0 += R) {
+        u32 acc[R];
+        deltas(acc, g0, 0u);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const u32 j = g0 + r;
+            if (j < nr && acc[r]) {
+                bad = true;
+                if (t) {  // S_l ^= u_j x_j^l d_j
+                    u32 term = gf_mul_byte(utab(k + j), acc[r]);
+                    for (u32 l = 0; l < 2 * t; ++l) {
+                        st.S(l) ^= (u8)term;
+                        term = gf_mul_byte(xtab(k + j), term);
+                    }
+                }
+            }
+        }
+    }
+    if (!bad)
+        return {false, false, 0u};
+    if (t == 0)
+        return {true, true, 0u};
+    // Berlekamp-Massey, 2t steps: S_i = sum_{q = 1 .. L} C_q S_{i - q}
+    for (u32 q = 0; q <= kCxT; ++q)
+        st.C(q) = st.B(q) = q == 0;
+    u32 L = 0, sh = 1, b = 1;
+    for (u32 i = 0; i < 2 * t; ++i) {
+        u32 dd = st.S(i);
+        const u32 qn = min(min(L, i), kCxT);
+        for (u32 q = 1; q <= qn; ++q)
+            dd ^= gf_mul2(st.C(q), st.S(i - q));
+        if (dd == 0) {
+            ++sh;
+            continue;
+        }
+        const u32 f = gf_div2(dd, b);
+        const bool grow = 2 * L <= i;
+        for (int q = (int)kCxT; q >= 0; --q) {  // C += f z^sh B, and B = the old C where L grows, in place
+            const u32 c = st.C(q);
+            if ((u32)q >= sh)
+                st.C(q) = (u8)(c ^ gf_mul2(f, st.B((u32)q - sh)));
+            if (grow)
+                st.B(q) = (u8)c;
+        }
+        if (grow) {
+            L = i + 1 - L;
+            b = dd;
+            sh = 1;
+        } else {
+            ++sh;
+        }
+    }
+    if (L > t)
+        return {true, true, 0u};
+    // the roots of R(z) = sum_q C_q z^(L - q) among the held points
+    u32 nloc = 0;
+    for (u32 j = 0; j < n; ++j) {
+        u32 v = 0;
+        for (u32 q = 0; q <= L; ++q)
+            v = gf_mul_byte(xtab(j), v) ^ st.C(q);
+        if (v == 0) {
+            if (nloc < L)
+                st.slot(nloc) = (u8)j;
+            ++nloc;
+        }
+    }
+    if (nloc != L)
+        return {true, true, 0u};
+    bool ok = true;
+    for (u32 a = 0; a < L; ++a) {
+        const u32 j = st.slot(a);
+        u32 q = 0, num = 0, den = 0;
+        for (int l = (int)L - 1; l >= 0; --l) {
+            q = st.C(L - 1 - (u32)l) ^ gf_mul_byte(xtab(j), q);
+            num ^= gf_mul2(q, st.S((u32)l));
+            den = gf_mul_byte(xtab(j), den) ^ q;
+        }
+        const u32 ev = den ? gf_mul_byte(vtab(j), gf_div2(num, den)) : 0u;
+        ok = ok && ev != 0;
+        st.val(a) = (u8)ev;
+    }
+    for (u32 g0 = 0; ok && g0 < nr; g0 += R) {  // the check rows once more, on the changed column
+        u32 acc[R];
+        deltas(acc, g0, L);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (g0 + r < nr && acc[r])
+                ok = false;
+    }
+    return ok ? CxVerdict{true, false, L} : CxVerdict{true, true, 0u};
+}
+
+// The decode's output part (cor_byte's) from the basis column with nfix fixes applied
+template <int R>
+__device__ __forceinline__ void corx_store(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
+                                           const u32 *__restrict__ tabs, const sec::CorSlots sl, u32 p,
+                                           const CxState st, u32 nfix)
+{
+    const u32 k = d.k, e = d.e;
+    u8 *dst = out + d.out_off + p;
+    for (u32 c0 = 0; c0 < k; c0 += kBatch) {
+        u32 x[kBatch];
+        load_slot_bytes(x, blocks, sl, d.slot0, c0, k, p);
+        for (u32 f = 0; f < nfix; ++f) {
+            const u32 s = st.slot(f), v = st.val(f);
+#pragma unroll
+            for (u32 q = 0; q < kBatch; ++q)
+                x[q] ^= s == c0 + q ? v : 0u;
+        }
+#pragma unroll
+        for (u32 q = 0; q < kBatch; ++q)
+            if (c0 + q < k) {
+                const u32 orow = sl.row[d.slot0 + c0 + q];
+                if (orow != 0xFFFFFFFFu && (u64)orow * d.B + p < d.n)
+                    dst[(u64)orow * d.B] = (u8)x[q];
+            }
+    }
+    for (u32 g0 = 0; g0 < e; g0 += R) {
+        u32 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            acc[r] = 0u;
+        corx_byte_rows<R>(acc, blocks, d, tabs, sl, p, g0, e - 1, st, nfix);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (g0 + r < e) {
+                const u32 orow = sl.miss[d.slot0 + g0 + r];
+                if ((u64)orow * d.B + p < d.n)
+                    dst[(u64)orow * d.B] = (u8)acc[r];
+            }
+    }
+}
+
+// The repair's output part (rcor_byte's): every target's row times the basis column with nfix fixes applied
+template <int R>
+__device__ __forceinline__ void corx_store(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
+                                           const u32 *__restrict__ tabs, const sec::RCorSlots sl, u32 p,
+                                           const CxState st, u32 nfix)
+{
+    const u32 nt = d.e;
+    for (u32 g0 = 0; g0 < nt; g0 += R) {
+        u32 acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            acc[r] = 0u;
+        corx_byte_rows<R>(acc, blocks, d, tabs, sl, p, g0, nt - 1, st, nfix);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (g0 + r < nt)
+                out[sl.tgt_off[d.tgt0 + g0 + r] + p] = (u8)acc[r];
+    }
+}
+
+// cor_tally with up to 16 hits per position: the position counts once in `corrected`, every changed
+// entry once in its own word
+template <bool WAVE, class Slots>
+__device__ __forceinline__ void corx_tally(const sec::CorDesc &d, const Slots sl, u32 p, const CxVerdict v,
+                                           const CxState st)
+{
+    u32 *f = sl.flags + d.flag0, *c = sl.flags + d.cnt0;
+    if (v.bad)
+        min_word(f, p);
+    if (v.open)
+        min_word(f + 1, p);
+    if constexpr (!WAVE) {
+        if (v.nfix)
+            atomicAdd(c, 1u);
+        for (u32 a = 0; a < v.nfix; ++a)
+            atomicAdd(c + 2 + st.slot(a), 1u);
+        if (v.open)
+            atomicAdd(c + 1, 1u);
+        return;
+    }
+    wave_count(c, v.nfix != 0);
+    wave_count(c + 1, v.open);
+    // per fix index, one atomic per distinct entry among the wave's active lanes (both loops are
+    // wave-uniform and bounded: ballots decide them, and every pass clears its leader's bit)
+    for (u32 a = 0; a < kCxT; ++a) {
+        const int h = a < v.nfix ? (int)st.slot(a) : -1;
+        u64 rem = __ballot(h >= 0);
+        for (int pass = 0; pass < 64 && rem; ++pass) {
+            const u32 lead = (u32)__builtin_ctzll(rem);
+            const int hl = __builtin_amdgcn_readlane(h, (int)lead);
+            const u64 m = __ballot(h == hl);
+            if (cor_lane() == lead)
+                atomicAdd(c + 2 + hl, (u32)__builtin_popcountll(m));
+            rem &= ~m;
+        }
+    }
+}
+
+template <int R, bool WAVE = true, class Slots>
+__device__ __forceinline__ void cor_pos(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
+                                        const u32 *__restrict__ tabs, const Slots sl, u32 p, CorMany j)
+{
+    const CxState st = cx_state();
+    const CxVerdict v = corx_judge<R>(blocks, d, tabs, sl, p, j.tmax, st);
+    corx_store<R>(blocks, out, d, tabs, sl, p, st, v.nfix);
+    corx_tally<WAVE>(d, sl, p, v, st);
 }
 
 constexpr int kCorBatch = 8;  // slots per load batch of cor_rows
@@ -1976,16 +2294,16 @@ __device__ __forceinline__ u32 cor_lane_deltas(u32x4 (&acc)[R], const u8 *__rest
 }
 
 // A lane's 16 whole positions [pos, pos + 16), all below `valid`
-template <int R>
+template <int R, class J = CorOne>
 __device__ __forceinline__ void cor_main(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
-                                         u32 pos, const u32 *__restrict__ tabs, const sec::CorSlots sl)
+                                         u32 pos, const u32 *__restrict__ tabs, const sec::CorSlots sl, J j = {})
 {
     const u32 k = d.k, e = d.e;
     u32x4 acc[R];
     const u32 any = cor_lane_deltas<R>(acc, blocks, d, pos, tabs, sl);
     if (any) {
         for (u32 i = 0; i < (u32)sec::kLaneBytes; ++i)
-            cor_pos<R>(blocks, out, d, tabs, sl, pos + i);
+            cor_pos<R>(blocks, out, d, tabs, sl, pos + i, j);
         return;
     }
     u8 *dst = out + d.out_off + pos;
@@ -2048,6 +2366,45 @@ __global__ __launch_bounds__(256) void sec_decode_correct_tail(const u8 *__restr
     cor_pos<4, false>(blocks, out, d, tabs, sl, it.t);
 }
 
+// The same two kernels with corx_judge at the byte level (sec_decode_correct_ex_batch): a lane whose
+// check deltas OR to zero takes cor_main's vector path unchanged
+template <int R>
+__global__ __launch_bounds__(sec::kLanes) void sec_decode_correct_ex_kernel(const u8 *__restrict__ blocks,
+                                                                            u8 *__restrict__ out,
+                                                                            const sec::CorDesc *__restrict__ descs,
+                                                                            const sec::Tile *__restrict__ tiles,
+                                                                            const u32 *__restrict__ tabs,
+                                                                            const sec::CorSlots sl, const u32 tmax)
+{
+    const sec::Tile tl = sec::own_tile(tiles);
+    const sec::CorDesc d = descs[tl.chunk];
+    const CorMany j{tmax};
+    const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
+    if (t + sec::kLaneBytes <= d.valid) {
+        cor_main<R>(blocks, out, d, t, tabs, sl, j);
+    } else if (t < d.valid) {  // the lane that straddles `valid`
+        for (u32 p = t; p < d.valid; ++p)
+            cor_pos<R>(blocks, out, d, tabs, sl, p, j);
+    }
+    if (tl.ntail)
+        for (u32 i = ragged_lane0(d.valid, tl.t0); i < tl.ntail; i += blockDim.x)
+            cor_pos<R>(blocks, out, d, tabs, sl, d.valid + i, j);
+}
+
+__global__ __launch_bounds__(256) void sec_decode_correct_ex_tail(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                                  const sec::CorDesc *__restrict__ descs,
+                                                                  const sec::TailItem *__restrict__ items, u32 nitems,
+                                                                  const u32 *__restrict__ tabs, const sec::CorSlots sl,
+                                                                  const u32 tmax)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nitems)
+        return;
+    const sec::TailItem it = items[i];
+    const sec::CorDesc d = descs[it.chunk];
+    cor_pos<4, false>(blocks, out, d, tabs, sl, it.t, CorMany{tmax});
+}
+
 // One thread per entry, after the kernels above: the entry's counter into hits (the caller's
 // order); the chunk's first entry also turns the chunk's words into its result.
 __global__ __launch_bounds__(256) void sec_decode_correct_final(const sec::CorDesc *__restrict__ descs, u32 nentries,
@@ -2083,16 +2440,16 @@ __global__ __launch_bounds__(256) void sec_decode_correct_final(const sec::CorDe
 // straddles `valid`, the ragged end [valid, B) and the tail kernel's chunks go byte by byte
 // (rcor_byte), and no output byte is written twice.  valid = min(B, every entry's avail): every
 // target byte up to B is stored.
-template <int R>
+template <int R, class J = CorOne>
 __device__ __forceinline__ void rcor_main(const u8 *__restrict__ blocks, u8 *__restrict__ out, const sec::CorDesc &d,
-                                          u32 pos, const u32 *__restrict__ tabs, const sec::RCorSlots sl)
+                                          u32 pos, const u32 *__restrict__ tabs, const sec::RCorSlots sl, J j = {})
 {
     const u32 nt = d.e;
     u32x4 acc[R];
     const u32 any = cor_lane_deltas<R>(acc, blocks, d, pos, tabs, sl);
     if (any) {
         for (u32 i = 0; i < (u32)sec::kLaneBytes; ++i)
-            cor_pos<R>(blocks, out, d, tabs, sl, pos + i);
+            cor_pos<R>(blocks, out, d, tabs, sl, pos + i, j);
         return;
     }
     const u64 *to = sl.tgt_off + d.tgt0;
@@ -2141,6 +2498,44 @@ __global__ __launch_bounds__(256) void sec_repair_correct_tail(const u8 *__restr
     const sec::TailItem it = items[i];
     const sec::CorDesc d = descs[it.chunk];
     cor_pos<4, false>(blocks, out, d, tabs, sl, it.t);
+}
+
+// The same two kernels with corx_judge at the byte level (sec_repair_correct_ex_batch)
+template <int R>
+__global__ __launch_bounds__(sec::kLanes) void sec_repair_correct_ex_kernel(const u8 *__restrict__ blocks,
+                                                                            u8 *__restrict__ out,
+                                                                            const sec::CorDesc *__restrict__ descs,
+                                                                            const sec::Tile *__restrict__ tiles,
+                                                                            const u32 *__restrict__ tabs,
+                                                                            const sec::RCorSlots sl, const u32 tmax)
+{
+    const sec::Tile tl = sec::own_tile(tiles);
+    const sec::CorDesc d = descs[tl.chunk];
+    const CorMany j{tmax};
+    const u32 t = tl.t0 + threadIdx.x * sec::kLaneBytes;
+    if (t + sec::kLaneBytes <= d.valid) {
+        rcor_main<R>(blocks, out, d, t, tabs, sl, j);
+    } else if (t < d.valid) {  // the lane that straddles `valid`
+        for (u32 p = t; p < d.valid; ++p)
+            cor_pos<R>(blocks, out, d, tabs, sl, p, j);
+    }
+    if (tl.ntail)
+        for (u32 i = ragged_lane0(d.valid, tl.t0); i < tl.ntail; i += blockDim.x)
+            cor_pos<R>(blocks, out, d, tabs, sl, d.valid + i, j);
+}
+
+__global__ __launch_bounds__(256) void sec_repair_correct_ex_tail(const u8 *__restrict__ blocks, u8 *__restrict__ out,
+                                                                  const sec::CorDesc *__restrict__ descs,
+                                                                  const sec::TailItem *__restrict__ items, u32 nitems,
+                                                                  const u32 *__restrict__ tabs, const sec::RCorSlots sl,
+                                                                  const u32 tmax)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nitems)
+        return;
+    const sec::TailItem it = items[i];
+    const sec::CorDesc d = descs[it.chunk];
+    cor_pos<4, false>(blocks, out, d, tabs, sl, it.t, CorMany{tmax});
 }
 
 // ---- SHA-1 of pieces (storb piece ids, /root/reference/storb/util/piece.py:54-68) ----
@@ -2706,12 +3101,19 @@ int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uin
 }
 
 int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::Tile *tiles,
-                       uint32_t ntiles, const uint32_t *tabs, sec::CorSlots sl, void *stream)
+                       uint32_t ntiles, const uint32_t *tabs, sec::CorSlots sl, void *stream, uint32_t tmax)
 {
     if (ntiles == 0)
         return hipSuccess;
     const dim3 grid(ntiles), block(sec::kLanes);
     hipStream_t s = (hipStream_t)stream;
+    switch (tmax ? rows : 0) {
+    case 2: return launch(sec_decode_correct_ex_kernel<2>, grid, block, s, blocks, out, descs, tiles, tabs, sl, tmax);
+    case 4: return launch(sec_decode_correct_ex_kernel<4>, grid, block, s, blocks, out, descs, tiles, tabs, sl, tmax);
+    case 8: return launch(sec_decode_correct_ex_kernel<8>, grid, block, s, blocks, out, descs, tiles, tabs, sl, tmax);
+    case 0: break;
+    default: return hipErrorInvalidValue;
+    }
     switch (rows) {
     case 2: return launch(sec_decode_correct_kernel<2>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
     case 4: return launch(sec_decode_correct_kernel<4>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
@@ -2721,21 +3123,31 @@ int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec:
 }
 
 int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::TailItem *items,
-                            uint32_t nitems, const uint32_t *tabs, sec::CorSlots sl, void *stream)
+                            uint32_t nitems, const uint32_t *tabs, sec::CorSlots sl, void *stream, uint32_t tmax)
 {
     if (nitems == 0)
         return hipSuccess;
+    if (tmax)
+        return launch(sec_decode_correct_ex_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks,
+                      out, descs, items, nitems, tabs, sl, tmax);
     return launch(sec_decode_correct_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out,
                   descs, items, nitems, tabs, sl);
 }
 
 int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::Tile *tiles,
-                       uint32_t ntiles, const uint32_t *tabs, sec::RCorSlots sl, void *stream)
+                       uint32_t ntiles, const uint32_t *tabs, sec::RCorSlots sl, void *stream, uint32_t tmax)
 {
     if (ntiles == 0)
         return hipSuccess;
     const dim3 grid(ntiles), block(sec::kLanes);
     hipStream_t s = (hipStream_t)stream;
+    switch (tmax ? rows : 0) {
+    case 2: return launch(sec_repair_correct_ex_kernel<2>, grid, block, s, blocks, out, descs, tiles, tabs, sl, tmax);
+    case 4: return launch(sec_repair_correct_ex_kernel<4>, grid, block, s, blocks, out, descs, tiles, tabs, sl, tmax);
+    case 8: return launch(sec_repair_correct_ex_kernel<8>, grid, block, s, blocks, out, descs, tiles, tabs, sl, tmax);
+    case 0: break;
+    default: return hipErrorInvalidValue;
+    }
     switch (rows) {
     case 2: return launch(sec_repair_correct_kernel<2>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
     case 4: return launch(sec_repair_correct_kernel<4>, grid, block, s, blocks, out, descs, tiles, tabs, sl);
@@ -2745,10 +3157,13 @@ int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec:
 }
 
 int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::TailItem *items,
-                            uint32_t nitems, const uint32_t *tabs, sec::RCorSlots sl, void *stream)
+                            uint32_t nitems, const uint32_t *tabs, sec::RCorSlots sl, void *stream, uint32_t tmax)
 {
     if (nitems == 0)
         return hipSuccess;
+    if (tmax)
+        return launch(sec_repair_correct_ex_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks,
+                      out, descs, items, nitems, tabs, sl, tmax);
     return launch(sec_repair_correct_tail, dim3((nitems + 255) / 256), dim3(256), (hipStream_t)stream, blocks, out,
                   descs, items, nitems, tabs, sl);
 }

@@ -456,16 +456,20 @@ int sec_launch_check_final(const uint8_t *blocks, const sec::ChkDesc *descs, uin
 // positions in groups of `rows` (2, 4 or 8), its byte-granular tail kernel, and, after both, one
 // thread per entry: the chunks' words into results[d.res] and hits[d.cslot0 + ..] (hits nullable)
 int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::Tile *tiles,
-                       uint32_t ntiles, const uint32_t *tabs, sec::CorSlots slots, void *stream);
+                       uint32_t ntiles, const uint32_t *tabs, sec::CorSlots slots, void *stream, uint32_t tmax = 0);
 int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::TailItem *items,
-                            uint32_t nitems, const uint32_t *tabs, sec::CorSlots slots, void *stream);
+                            uint32_t nitems, const uint32_t *tabs, sec::CorSlots slots, void *stream,
+                            uint32_t tmax = 0);
 int sec_launch_correct_final(const sec::CorDesc *descs, uint32_t nentries, sec::CorSlots slots, sec::CorResult *results,
                              uint32_t *hits, void *stream);
+// tmax != 0: the _ex kernels instead (several errors per position, a chunk's bound min(tmax, nr / 2);
+// its table then carries 3n coefficients more, kernels.hip corx_judge), for both operations
 // Repair + correct: sec_repair_correct_kernel and its tail kernel over the same tiles and items, the
 // targets stored whole at their own addresses; its results by sec_launch_correct_final (slots: off,
 // avail, cpos, echunk and flags of the RCorSlots, row / miss unused)
 int sec_launch_correct(int rows, const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::Tile *tiles,
-                       uint32_t ntiles, const uint32_t *tabs, sec::RCorSlots slots, void *stream);
+                       uint32_t ntiles, const uint32_t *tabs, sec::RCorSlots slots, void *stream, uint32_t tmax = 0);
 int sec_launch_correct_tail(const uint8_t *blocks, uint8_t *out, const sec::CorDesc *descs, const sec::TailItem *items,
-                            uint32_t nitems, const uint32_t *tabs, sec::RCorSlots slots, void *stream);
+                            uint32_t nitems, const uint32_t *tabs, sec::RCorSlots slots, void *stream,
+                            uint32_t tmax = 0);
 }

@@ -223,10 +223,11 @@ class Engine:
 
     # -- the repair / check family: shared plumbing ---------------------------
     def _row_call(self, fn, dtype, descs, sharenums, block_offs, block_avail, targets, bufs, *, host, asynchronous,
-                  recover_only=False) -> None:
+                  recover_only=False, extra=()) -> None:
         """One call of the repair / check family: fn(ctx, descs, n, sharenums, block_offs,
-        block_avail, blocks, [target_nums, target_offs,] *outputs, flags).  targets: (target_nums,
-        target_offs) or None; bufs: (blocks, *outputs), each an address, tensor, array or None."""
+        block_avail, blocks, [target_nums, target_offs,] *outputs, *extra, flags).  targets:
+        (target_nums, target_offs) or None; bufs: (blocks, *outputs), each an address, tensor, array
+        or None; extra: integer arguments in front of the flags (the _ex calls' max_errors)."""
         descs = np.ascontiguousarray(descs, dtype=dtype)
         sn = np.ascontiguousarray(sharenums, dtype=np.int32)
         bo = np.ascontiguousarray(block_offs, dtype=np.uint64)
@@ -244,7 +245,7 @@ class Engine:
         if tn is not None:
             args += [_ptr(tn) or None, _ptr(to) or None]
         args += [a or None for a, _ in held[1:]]
-        self._check(fn(self._ctx, _ptr(descs), len(descs), *args,
+        self._check(fn(self._ctx, _ptr(descs), len(descs), *args, *extra,
                        _flags(host, asynchronous, recover_only=recover_only)))
 
     @staticmethod
@@ -453,25 +454,35 @@ class Engine:
 
     def decode_correct_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks, out,
                              results, *, block_avail: np.ndarray | None = None, entry_hits=None, host: bool = False,
-                             asynchronous: bool = False) -> None:
+                             asynchronous: bool = False, max_errors: int = 1) -> None:
         """sec_decode_correct_batch: every byte position's column of each chunk's n entries
         (DCHK_DTYPE descriptors) judged as ``check_locate`` judges it, and `out` what decode_batch
         writes from the first k entries after the one wrong basis byte of a position, if any, is
         put right.  results: one COR_RESULT_DTYPE per chunk; entry_hits (optional): one uint32 per
         slot entry, the positions at which that entry was the one changed; both where the blocks
-        live.  host: host buffers, always staged, every entry gathered once."""
-        self._row_call(self.lib.sec_decode_correct_batch, DCHK_DTYPE, descs, sharenums, block_offs, block_avail, None,
-                       (blocks, out, results, entry_hits), host=host, asynchronous=asynchronous)
+        live.  host: host buffers, always staged, every entry gathered once.
 
-    def decode_correct_host(self, items):
-        """Reassemble host chunks, correcting one wrong block per byte position, in one call.
+        max_errors other than 1: sec_decode_correct_ex_batch, which judges a column as
+        ``check_correct`` does: up to t = min(max_errors, (n - k) // 2, 16) wrong entries of a
+        position are put right (0: the code's limit), each counting a hit; more than t and at most
+        n - k - t are always open."""
+        if max_errors == 1:
+            self._row_call(self.lib.sec_decode_correct_batch, DCHK_DTYPE, descs, sharenums, block_offs, block_avail,
+                           None, (blocks, out, results, entry_hits), host=host, asynchronous=asynchronous)
+            return
+        self._row_call(self.lib.sec_decode_correct_ex_batch, DCHK_DTYPE, descs, sharenums, block_offs, block_avail,
+                       None, (blocks, out, results, entry_hits), host=host, asynchronous=asynchronous,
+                       extra=(int(max_errors),))
+
+    def decode_correct_host(self, items, max_errors: int = 1):
+        """Reassemble host chunks, correcting wrong blocks per byte position, in one call.
 
         items: [(k, m, blocks, sharenums, padlen)] as ``decode_check_host`` takes them.  Returns
         ``(data, results)``: data = every chunk's k*B - padlen bytes concatenated; results = per
         chunk ``(first, first_open, corrected, open, hits)``: the lowest position whose column is
         no code word and the lowest one left open (None: there is none), the counts of corrected
-        and of open positions, and per block of the chunk the positions at which it was the one
-        changed."""
+        and of open positions, and per block of the chunk the positions at which it was changed.
+        max_errors as ``decode_correct_batch``: 1 puts one wrong block of a position right."""
         for it in items:
             check_decode_correct_item(*it)
         if not items:
@@ -484,7 +495,7 @@ class Engine:
         buf = self._out_buffer(max(starts[-1], 1))
         res = np.zeros(len(items), dtype=COR_RESULT_DTYPE)
         hits = np.zeros(sn.size, dtype=np.uint32)
-        self.decode_correct_batch(descs, sn, bo, 0, buf, res, entry_hits=hits, host=True)
+        self.decode_correct_batch(descs, sn, bo, 0, buf, res, entry_hits=hits, host=True, max_errors=max_errors)
         return buf[:starts[-1]].tobytes(), self._correct_results(items, slot0, res, hits)
 
     def repair_check_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
@@ -526,18 +537,24 @@ class Engine:
     def repair_correct_batch(self, descs: np.ndarray, sharenums: np.ndarray, block_offs: np.ndarray, blocks,
                              target_nums: np.ndarray, target_offs: np.ndarray, out, results, *,
                              block_avail: np.ndarray | None = None, digests=None, entry_hits=None,
-                             host: bool = False, asynchronous: bool = False) -> None:
+                             host: bool = False, asynchronous: bool = False, max_errors: int = 1) -> None:
         """sec_repair_correct_batch: every byte position's column of each chunk's n entries
         (RCHK_DTYPE descriptors) judged as ``check_locate`` judges it, and every target written
         whole from the first k entries after the one wrong basis byte of a position, if any, is
         put right.  A target may be a held entry (a heal target).  digests as repair_batch;
         results and entry_hits as decode_correct_batch.  host: host buffers, always staged, every
-        entry gathered once."""
-        self._row_call(self.lib.sec_repair_correct_batch, RCHK_DTYPE, descs, sharenums, block_offs, block_avail,
+        entry gathered once.  max_errors other than 1: sec_repair_correct_ex_batch, the columns
+        judged as ``decode_correct_batch`` says, every changed basis entry applied to a target."""
+        if max_errors == 1:
+            self._row_call(self.lib.sec_repair_correct_batch, RCHK_DTYPE, descs, sharenums, block_offs, block_avail,
+                           (target_nums, target_offs), (blocks, out, digests, results, entry_hits), host=host,
+                           asynchronous=asynchronous)
+            return
+        self._row_call(self.lib.sec_repair_correct_ex_batch, RCHK_DTYPE, descs, sharenums, block_offs, block_avail,
                        (target_nums, target_offs), (blocks, out, digests, results, entry_hits), host=host,
-                       asynchronous=asynchronous)
+                       asynchronous=asynchronous, extra=(int(max_errors),))
 
-    def repair_correct_host(self, items, digests: bool = False):
+    def repair_correct_host(self, items, digests: bool = False, max_errors: int = 1):
         """Blocks of host chunks regenerated or healed from the column-corrected code word, in one
         call.
 
@@ -559,7 +576,8 @@ class Engine:
             descs[j] = (len(blocks[0]), slot0[j], tgt0[j], len(targets), len(blocks), k, m)
         res = np.zeros(len(items), dtype=COR_RESULT_DTYPE)
         hits = np.zeros(sn.size, dtype=np.uint32)
-        self.repair_correct_batch(descs, sn, bo, 0, tn, to, 0, res, digests=dig, entry_hits=hits, host=True)
+        self.repair_correct_batch(descs, sn, bo, 0, tn, to, 0, res, digests=dig, entry_hits=hits, host=True,
+                                  max_errors=max_errors)
         out, digs = self._targets_done(objs, dig)
         cor = self._correct_results(items, slot0, res, hits)
         return (out, digs, cor) if digests else (out, cor)
@@ -1039,6 +1057,26 @@ def check_locate(k: int, m: int, sharenums, column) -> int:
     who = ctypes.c_int32(0)
     check(lib.sec_check_locate(int(k), int(m), _ptr(sn) or None, sn.size, _ptr(col) or None, ctypes.byref(who)), lib)
     return who.value
+
+
+def check_correct(k: int, m: int, sharenums, column, max_errors: int = 0):
+    """The code word within t entries of a column (sec_check_correct), the one-column model of the
+    correcting calls: sharenums = the n held block numbers, the first k the basis, column = their
+    n bytes at one position; t = min(max_errors, (n - k) // 2, 16), max_errors 0 = the code's
+    limit.  Returns ``(fixed, nchanged)``: the n corrected bytes, and 0 for a code word, 1 .. t
+    for that many entries changed, -2 for an open column (fixed = column)."""
+    lib = _lib.load()
+    sn = np.ascontiguousarray([int(x) for x in sharenums], dtype=np.int32)
+    col = np.frombuffer(bytes(column), dtype=np.uint8)
+    if col.size != sn.size:
+        raise ValueError("check_correct: one column byte per sharenum")
+    if max_errors < 0:
+        raise ValueError("check_correct: max_errors is 0 (the code's limit) or a positive bound")
+    fixed = np.zeros(max(col.size, 1), dtype=np.uint8)
+    changed = ctypes.c_int32(0)
+    check(lib.sec_check_correct(int(k), int(m), _ptr(sn) or None, sn.size, _ptr(col) or None, int(max_errors),
+                                _ptr(fixed), ctypes.byref(changed)), lib)
+    return fixed[:col.size].tobytes(), changed.value
 
 
 def repair_method(k: int, m: int, sharenums, targets, B: int, avail=None) -> bool:

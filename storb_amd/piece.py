@@ -49,6 +49,7 @@ Deliberate differences (documented in DESIGN.md §Boundary):
 from __future__ import annotations
 
 import ctypes
+import functools
 import hashlib
 import logging
 import math
@@ -1241,6 +1242,10 @@ def _note_correction(ck: ChunkCorrection, piece_idx, found) -> None:
     ck.damaged = {int(idx): h for idx, h in zip(piece_idx, hits) if h}
 
 
+def _per_offset(max_errors) -> str:
+    return "one piece per offset" if max_errors == 1 else "the pieces correctable per offset"
+
+
 class PieceCorrectionError(ValueError):
     """``reconstruct_data_corrected``: at some offset of some chunk the held pieces disagree and no
     single piece's change explains it, so those bytes cannot be trusted.  ``checks``: every chunk's
@@ -1251,7 +1256,18 @@ class PieceCorrectionError(ValueError):
         self.checks = checks
 
 
-def decode_chunks_corrected(encoded_chunks: typing.Sequence[EncodedChunk]) -> tuple[bytes, list[ChunkCorrection]]:
+def _max_errors_kw(max_errors) -> dict:
+    """The engine keyword of a piece-layer ``max_errors`` (None: the code's limit, the engine's 0).
+    The default, 1, passes nothing: the call is the one made before the keyword existed."""
+    if max_errors is None:
+        return {"max_errors": 0}
+    if int(max_errors) < 1:
+        raise ValueError("max_errors is None (the code's limit) or a positive bound")
+    return {} if int(max_errors) == 1 else {"max_errors": int(max_errors)}
+
+
+def decode_chunks_corrected(encoded_chunks: typing.Sequence[EncodedChunk], *,
+                            max_errors: int | None = 1) -> tuple[bytes, list[ChunkCorrection]]:
     """``decode_chunks_checked`` that corrects instead of dropping: the concatenation of every
     chunk's bytes with one corrupt piece per byte offset put right, and per chunk what was found.
 
@@ -1269,7 +1285,17 @@ def decode_chunks_corrected(encoded_chunks: typing.Sequence[EncodedChunk]) -> tu
     two, two wrong bytes at one offset may be attributed to a third piece, which only the recorded
     piece ids exclude.  With fewer than two spare pieces nothing can be corrected and every bad
     offset is open.  One device, one call; the streaming form is
-    ``reconstruct_data_stream_corrected``."""
+    ``reconstruct_data_stream_corrected``.
+
+    max_errors (default 1: all of the above, byte for byte): how many wrong pieces per byte offset
+    are put right, t = min(max_errors, r // 2, 16) with r the pieces held beyond k; None is the
+    code's limit.  Round one is unchanged, so clean input launches nothing new; the second call
+    then judges a column as ``engine.check_correct`` does.  At most t wrong bytes at an offset are
+    always put right; more than t and at most r - t are always reported open; beyond r - t the
+    column may be corrected to another code word, which only the recorded piece ids exclude.  An
+    offset with several pieces changed counts once in ``corrected_positions`` and once per piece
+    in ``damaged``."""
+    kw = _max_errors_kw(max_errors)
     chunks = list(encoded_chunks)
     out: list[ChunkCorrection] = []
     full = []
@@ -1285,7 +1311,7 @@ def decode_chunks_corrected(encoded_chunks: typing.Sequence[EncodedChunk]) -> tu
     redo = [i for i, (first_at, _bad, _column) in enumerate(res) if first_at is not None]
     if not redo:
         return data, out
-    fixed, cor = get_engine().decode_correct_host([full[i] for i in redo])
+    fixed, cor = get_engine().decode_correct_host([full[i] for i in redo], **kw)
     starts = _decoded_starts(full)
     parts, at, f = [], 0, 0
     view = memoryview(data)
@@ -1300,38 +1326,45 @@ def decode_chunks_corrected(encoded_chunks: typing.Sequence[EncodedChunk]) -> tu
     return b"".join(parts), out
 
 
-def reconstruct_data_corrected(pieces: list[Piece],
-                               chunks: list[EncodedChunk]) -> tuple[bytes, list[ChunkCorrection]]:
+def reconstruct_data_corrected(pieces: list[Piece], chunks: list[EncodedChunk], *,
+                               max_errors: int | None = 1) -> tuple[bytes, list[ChunkCorrection]]:
     """``reconstruct_data`` with one corrupt piece per byte offset put right
     (``decode_chunks_corrected`` over every piece handed over, grouped as ``reconstruct_data``
     groups them).  Raises ``ValueError("Not enough pieces to reconstruct chunk N")`` as
     ``reconstruct_data`` does, before any decode, and ``PieceCorrectionError`` (carrying
     ``.checks``) when some chunk has open positions; otherwise returns the bytes, all trustworthy
-    in ``decode_chunks_corrected``'s sense, and the checks."""
+    in ``decode_chunks_corrected``'s sense, and the checks.  max_errors: as
+    ``decode_chunks_corrected``'s (None: up to (pieces beyond k) // 2 corrupt pieces per offset)."""
     _group_pieces(pieces, chunks)
-    data, checks = decode_chunks_corrected(chunks)
+    data, checks = decode_chunks_corrected(chunks, max_errors=max_errors)
     bad = [ck.chunk_idx for ck in checks if ck.open_positions]
     if bad:
-        raise PieceCorrectionError(f"Held pieces disagree beyond what one piece per offset explains in chunk(s) {bad}",
-                                   checks)
+        raise PieceCorrectionError(f"Held pieces disagree beyond what {_per_offset(max_errors)} explains "
+                                   f"in chunk(s) {bad}", checks)
     return data, checks
 
 
 def reconstruct_data_stream_corrected(pieces: list[Piece], chunks: list[EncodedChunk], *,
-                                      window_bytes: int | None = None) -> Iterator[tuple[bytes, ChunkCorrection]]:
+                                      window_bytes: int | None = None,
+                                      max_errors: int | None = 1) -> Iterator[tuple[bytes, ChunkCorrection]]:
     """``reconstruct_data_corrected``'s contract, delivered as ``reconstruct_data_stream_checked``
     delivers: yield ``(bytes, ChunkCorrection)`` chunk by chunk, in order, each window one
     ``decode_chunks_corrected`` on the stream worker.  ``PieceCorrectionError`` (``.checks``: the
     checks of the chunks seen so far, that chunk's last) is raised when the stream reaches a chunk
-    with open positions, after every earlier chunk has been yielded."""
+    with open positions, after every earlier chunk has been yielded.  max_errors: as
+    ``decode_chunks_corrected``'s."""
+    _max_errors_kw(max_errors)  # a bad bound is refused here, not on the stream worker
+    decode = decode_chunks_corrected if max_errors == 1 else functools.partial(decode_chunks_corrected,
+                                                                               max_errors=max_errors)
     yield from _stream_verified(
-        pieces, list(zip(chunks)), window_bytes, decode_chunks_corrected, lambda ck: not ck.open_positions,
+        pieces, list(zip(chunks)), window_bytes, decode, lambda ck: not ck.open_positions,
         lambda ck, seen: PieceCorrectionError(
-            f"Held pieces disagree beyond what one piece per offset explains in chunk {ck.chunk_idx}", seen))
+            f"Held pieces disagree beyond what {_per_offset(max_errors)} explains in chunk {ck.chunk_idx}", seen))
 
 
 def repair_chunks_corrected(chunks: typing.Sequence[EncodedChunk], targets=None, *, piece_ids: bool = False,
-                            heal: bool = True) -> tuple[list[list[Piece]], list[ChunkCorrection]]:
+                            heal: bool = True,
+                            max_errors: int | None = 1) -> tuple[list[list[Piece]], list[ChunkCorrection]]:
     """``repair_chunks_checked`` that corrects instead of dropping: per chunk the regenerated
     pieces, the damaged held pieces healed, and what was found.
 
@@ -1358,7 +1391,13 @@ def repair_chunks_corrected(chunks: typing.Sequence[EncodedChunk], targets=None,
     two, two wrong bytes at one offset may be attributed to a third piece, which only the recorded
     piece ids exclude.  With fewer than two spare pieces nothing can be corrected and every bad
     offset is open; at an open offset a piece holds what the first k pieces as held predict.
-    One device, one call; ``repair_chunks`` and ``repair_chunks_checked`` are unchanged."""
+    One device, one call; ``repair_chunks`` and ``repair_chunks_checked`` are unchanged.
+
+    max_errors (default 1: all of the above, byte for byte): as ``decode_chunks_corrected``'s.  With
+    t = min(max_errors, r // 2, 16), None the code's limit, up to t wrong pieces per offset are put
+    right and every piece is made from the column with all of them corrected; more than t and at
+    most r - t are always open; beyond r - t a column may be corrected to another code word."""
+    kw = _max_errors_kw(max_errors)
     chunks = list(chunks)
     if targets is not None and len(targets) != len(chunks):
         raise ValueError("repair_chunks_corrected: one target list (or None) per chunk")
@@ -1380,7 +1419,7 @@ def repair_chunks_corrected(chunks: typing.Sequence[EncodedChunk], targets=None,
         again = [full[i][:4] + (tgs[i] + (sorted(full[i][3]) if heal else []),) for i in redo]
         for it in again:
             check_repair_correct_item(*it)
-        fixed = get_engine().repair_correct_host(again, digests=piece_ids)
+        fixed = get_engine().repair_correct_host(again, digests=piece_ids, **kw)
         fblocks, fdigs, cor = fixed if piece_ids else (fixed[0], None, fixed[1])
         for j, i in enumerate(redo):
             ck = out[i]
@@ -1394,11 +1433,11 @@ def repair_chunks_corrected(chunks: typing.Sequence[EncodedChunk], targets=None,
     return _repaired_pieces(chunks, tgs, blocks, digs), out
 
 
-def repair_pieces_corrected(chunk: EncodedChunk, targets=None, *, piece_ids: bool = False,
-                            heal: bool = True) -> tuple[list[Piece], ChunkCorrection]:
+def repair_pieces_corrected(chunk: EncodedChunk, targets=None, *, piece_ids: bool = False, heal: bool = True,
+                            max_errors: int | None = 1) -> tuple[list[Piece], ChunkCorrection]:
     """``repair_chunks_corrected`` for one chunk."""
     pieces, checks = repair_chunks_corrected([chunk], None if targets is None else [targets], piece_ids=piece_ids,
-                                             heal=heal)
+                                             heal=heal, max_errors=max_errors)
     return pieces[0], checks[0]
 
 
